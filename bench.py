@@ -36,6 +36,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_MAX_PIXELS = 1 << 21   # --dump-outputs: 24 B per pixel (f64 index + 3 x f32 xyz + f32 valid) -> at most 50.3 MB
 
 
 def measured_traffic(px_per_launch, kernel="dense"):
@@ -100,7 +101,16 @@ def parse():
     ap.add_argument("--rendezvous-timeout", type=float, default=180.0, help="seconds init_process_group / a collective may wait for the other ranks (N>1)")
     ap.add_argument("--check", action="store_true", help="add SHA-256 digests of the assembled results (dense and compacted) to the line")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="rows of one view timed on the CPU (0 = whole view)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed launch computed (xyz and valid of every view; a fixed seeded "
+                         "sample of the pixels above %d of them) to DIR/{pixel_index,xyz,valid}.npy, float32 / float64, at most 64 MB"
+                         % DUMP_MAX_PIXELS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.idle_only or args.one_view_cold_only or args.families_only):
+        ap.error("--dump-outputs writes the outputs of the timed launches of one GPU: not with --gpus > 1 or the *-only modes")
+    return args
 
 
 class _DevMem:
@@ -698,6 +708,8 @@ def main():
     dt = time.perf_counter() - t0
     dt = dmod.max_over_ranks(dt, red_dev)
     ev_ms = dmod.max_over_ranks(ev_ms, red_dev)
+    # before any later leg launches on this context again: the results of the last timed launch
+    dumped = dump_outputs(np, sc, n_views, rows, W, args.dump_outputs) if args.dump_outputs else None
 
     px_per_launch = n_views * rows * W                     # pixels one launch processes on one GPU
     px_per_step = n_views * H * W                          # ... and all ranks together
@@ -727,6 +739,8 @@ def main():
                      "kernel": kernel_name, "algorithmic_bytes_per_pixel": alg_bytes_px,
                      "pixels_per_launch": px_per_launch, "avg_launch_ms": round(launch_s * 1e3, 4)},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
 
     # end to end from device-resident frames to compacted clouds: ONE launch, the compaction of
     # 8/save_point_cloud.cpp:85-104 happens inside the fused kernel (sl3d_run_clouds), plus the read-back of the counts;
@@ -913,6 +927,38 @@ def single_rank_digests(np, sc, n_views):
     for c in sc.fused_clouds(0, n_views):
         hc.update(c.tobytes())
     return {"dense_sha256": hd.hexdigest(), "compact_sha256": hc.hexdigest()}
+
+
+def dump_outputs(np, sc, n_views, rows, W, out_dir, seed=0):
+    """--dump-outputs: what a caller of the timed launch receives, the dense xyz and the valid map of every view, as DIR/xyz.npy
+    (n, 3) float32 (0 where the pixel is invalid) and DIR/valid.npy (n,) float32 (0 / 1).  DIR/pixel_index.npy (n,) float64 holds
+    each pixel's flat index into [view][row][col]: every pixel up to DUMP_MAX_PIXELS, above that a sorted sample drawn with a
+    fixed seed, so two runs with the same arguments write the same pixels."""
+    px_view = rows * W
+    total = n_views * px_view
+    if total <= DUMP_MAX_PIXELS:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(total, size=DUMP_MAX_PIXELS, replace=False))
+    xyz = np.empty((len(idx), 3), dtype=np.float32)
+    valid = np.empty(len(idx), dtype=np.float32)
+    bounds = np.searchsorted(idx, np.arange(n_views + 1) * px_view)
+    for v in range(n_views):
+        lo, hi = bounds[v], bounds[v + 1]
+        if lo < hi:
+            p, m = sc.points(v)
+            local = idx[lo:hi] - v * px_view
+            xyz[lo:hi] = p.reshape(-1, 3)[local]
+            valid[lo:hi] = m.reshape(-1)[local]
+    # the library's NaN marks an invalid pixel, which valid.npy already says: the files hold finite numbers only (a NaN at a
+    # VALID pixel would be a defect and is kept)
+    xyz[valid == 0] = 0.0
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "xyz.npy"), xyz)
+    np.save(os.path.join(out_dir, "valid.npy"), valid)
+    return {"dir": out_dir, "files": ["pixel_index.npy", "xyz.npy", "valid.npy"], "pixels": int(len(idx)), "of_pixels": int(total),
+            "sample_seed": seed if len(idx) < total else None}
 
 
 def syn_full_mask(W, H):
