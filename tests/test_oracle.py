@@ -403,3 +403,47 @@ def test_restated_opencv_routines_against_independent_implementations():
         F = np.array([Ac[2, 3] * cu - Ac[0, 3], Ac[2, 3] * cv - Ac[1, 3], Ap[2, 3] * pu - Ap[0, 3], Ap[2, 3] * pv - Ap[1, 3]])
         X = np.linalg.lstsq(P, F, rcond=None)[0]
         assert np.linalg.norm(X - pts[r, c]) <= 1e-9 * max(1.0, np.linalg.norm(X))
+
+
+def test_stage7_pinned_on_reference_point_cloud():
+    """T0-T3 and O1 pinned on the reference's own output: Point_cloud/test data/point_cloud_2.ply (tests/golden/ply_stage7.npz).
+    The synthetic capture of tests/ply_capture.py decodes, at every vertex pixel (c, r), the projector pixel (x, y) whose
+    triangulation the reference wrote; the oracle's literal stages 3 -> 8 must give those correspondences, a valid map set on exactly
+    those pixels, and the PLY's floats in the PLY's order -- bit for bit apart from the recorded exceptions (1 ulp each: where the
+    reference's own fp64 arithmetic rounds the other way, make_golden.py::ply_stage7).  The independent NumPy restatement
+    (make_golden.py::independent_stage_5_7) on the oracle's unwrapped phases is the second restatement: within 1 ulp everywhere."""
+    import os
+    import sys
+    from conftest import GOLDEN, ROOT
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, GOLDEN)
+    import make_golden as MG
+    import ply_capture as PC
+    fx = PC.load_fixture()
+    cal, dims = golden_calibration()
+    n = len(fx["xyz"])
+    tup, ref = PC.matched_tuples(fx), PC.matched_xyz(fx)
+    assert len(tup) == n - len(fx["unmatched_index"]) and len(tup) >= 0.999 * n
+    mask, planes_v, planes_h = PC.capture(fx)
+    o = Oracle(PC.W, PC.H, PC.PW, PC.PH, PC.N_V, PC.N_H, PC.FW, PC.FW, ncodes_v=PC.NCODES_V, ncodes_h=PC.NCODES_H)
+    o.set_mask(mask)
+    o.set_calibration(*cal)
+    o.run_scan(list(planes_v), list(planes_h))
+    vm = o.valid_map(2) == 1
+    assert np.array_equal(vm, PC.vertex_map(fx))
+    cp = o.c_p_map()
+    assert np.array_equal(cp[tup[:, 1], tup[:, 0]], tup[:, 2:])
+    cloud = o.point_cloud()
+    assert cloud.shape == ref.shape
+    d = MG.ulp_distance(cloud, ref).max(-1)
+    # the exceptions, by index into the PLY: exactly the recorded ones, by exactly the recorded distance
+    matched_index = np.nonzero(fx["tuples"][:, 0] >= 0)[0]
+    assert np.array_equal(matched_index[d > 0], fx["inexact_index"])
+    assert np.array_equal(d[d > 0], fx["inexact_ulp"]) and int(d.max()) <= 1
+    assert int((d == 0).sum()) == len(tup) - len(fx["inexact_index"]) >= 0.99 * n
+    # second restatement on the same phases
+    iv, icp, ipts = MG.independent_stage_5_7(o.unwrapped_phi(0), o.unwrapped_phi(1), o.valid_map(0), o.valid_map(1),
+                                             {k: c for k, c in zip(("Kc", "dc", "rc", "tc", "Kp", "dp", "rp", "tp"), cal)})
+    assert np.array_equal(iv, vm) and np.array_equal(icp[vm], cp[vm])
+    ind = ipts[tup[:, 1], tup[:, 0]].astype(np.float32)
+    assert int(MG.ulp_distance(ind, ref).max()) <= 1 and int(MG.ulp_distance(ind, cloud).max()) <= 1
