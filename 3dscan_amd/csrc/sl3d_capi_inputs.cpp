@@ -38,7 +38,7 @@ bool quads_known(const sl3d_ctx *x, int view, unsigned *quads)
 }
 
 // true if every view of [first, first + n) is known to be sparsely selected (fewer than 65 % of its quads hold a valid pixel): a
-// launch over such views takes the instantiation whose every plane request waits for the valid bits (choose_fused: the large-launch
+// launch over such views takes the instantiation whose every plane request waits for the valid bits (fused_key: the large-launch
 // kernel without early requests, also for a small launch).  A view whose count is still on its way -- the reference's loop sets a new
 // selection and launches at once, scan after scan -- is routed by the last count that did arrive (the lasso of one scan is about as
 // large as that of the scan before; the route decides time only, never results); a view that never had a complete count is dense:

@@ -54,14 +54,12 @@ try {
 }
 SL3D_CATCH(x)
 
-// every fused launch of the library goes through here: the kernel is chosen by what is known about the views' masks NOW, and the
-// choice is recorded (sl3d_last_fused_kernel_name reports the instantiation that ran, not a later prediction)
 // can the launch over views [first_view, first_view + n_views) evaluate their (deferred) selections itself?  Every view's mask is
 // deferred, in one layout, and the launch has a MASKIN instantiation.  (Views known -- by their LAST counts -- to be sparsely selected take
 // the gated MASKIN form, whose plane requests wait for the valid bits the launch has just evaluated: launch_fused.)
 bool maskin_launch(const sl3d_ctx *x, int first_view, int n_views, bool keep)
 {
-    if (x->n_pending == 0 || !fused_maskin_available(x->P, x->rig, n_views, keep)) return false;
+    if (x->n_pending == 0 || fused_choice(x->P, x->rig, n_views, keep, 0, false, true).nmax == 0) return false;
     const sl3d_ctx::PendingMask &p0 = x->pend[(size_t)first_view];
     for (int v = first_view; v < first_view + n_views; v++) {
         const sl3d_ctx::PendingMask &pm = x->pend[(size_t)v];
@@ -133,16 +131,13 @@ int small_launch_overlaps(sl3d_ctx *x, int first_view, int n_views, bool *overla
     return *overlap ? SL3D_OK : lanes_wait(x);
 }
 
+// every fused launch of the library goes through here: the kernel is chosen by what is known about the views' masks NOW, and
+// launch_fused records the instantiation that ran (sl3d_last_fused_kernel_name reports it, not a later prediction)
 // may_overlap: the caller (sl3d_run, sl3d_run_clouds) took the QUIET form of ON_DEVICE for a small launch on a context with lanes
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
     const bool prefer_gated = sparse_views(x, first_view, n_views);
     const bool maskin = maskin_launch(x, first_view, n_views, keep);
-    x->last_fused.n_views = n_views;
-    x->last_fused.cmode = cmode;
-    x->last_fused.keep = keep;
-    x->last_fused.prefer_gated = prefer_gated;
-    x->last_fused.maskin = maskin;
     hipStream_t st = x->stream;
     int lane = -1;
     struct Count {  // (where the launch went, whichever return below is taken)
@@ -159,7 +154,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
             if ((rc = lane_begin(x, first_view, n_views, &lane))) return rc;
             st = x->lane[lane];
         }
-        rc = launched(x, launch_fused(x->P, x->d_cal, x->rig, first_view, n_views, keep, cmode, st, prefer_gated));
+        rc = launched(x, launch_fused(x->P, x->d_cal, x->rig, first_view, n_views, keep, cmode, st, prefer_gated, nullptr, x->last_fused));
         if (!rc && lane >= 0) x->lp.end(lane, first_view, n_views);
         return rc;
     }
@@ -189,7 +184,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
     mi.part = x->d_mi_part;
     mi.part_stride = x->mi_part_stride;
     mi.seq = seq & 0xffffffu;
-    const int rc = launched(x, launch_fused(x->P, x->d_cal, x->rig, first_view, n_views, keep, cmode, st, prefer_gated, &mi));
+    const int rc = launched(x, launch_fused(x->P, x->d_cal, x->rig, first_view, n_views, keep, cmode, st, prefer_gated, &mi, x->last_fused));
     if (!rc && lane >= 0) x->lp.end(lane, first_view, n_views);
     return rc;
 }
@@ -205,9 +200,8 @@ extern "C" int sl3d_launch_counts(sl3d_ctx *x, int64_t *on_stream, int64_t *on_l
 extern "C" int sl3d_last_fused_kernel_name(sl3d_ctx *x, char *buf, size_t capacity)
 try {
     if (!x || !buf || capacity == 0) return fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: null argument");
-    if (x->last_fused.n_views < 1) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
-    const int n = fused_kernel_name(x->P, x->rig, x->last_fused.n_views, x->last_fused.keep, x->last_fused.cmode, buf, capacity, x->last_fused.prefer_gated,
-                                    x->last_fused.maskin);
+    if (x->last_fused.nmax == 0) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
+    const int n = fused_key_name(x->last_fused, buf, capacity);
     return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: buffer too small");
 }
 SL3D_CATCH(x)
@@ -233,7 +227,7 @@ try {
     if (!x || !buf || capacity == 0 || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: null argument");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called (the rig class is part of the name)");
     const bool fits = n_views <= x->cfg.max_views, gated = fits && sparse_views(x, 0, n_views);
-    const int n = fused_kernel_name(x->P, x->rig, n_views, x->keep, clouds ? 2 : 0, buf, capacity, gated, fits && maskin_launch(x, 0, n_views, x->keep));
+    const int n = fused_key_name(fused_choice(x->P, x->rig, n_views, x->keep, clouds ? 2 : 0, gated, fits && maskin_launch(x, 0, n_views, x->keep)), buf, capacity);
     return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: buffer too small");
 }
 SL3D_CATCH(x)

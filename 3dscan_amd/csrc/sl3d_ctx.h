@@ -66,8 +66,8 @@ struct sl3d_ctx {
     unsigned *d_mi_part = nullptr;
     unsigned mi_part_stride = 0, mi_part_words = 0;
     std::vector<uint8_t> quad_kind;           // [max_views] whose words hold the view's count: 0 = k_mask_prepare's blocks, 1 = a MASKIN launch's waves
-    // the fused launch made last on this context (sl3d_last_fused_kernel_name: the instantiation that RAN, not a prediction)
-    struct { int n_views = 0, cmode = 0; bool keep = false, prefer_gated = false, maskin = false; } last_fused;
+    // the instantiation the fused launch made last on this context RAN (launch_fused; nmax == 0: none yet)
+    FusedKey last_fused;
     float *d_points = nullptr;
     unsigned *d_blk_cnt = nullptr;            // compaction scratch: per-1024-pixel block counts,
     unsigned long long *d_blk_off = nullptr;  // their exclusive scan, and the total

@@ -3,7 +3,7 @@
 // One lane owns 4 horizontally adjacent pixels = one dword of every 8-bit plane, so a wave reads 256 contiguous bytes of each of
 // the 2F+2Nv+2Nh planes (coalesced) and writes 3 KiB of xyz + 256 B of valid.  No MFMA: this is a per-pixel map bounded by HBM
 // bandwidth and by fp64 VALU.  The kernel is a template; its instantiations are compiled by the sl3d_fused_*.hip translation units
-// (one family each, in parallel) and picked by launch_fused (sl3d_fused_launch.hip).
+// (a few families each, in parallel) and picked by launch_fused (sl3d_fused_launch.hip) by the rule of sl3d_fused_choice.h.
 //
 // The body of k_fused is a sequence of named phases, each a __device__ __forceinline__ function below:
 //   item_begin        what depends on the pixel only: tile -> row / column, the first valid-map dword, camera-side T1 (cam_table_*)
@@ -20,12 +20,11 @@
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
+#include <utility>
 #include "sl3d_device.h"
 #include "sl3d_maskbits.h"
 
-#define SL3D_BLOCK 256 /* threads per block: a block is a 1024-pixel tile of the scan, 4 waves = 4 segments of 256 pixels */
-#define SL3D_OCC 4     /* waves per SIMD the fused kernel is compiled for (128 VGPRs) */
-#define SL3D_SMALL_BLOCK SL3D_BLOCK /* the small-launch instantiation keeps 256-thread blocks too (round 4: 128 / 64 threads +-0.5 %) */
+#define SL3D_OCC 4     /* waves per SIMD the fused kernel is compiled for (128 VGPRs; SL3D_BLOCK / SL3D_SMALL_BLOCK: sl3d_internal.h) */
 
 // measurement only (tools/ab.sh builds with -DSL3D_MEASURE -DSL3D_ABLATE=n): 2 = no mask reads, 4 = no xyz stores.  Results are wrong
 // by construction; the shipped build has neither the compile-time switch nor the run-time hooks (SL3D_VPT / SL3D_CAMTAB
@@ -202,7 +201,7 @@ struct Item {
 // radial model), kind 2 = the normalised point itself (tangential terms).  Request and use are separate so that the small-launch
 // instantiation can put its plane requests in between.
 // KIND2 = false (the MASKIN instantiations): the two-double kind is not compiled in -- its 16 registers between request and use are
-// what the launch's mask words live in; a calibration with tangential camera terms keeps the two-kernel route (fused_maskin_available).
+// what the launch's mask words live in; a calibration with tangential camera terms keeps the two-kernel route (sl3d_fused_choice.h: fused_key).
 template <bool KIND2 = true>
 __device__ __forceinline__ void cam_table_request(const KParams &P, const Item &it, double (&t)[8])
 {
@@ -577,7 +576,7 @@ __device__ __forceinline__ void issue_gray(const KParams &P, int view, unsigned 
         const int N = a == 0 ? Nv : Nh;
         // (PLANES == 2 needs N >= 1 on both axes: an axis WITHOUT Gray planes has no plane of its own to pad with, and its padded loads
         // would read whatever follows the axis -- for the last axis of the last resident view the first bytes past the frame stack.
-        // choose_fused sends such pattern sets to the per-plane-test kernel)
+        // fused_key sends such pattern sets to the per-plane-test kernel)
         const unsigned pg = (unsigned)((a == 0 ? 0 : F + 2 * Nv) + F) * psv;
         // (behind an empty asm: everything derived from it is loop-invariant, and 40 hoisted plane offsets + 20 masks are more
         // SGPRs than there are)
@@ -1210,150 +1209,31 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
     }
 }
 
-// ---- launch plumbing -------------------------------------------------------------------------------------------------------------
-// Instantiations: the timed 3-step kernel exists for every N = 6..12 with both axes equal (EXACT), as padded straight-line code for
-// every NMAX = 6..12 (any other pair of axes up to NMAX planes -- issue_gray; the 4-/5-step fringes have this form only) and with
-// the unroll bound 16 beyond; the parity mode uses the bounds 8 / 12 / 16 with per-plane tests.  Dense 3-step launches
-// of at most SL3D_SMALL_LAUNCH_VIEWS views take the instantiation without the LDS reciprocal table (re-measured with the streaming
-// stores: 8 views 185.6-187.5 us through it against 183.8-184.7, 16 views +-0: stays at 4).
-struct FusedChoice {
-    int nmax;
-    bool exact, small;  // exact: both axes have exactly nmax planes.  (!exact, timed kernels, nmax <= 12: the padded form, issue_gray)
-    bool early;         // the last template argument (EARLY): see k_fused
+// ---- instantiation ------------------------------------------------------------------------------------------------------------------
+// fused_table<FAMILY>: one launcher per key of the family (sl3d_fused_choice.h: fused_family).  Each sl3d_fused_*.hip unit instantiates
+// the families it compiles explicitly; launch_fused (sl3d_fused_launch.hip) sees the declaration only.
+template <int FAMILY>
+struct FusedFamilyOf {
+    static constexpr FusedFamily keys = fused_family(FAMILY);
+    template <int I>
+    static void launch(unsigned gx, unsigned gy, unsigned block, void *st, const KParams &P, const DevCal *C, int first_view, int n_views, int vpt)
+    {
+        constexpr FusedKey k = keys.key[I];
+        hipLaunchKernelGGL((k_fused<k.keep, k.nmax, k.fgen, k.exact, k.rig, k.cmode, k.rcpt, k.early>), dim3(gx, gy, 1), dim3(block, 1, 1), 0, (hipStream_t)st, P,
+                           C, first_view, n_views, vpt);
+    }
+    template <int... I>
+    static FusedTable table(std::integer_sequence<int, I...>)
+    {
+        static constexpr FusedEntry entry[] = {{keys.key[I], &launch<I>}...};
+        return {entry, (int)sizeof...(I)};
+    }
 };
-// prefer_gated: the views of the launch are sparsely selected -- a small launch then takes the large-launch instantiation, whose
-// plane requests wait for the valid bits instead of going out first (one view of 1080p with 19 % of the frame selected, as in the
-// reference's real captures: 15.8 us against 22.2; a full frame: 26.9 against 24.6 -- profiles/r04_sparse_mask.txt)
-// rig: the rig class the launch runs (0 = the un-pipelined general kernel: no early requests there)
-inline FusedChoice choose_fused(bool keep, bool fgen, int cmode, int nv, int nh, int n_views, bool prefer_gated, int rig)
+template <int FAMILY>
+FusedTable fused_table()
 {
-    FusedChoice c;
-    const int m = nv > nh ? nv : nh;
-    c.exact = !keep && !fgen && nv == nh && nv >= 6 && nv <= 12;
-    if (c.exact) c.nmax = nv;
-    else if (!keep && m <= 12 && nv > 0 && nh > 0) c.nmax = m < 6 ? 6 : m;  // padded (4-/5-step fringes: always)
-    else if (!keep) c.nmax = SL3D_MAX_GRAY;  // more than 12 planes, or an axis with NONE (sl3d_config allows 0): the per-plane tests
-    else c.nmax = m <= 8 ? 8 : (m <= 12 ? 12 : SL3D_MAX_GRAY);
-    c.small = !keep && !fgen && n_views <= SL3D_SMALL_LAUNCH_VIEWS && !prefer_gated;
-#ifdef SL3D_MEASURE
-    if (getenv("SL3D_NO_SMALL")) c.small = false;
-#endif
-    const bool pipelined = !keep && rig != 0 && m <= 12 && nv > 0 && nh > 0;
-    c.early = c.small ? pipelined : (pipelined && !fgen && !prefer_gated);
-    return c;
+    static_assert(FusedFamilyOf<FAMILY>::keys.n > 0, "a family the rule never reaches");
+    return FusedFamilyOf<FAMILY>::table(std::make_integer_sequence<int, FusedFamilyOf<FAMILY>::keys.n>());
 }
-
-template <bool KEEP, bool FGEN, int RIG, int CMODE>
-static void launch_fused_n(int nv, int nh, dim3 grid, hipStream_t st, const KParams &P, const DevCal *C, int first_view, int n_views, int vpt)
-{
-    const dim3 block(SL3D_BLOCK, 1, 1);
-    const FusedChoice c = choose_fused(KEEP, FGEN, CMODE, nv, nh, n_views, P.prefer_gated != 0, RIG);
-    constexpr bool HAS_SMALL = !KEEP && !FGEN;  // (the 3-step timed families have the second instantiation, dense and clouds)
-    const long quads_ = (long)(P.pitch >> 2) * P.H;
-    const dim3 small_grid((((unsigned)((quads_ + SL3D_SMALL_BLOCK - 1) / SL3D_SMALL_BLOCK)) + 7u) & ~7u, grid.y, 1);
-#define SL3D_LAUNCH(NM, EX)                                                                                                                \
-    do {                                                                                                                                   \
-        if constexpr (HAS_SMALL) {                                                                                                         \
-            if (c.small) {                                                                                                                 \
-                hipLaunchKernelGGL((k_fused<KEEP, NM, FGEN, EX, RIG, CMODE, false, RIG != 0>), small_grid, dim3(SL3D_SMALL_BLOCK), 0, st, P, C, first_view, n_views, vpt); \
-                break;                                                                                                                     \
-            }                                                                                                                              \
-        }                                                                                                                                  \
-        if constexpr (HAS_SMALL && RIG != 0 && (NM) <= 12) {                                                                               \
-            if (c.early) {                                                                                                                 \
-                hipLaunchKernelGGL((k_fused<KEEP, NM, FGEN, EX, RIG, CMODE, true, true>), grid, block, 0, st, P, C, first_view, n_views, vpt); \
-                break;                                                                                                                     \
-            }                                                                                                                              \
-        }                                                                                                                                  \
-        hipLaunchKernelGGL((k_fused<KEEP, NM, FGEN, EX, RIG, CMODE, true, false>), grid, block, 0, st, P, C, first_view, n_views, vpt);     \
-    } while (0)
-    if constexpr (!KEEP) {
-        if constexpr (!FGEN) {
-            if (c.exact) {
-                switch (c.nmax) {
-                case 6: SL3D_LAUNCH(6, true); break;
-                case 7: SL3D_LAUNCH(7, true); break;
-                case 8: SL3D_LAUNCH(8, true); break;
-                case 9: SL3D_LAUNCH(9, true); break;
-                case 10: SL3D_LAUNCH(10, true); break;
-                case 11: SL3D_LAUNCH(11, true); break;
-                default: SL3D_LAUNCH(12, true); break;
-                }
-                return;
-            }
-        }
-        switch (c.nmax) {  // padded (unequal axes, or fewer than 6 planes); more than 12 planes: the per-plane tests
-        case 6: SL3D_LAUNCH(6, false); break;
-        case 7: SL3D_LAUNCH(7, false); break;
-        case 8: SL3D_LAUNCH(8, false); break;
-        case 9: SL3D_LAUNCH(9, false); break;
-        case 10: SL3D_LAUNCH(10, false); break;
-        case 11: SL3D_LAUNCH(11, false); break;
-        case 12: SL3D_LAUNCH(12, false); break;
-        default:
-            // 13..16 planes: per-plane tests, un-pipelined general kernel only (launch_fused routes every rig class there: the
-            // pipelined kernels with per-plane tests spill 3.5 KB per lane -- 21 ms per 16-view launch, tools/corners.py)
-            if constexpr (RIG == 0) SL3D_LAUNCH(SL3D_MAX_GRAY, false);
-            break;
-        }
-    } else {
-        if (c.nmax == 8) SL3D_LAUNCH(8, false);
-        else if (c.nmax == 12) SL3D_LAUNCH(12, false);
-        else SL3D_LAUNCH(SL3D_MAX_GRAY, false);
-    }
-#undef SL3D_LAUNCH
-}
-
-// MASKIN launches (CMODE | 4): the pipelined small-launch instantiation of every N, exact and padded, nothing else
-// GATED: the views are known (by their last counts) to be sparsely selected -- the large-launch form whose plane requests wait for the
-// valid bits (k_fused<..., true, false>); the selection is then evaluated under the block's reciprocal-table fill, in front of those requests
-template <int RIG, int CMODE, bool GATED>
-static void launch_fused_maskin_n(int nv, int nh, dim3 grid, hipStream_t st, const KParams &P, const DevCal *C, int first_view, int n_views, int vpt)
-{
-    static_assert(RIG != 0 && (CMODE == 4 || CMODE == 6), "MASKIN: rig classes 1..3, dense or segmented clouds");
-    const FusedChoice c = choose_fused(false, false, CMODE & 2, nv, nh, n_views, GATED, RIG);
-    const long quads_ = (long)(P.pitch >> 2) * P.H;
-    const dim3 small_grid((((unsigned)((quads_ + SL3D_SMALL_BLOCK - 1) / SL3D_SMALL_BLOCK)) + 7u) & ~7u, grid.y, 1);
-#define SL3D_LAUNCH_MI(NM, EX) hipLaunchKernelGGL((k_fused<false, NM, false, EX, RIG, CMODE, GATED, !GATED>), GATED ? grid : small_grid, dim3(GATED ? SL3D_BLOCK : SL3D_SMALL_BLOCK), 0, st, P, C, first_view, n_views, vpt)
-    if (c.exact) {
-        switch (c.nmax) {
-        case 6: SL3D_LAUNCH_MI(6, true); break;
-        case 7: SL3D_LAUNCH_MI(7, true); break;
-        case 8: SL3D_LAUNCH_MI(8, true); break;
-        case 9: SL3D_LAUNCH_MI(9, true); break;
-        case 10: SL3D_LAUNCH_MI(10, true); break;
-        case 11: SL3D_LAUNCH_MI(11, true); break;
-        default: SL3D_LAUNCH_MI(12, true); break;
-        }
-        return;
-    }
-    switch (c.nmax) {
-    case 6: SL3D_LAUNCH_MI(6, false); break;
-    case 7: SL3D_LAUNCH_MI(7, false); break;
-    case 8: SL3D_LAUNCH_MI(8, false); break;
-    case 9: SL3D_LAUNCH_MI(9, false); break;
-    case 10: SL3D_LAUNCH_MI(10, false); break;
-    case 11: SL3D_LAUNCH_MI(11, false); break;
-    default: SL3D_LAUNCH_MI(12, false); break;
-    }
-#undef SL3D_LAUNCH_MI
-}
-
-// one family of instantiations per translation unit (sl3d_fused_*.hip; they compile in parallel): 3-step timed kernels per rig,
-// dense and segmented; the 4-/5-step timed kernels; the parity mode
-#define SL3D_FUSED_FAMILY_ARGS int nv, int nh, dim3 grid, hipStream_t st, const KParams &P, const DevCal *C, int first_view, int n_views, int vpt
-void fused_dense_rig0(SL3D_FUSED_FAMILY_ARGS);
-void fused_dense_rig1(SL3D_FUSED_FAMILY_ARGS);
-void fused_dense_rig2(SL3D_FUSED_FAMILY_ARGS);
-void fused_dense_rig3(SL3D_FUSED_FAMILY_ARGS);
-void fused_clouds_rig0(SL3D_FUSED_FAMILY_ARGS);
-void fused_clouds_rig1(SL3D_FUSED_FAMILY_ARGS);
-void fused_clouds_rig2(SL3D_FUSED_FAMILY_ARGS);
-void fused_clouds_rig3(SL3D_FUSED_FAMILY_ARGS);
-void fused_maskin_rig1(int cmode, bool gated, SL3D_FUSED_FAMILY_ARGS);  // MASKIN launches (cmode 4 / 6), one translation unit per rig class
-void fused_maskin_rig2(int cmode, bool gated, SL3D_FUSED_FAMILY_ARGS);
-void fused_maskin_rig3(int cmode, bool gated, SL3D_FUSED_FAMILY_ARGS);
-void fused_fgen(int rig, int cmode, SL3D_FUSED_FAMILY_ARGS);  // 4-step (and the all-invalid 5-step) fringes: the F test stays a run-time branch
-void fused_parity(bool fgen, SL3D_FUSED_FAMILY_ARGS);
 
 }  // namespace sl3d

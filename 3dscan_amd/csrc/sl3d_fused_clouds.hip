@@ -1,7 +1,7 @@
-// the 3-step timed kernels that write segmented ordered clouds (CMODE 2, sl3d_run_clouds), all three rig classes (sl3d_fused.h)
+// the 3-step timed kernels that write segmented ordered clouds (CMODE 2, sl3d_run_clouds), rig classes 0 and 1 (sl3d_fused.h; rig class 2:
+// sl3d_fused_clouds_rig2.hip, rig class 3: sl3d_fused_rig3.hip)
 #include "sl3d_fused.h"
 namespace sl3d {
-void fused_clouds_rig0(SL3D_FUSED_FAMILY_ARGS) { launch_fused_n<false, false, 0, 2>(nv, nh, grid, st, P, C, first_view, n_views, vpt); }
-void fused_clouds_rig1(SL3D_FUSED_FAMILY_ARGS) { launch_fused_n<false, false, 1, 2>(nv, nh, grid, st, P, C, first_view, n_views, vpt); }
-void fused_clouds_rig2(SL3D_FUSED_FAMILY_ARGS) { launch_fused_n<false, false, 2, 2>(nv, nh, grid, st, P, C, first_view, n_views, vpt); }
+template FusedTable fused_table<fused_family_id(false, false, 0, 2)>();
+template FusedTable fused_table<fused_family_id(false, false, 1, 2)>();
 }  // namespace sl3d

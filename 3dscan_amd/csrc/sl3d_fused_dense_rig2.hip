@@ -2,5 +2,5 @@
 // without the LDS reciprocal table
 #include "sl3d_fused.h"
 namespace sl3d {
-void fused_dense_rig2(SL3D_FUSED_FAMILY_ARGS) { launch_fused_n<false, false, 2, 0>(nv, nh, grid, st, P, C, first_view, n_views, vpt); }
+template FusedTable fused_table<fused_family_id(false, false, 2, 0)>();
 }  // namespace sl3d

@@ -1,9 +1,12 @@
-// sl3d_fused_launch.hip -- launch_fused: grid shape, views per lane and the choice of the k_fused instantiation.  The
-// instantiations themselves live in the sl3d_fused_*.hip translation units (one family each; sl3d_fused.h).
-#include <stdio.h>
+// sl3d_fused_launch.hip -- launch_fused: grid shape, views per lane and the k_fused instantiation (sl3d_fused_choice.h: the rule).
+// The instantiations themselves live in the sl3d_fused_*.hip translation units (a few families each); this unit only looks them up,
+// and does not see the kernel.
+#include <hip/hip_runtime.h>
 #include <stdlib.h>
 
-#include "sl3d_fused.h"
+#include <utility>
+
+#include "sl3d_internal.h"
 
 namespace sl3d {
 
@@ -37,25 +40,26 @@ static int views_per_lane(unsigned bx, int n_views, int cam_table_kind, bool sma
     return vpt;
 }
 
-// (more than 12 Gray planes on an axis: the general kernel whatever the calibration is -- it evaluates any rig, and it is the only
-// one whose per-plane-test form does not spill)
-static int timed_rig(const KParams &P, int rig)
+FusedKey fused_choice(const KParams &P, int rig, int n_views, bool keep, int cmode, bool prefer_gated, bool maskin)
 {
-    if (P.Nv > 12 || P.Nh > 12 || P.Nv == 0 || P.Nh == 0) return 0;  // (an axis without Gray planes: no plane to pad the straight-line kernels with)
-    return rig == 1 ? 1 : (rig == 2 && P.proj_disp) ? 2 : (rig == 3 && P.proj_rad && P.F == 3) ? 3 : 0;
+#ifdef SL3D_MEASURE
+    // (every launch takes the large-launch instantiation, as if it had more views)
+    if (getenv("SL3D_NO_SMALL") && n_views <= SL3D_SMALL_LAUNCH_VIEWS) n_views = SL3D_SMALL_LAUNCH_VIEWS + 1;
+#endif
+    return fused_key({keep, P.F, P.Nv, P.Nh, n_views, rig, cmode, prefer_gated, maskin, P.proj_disp != nullptr, P.proj_rad != nullptr,
+                      P.cam_tab != nullptr && P.cam_tab_kind == 2});
 }
 
-// rig: 0 / 1 / 2 / 3 (sl3d_fused.h; the host knows the calibration, the timed kernels fold it at compile time).
-// cmode: 0 = dense xyz + valid planes, 2 = segmented clouds (KParams::clouds / seg_counts must be set).
-// Returns the hipError_t of THIS launch.
-bool fused_maskin_available(const KParams &P, int rig, int n_views, bool keep)
+// the launcher of key k: from its family's table (a family no unit instantiates is a null weak reference: sl3d_internal.h)
+template <int... F>
+static FusedLauncher fused_launcher(const FusedKey &k, std::integer_sequence<int, F...>)
 {
-    // (a MASKIN kernel compiles the one-double camera table only: its mask words live in the registers of the two-double kind)
-    if (keep || P.F != 3 || n_views > SL3D_SMALL_LAUNCH_VIEWS || timed_rig(P, rig) == 0 || (P.cam_tab != nullptr && P.cam_tab_kind == 2)) return false;
-    // the small-launch form with early requests, or (views known to be sparsely selected) the gated large-launch form: both exist for
-    // every pattern set the pipelined kernels take
-    const FusedChoice c = choose_fused(false, false, 0, P.Nv, P.Nh, n_views, false, timed_rig(P, rig));
-    return c.small && c.early;
+    static FusedTable (*const tables[])() = {&fused_table<F>...};
+    if (k.nmax == 0 || !tables[fused_family_id(k)]) return nullptr;
+    const FusedTable t = tables[fused_family_id(k)]();
+    for (int i = 0; i < t.n; i++)
+        if (t.entry[i].key == k) return t.entry[i].launch;
+    return nullptr;
 }
 
 unsigned fused_maskin_part_stride(const KParams &P)
@@ -66,14 +70,14 @@ unsigned fused_maskin_part_stride(const KParams &P)
 unsigned fused_maskin_part_words(const KParams &P) { return (unsigned)(((long)(P.pitch >> 2) * P.H + 63) / 64); }
 
 int launch_fused(const KParams &P_, const DevCal *d_cal, int rig, int first_view, int n_views, bool keep, int cmode, void *stream, bool prefer_gated,
-                 const MaskIn *mi)
+                 const MaskIn *mi, FusedKey &ran)
 {
     KParams P = P_;
     P.prefer_gated = prefer_gated ? 1 : 0;
-    if (mi) {
-        if (!fused_maskin_available(P, rig, n_views, keep)) return (int)hipErrorInvalidValue;
-        P.mi = *mi;
-    }
+    const FusedKey k = fused_choice(P, rig, n_views, keep, cmode, prefer_gated, mi != nullptr);
+    const FusedLauncher launch = fused_launcher(k, std::make_integer_sequence<int, FUSED_FAMILIES>());
+    if (!launch) return (int)hipErrorInvalidValue;  // (a MASKIN launch the shape has no kernel for, or a key no unit compiled)
+    if (mi) P.mi = *mi;
     const long quads = (long)(P.pitch >> 2) * P.H;
     const unsigned bx = ((unsigned)((quads + SL3D_BLOCK - 1) / SL3D_BLOCK) + 7u) & ~7u;  // a multiple of 8: consecutive tiles go round the 8 XCDs
     // (`small` is the SIZE of the launch, not the kernel it takes: a launch of up to 4 sparsely selected views runs the large-launch
@@ -82,41 +86,20 @@ int launch_fused(const KParams &P_, const DevCal *d_cal, int rig, int first_view
     // coverage with 4 views per launch, 1-4 % faster at 50 %: profiles/r05_sparse_small_launch_vpt_ab.txt)
     // (a MASKIN launch: one view per item -- nothing of a next view is in flight beside the selection bytes)
     const int vpt = mi ? 1 : views_per_lane(bx, n_views, P.cam_tab != nullptr ? P.cam_tab_kind : 0, !keep && P.F == 3 && n_views <= SL3D_SMALL_LAUNCH_VIEWS);
-    const dim3 grid(bx, (unsigned)((n_views + vpt - 1) / vpt), 1);
+    const unsigned block = k.rcpt ? SL3D_BLOCK : SL3D_SMALL_BLOCK;
+    const unsigned gx = ((unsigned)((quads + block - 1) / block) + 7u) & ~7u;
     // the timed kernels read the camera-side T1 from the per-calibration table whatever the batch is: with 8 views per lane it
     // costs nothing (1 B/px/view), with 1..4 it saves the iteration (+2..13 %), and a view's result does not depend on the
     // batch it was launched in
     P.use_cam_table = P.cam_tab != nullptr ? P.cam_tab_kind : 0;
-    const int r = timed_rig(P, rig);
 #ifdef SL3D_MEASURE
     if (getenv("SL3D_CAMTAB") && atoi(getenv("SL3D_CAMTAB")) == 0) P.use_cam_table = 0;
 #endif
-    hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();  // an earlier sticky error of another library is not this launch's
-    if (mi) {
-        (r == 1 ? fused_maskin_rig1 : r == 2 ? fused_maskin_rig2 : fused_maskin_rig3)(cmode, prefer_gated, P.Nv, P.Nh, grid, st, P, d_cal, first_view, n_views, vpt);
-    } else if (keep) {
-        fused_parity(P.F != 3, P.Nv, P.Nh, grid, st, P, d_cal, first_view, n_views, vpt);
-    } else if (P.F != 3) {
-        fused_fgen(r, cmode, P.Nv, P.Nh, grid, st, P, d_cal, first_view, n_views, vpt);
-    } else if (cmode == 2) {
-        (r == 1 ? fused_clouds_rig1 : r == 2 ? fused_clouds_rig2 : r == 3 ? fused_clouds_rig3 : fused_clouds_rig0)(P.Nv, P.Nh, grid, st, P, d_cal, first_view, n_views, vpt);
-    } else {
-        (r == 1 ? fused_dense_rig1 : r == 2 ? fused_dense_rig2 : r == 3 ? fused_dense_rig3 : fused_dense_rig0)(P.Nv, P.Nh, grid, st, P, d_cal, first_view, n_views, vpt);
-    }
-    return (int)hipGetLastError();
-}
-
-// the instantiation launch_fused picks for such a launch, spelled as rocprofv3 prints it (bench.py names the kernel its roofline
-// figure is about; derived from the same choose_fused / timed_rig the launch uses, so it cannot go stale)
-int fused_kernel_name(const KParams &P, int rig, int n_views, bool keep, int cmode, char *buf, size_t cap, bool prefer_gated, bool maskin)
-{
-    const bool fgen = P.F != 3;
-    const int r = keep ? 0 : timed_rig(P, rig);
-    if (maskin) cmode |= 4;
-    const FusedChoice c = choose_fused(keep, fgen, cmode & 2, P.Nv, P.Nh, n_views, prefer_gated, r);
-    auto b = [](bool v) { return v ? "true" : "false"; };
-    return snprintf(buf, cap, "sl3d::k_fused<%s, %d, %s, %s, %d, %d, %s, %s>", b(keep), c.nmax, b(fgen), b(c.exact), r, keep ? 0 : cmode, b(!c.small), b(c.early));
+    launch(gx, (unsigned)((n_views + vpt - 1) / vpt), block, stream, P, d_cal, first_view, n_views, vpt);
+    const int rc = (int)hipGetLastError();
+    if (rc == hipSuccess) ran = k;
+    return rc;
 }
 
 }  // namespace sl3d

@@ -3,14 +3,6 @@
 // gated large-launch one for views known to be sparsely selected
 #include "sl3d_fused.h"
 namespace sl3d {
-void fused_maskin_rig3(int cmode, bool gated, SL3D_FUSED_FAMILY_ARGS)
-{
-    if (gated) {
-        if (cmode & 2) launch_fused_maskin_n<3, 6, true>(nv, nh, grid, st, P, C, first_view, n_views, vpt);
-        else launch_fused_maskin_n<3, 4, true>(nv, nh, grid, st, P, C, first_view, n_views, vpt);
-    } else {
-        if (cmode & 2) launch_fused_maskin_n<3, 6, false>(nv, nh, grid, st, P, C, first_view, n_views, vpt);
-        else launch_fused_maskin_n<3, 4, false>(nv, nh, grid, st, P, C, first_view, n_views, vpt);
-    }
-}
+template FusedTable fused_table<fused_family_id(false, false, 3, 4)>();
+template FusedTable fused_table<fused_family_id(false, false, 3, 6)>();
 }  // namespace sl3d

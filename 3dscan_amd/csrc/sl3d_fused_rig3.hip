@@ -2,6 +2,6 @@
 // segmented clouds
 #include "sl3d_fused.h"
 namespace sl3d {
-void fused_dense_rig3(SL3D_FUSED_FAMILY_ARGS) { launch_fused_n<false, false, 3, 0>(nv, nh, grid, st, P, C, first_view, n_views, vpt); }
-void fused_clouds_rig3(SL3D_FUSED_FAMILY_ARGS) { launch_fused_n<false, false, 3, 2>(nv, nh, grid, st, P, C, first_view, n_views, vpt); }
+template FusedTable fused_table<fused_family_id(false, false, 3, 0)>();
+template FusedTable fused_table<fused_family_id(false, false, 3, 2)>();
 }  // namespace sl3d

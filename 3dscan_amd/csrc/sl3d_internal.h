@@ -6,13 +6,15 @@
 
 #include <hip/hip_vector_types.h>  // float2
 
+#include "sl3d_fused_choice.h"  // SL3D_MAX_GRAY, SL3D_SMALL_LAUNCH_VIEWS, FusedKey
+
 #define SL3D_MASK_HALO 2        // rows / columns of selection mask kept around the window
 #define SL3D_MASK_LPAD 16       // bytes in front of window column 0 in every mask row
 #define SL3D_ATAN_T1 511        // t1 = I0 - I2        in [-255, 255]
 #define SL3D_ATAN_T2 1021       // t2 = 2*I1 - I0 - I2 in [-510, 510]
-#define SL3D_MAX_GRAY 16
 #define SL3D_SEG_POINTS 256     // pixels (point slots) per segment of the segmented clouds = one wave of the fused kernel
-#define SL3D_SMALL_LAUNCH_VIEWS 4  // launches of at most this many views take the small-launch instantiation (sl3d_fused.h)
+#define SL3D_BLOCK 256 /* threads per block of the fused kernel: a block is a 1024-pixel tile of the scan, 4 waves = 4 segments of 256 pixels */
+#define SL3D_SMALL_BLOCK SL3D_BLOCK /* the small-launch instantiation keeps 256-thread blocks too (round 4: 128 / 64 threads +-0.5 %) */
 
 namespace sl3d {
 
@@ -145,14 +147,27 @@ static_assert(SL3D_SMALL_LAUNCH_VIEWS == 4, "KParams::mi_origin holds one entry 
 // launchers (sl3d_fused_launch.hip, sl3d_kernels.hip); `stream` is a hipStream_t
 // cmode: 0 = dense xyz + valid planes, 2 = segmented clouds
 // prefer_gated: the views of a small launch are sparsely selected (sl3d_capi_inputs.cpp: sparse_views)
-// mi != nullptr: a MASKIN launch (the views' valid bits from their raw selection; only where fused_maskin_available says so)
-int launch_fused(const KParams &P, const DevCal *d_cal, int rig, int first_view, int n_views, bool keep, int cmode, void *stream, bool prefer_gated = false,
-                 const MaskIn *mi = nullptr);
-// the k_fused instantiation such a launch runs, as rocprofv3 spells it; returns snprintf's value
-int fused_kernel_name(const KParams &P, int rig, int n_views, bool keep, int cmode, char *buf, size_t cap, bool prefer_gated = false, bool maskin = false);
-// can a launch of n_views views of this context evaluate the selection itself?  (3-step fringes, a pipelined rig class, at most
-// SL3D_SMALL_LAUNCH_VIEWS views, up to 12 Gray planes per axis; not the parity mode)
-bool fused_maskin_available(const KParams &P, int rig, int n_views, bool keep);
+// mi != nullptr: a MASKIN launch (the views' valid bits from their raw selection; only where fused_choice has a MASKIN kernel)
+// ran: the instantiation that went out (left alone if none did)
+int launch_fused(const KParams &P, const DevCal *d_cal, int rig, int first_view, int n_views, bool keep, int cmode, void *stream, bool prefer_gated,
+                 const MaskIn *mi, FusedKey &ran);
+// the k_fused instantiation such a launch runs (sl3d_fused_choice.h: fused_key; nmax == 0: none)
+FusedKey fused_choice(const KParams &P, int rig, int n_views, bool keep, int cmode, bool prefer_gated, bool maskin);
+// the launchers of one family of k_fused instantiations (fused_family), one per key: family FAMILY is instantiated by the
+// sl3d_fused_*.hip unit that compiles it, and launch_fused looks its keys up.  A family no unit instantiates is a null weak reference
+// (its launches fail with hipErrorInvalidValue; tests/test_fused_choice.py: the library's instantiations are the rule's keys).
+typedef void (*FusedLauncher)(unsigned grid_x, unsigned grid_y, unsigned block, void *stream, const KParams &P, const DevCal *C, int first_view, int n_views,
+                              int vpt);
+struct FusedEntry {
+    FusedKey key;
+    FusedLauncher launch;
+};
+struct FusedTable {
+    const FusedEntry *entry;
+    int n;
+};
+template <int FAMILY>
+__attribute__((weak)) FusedTable fused_table();
 // words per view in MaskIn::part (one per wave of the small-launch grid) / how many of them belong to waves that own pixels
 unsigned fused_maskin_part_stride(const KParams &P);
 unsigned fused_maskin_part_words(const KParams &P);
