@@ -7,6 +7,8 @@
 //   * the families hold 530 keys, each in the family its id names.
 // usage: fused_choice_check [names] -> prints a summary (and with `names`, every compiled key as rocprofv3 spells it); exit code 0 iff
 // no violation
+//        fused_choice_check key -> reads one FusedShape per line from stdin, its twelve fields as integers in declaration order, and
+//        prints the key fused_key returns for it (an empty line: no kernel); what tests/test_gpu_instantiations.py's plan is checked by
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -27,8 +29,21 @@ static std::string name(const FusedKey &k)
     return buf;
 }
 
+// the `key` mode: the rule applied to shapes a test planned
+static int keys_of_shapes()
+{
+    int f[12];
+    while (scanf("%d %d %d %d %d %d %d %d %d %d %d %d", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5], &f[6], &f[7], &f[8], &f[9], &f[10], &f[11]) == 12) {
+        const FusedShape s{f[0] != 0, f[1], f[2], f[3], f[4], f[5], f[6], f[7] != 0, f[8] != 0, f[9] != 0, f[10] != 0, f[11] != 0};
+        const FusedKey k = fused_key(s);
+        printf("%s\n", k.nmax ? name(k).c_str() : "");
+    }
+    return ferror(stdin) ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "key")) return keys_of_shapes();
     FusedDomain d;
 #ifdef DROP_LARGE_LAUNCHES  // (the test's own teeth: families enumerated over small launches only -- the sweep must object)
     d.views[1] = d.views[0];

@@ -30,22 +30,12 @@ from conftest import ROOT, golden_calibration, pkg
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ply_capture as PC  # noqa: E402
+from point_bars import exact_fraction, scaled_ulps  # noqa: E402
 from oracle.oracle import Oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 MASKIN_FORMS = (", 4, false, true>", ", 4, true, false>")   # the one-view MASKIN instantiations (dense / gated)
-
-
-def scaled_ulps(got, ref):
-    """Per coordinate: |got - ref| in float32 ulps of max(|ref_i|, 2^-6 * |ref|)."""
-    r = ref.astype(np.float64)
-    scale = np.maximum(np.abs(r), 2.0 ** -6 * np.linalg.norm(r, axis=-1, keepdims=True))
-    return np.abs(got.astype(np.float64) - r) / np.spacing(scale.astype(np.float32)).astype(np.float64)
-
-
-def exact_fraction(got, ref):
-    return float(np.mean((got.view(np.uint32) == ref.view(np.uint32)).all(-1)))
 
 
 def make_case():
