@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the fused decode -> unwrap -> correspond -> triangulate kernel (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, the K timed steps, --dump-outputs if given, and the
+line.  --full adds everything else the benchmark measures or checks, after the headline: the compacted clouds leg, the side
+figures (other rigs, sizes and launch patterns, one scan from idle, a device copy), the CPU baseline that also checks one view of
+the GPU result, the host buffer paths, and for N > 1 the assembly variants that are never the headline.
 
 N > 1: one process per GPU over torch.distributed (backend nccl = RCCL).  Started by torch.distributed.run (the driver's
 way: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) each process is a rank; started plainly, `python
@@ -16,7 +21,8 @@ really streams from HBM).  With N GPUs every view is sharded by image rows (1080
 N*views views, so per-GPU work is fixed (weak scaling); the per-pixel map needs no collective (the mask halo comes from
 the input mask).  `value` is that compute-only rate.  The assembly of the clouds on rank 0 -- the north star's "single RCCL
 gather" -- is measured too and reported as `with_assembly`: end to end, pipelined per chunk of views on a communication
-stream beside the compute stream, dense (xyz + valid) and compacted (valid points only, compacted by the fused kernel).
+stream beside the compute stream, dense (xyz + valid) and, with --full or --check, compacted (valid points only, compacted
+by the fused kernel).
 
 The defaults (300 warm-up + 2000 timed launches, ~1 s of GPU time) let the clocks settle: the kernel runs the package
 into its power limit (~1.4 kW), and a 25 ms run from idle measures the ramp, not the steady state.  For the same reason
@@ -76,13 +82,18 @@ def parse():
                     help="reference = the reference's calibration rescaled (BASELINE workload); distorted = the same rig with "
                          "projector distortion and camera tangential terms (table path); general = skewed camera matrix as well "
                          "(everything evaluated in the kernel) -- the other two are sweeps / side figures only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-clouds", action="store_true", help="skip the frames -> compacted clouds leg (A/B builds of the dense kernel only)")
-    ap.add_argument("--no-side", action="store_true", help="skip the side figures (1 view latency, other rigs, N=9)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: the compacted clouds leg, the side figures (other "
+                         "rigs, sizes and launch patterns, device copy rate), the CPU baseline with its check of the GPU result, the host "
+                         "buffer paths and (N>1) the assembly variants that are never the headline. Off by default: a plain run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the host buffer figures")
+    ap.add_argument("--no-clouds", action="store_true", help="with --full: skip the frames -> compacted clouds leg (A/B builds of the dense kernel only)")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side figures (1 view latency, other rigs, N=9)")
     ap.add_argument("--no-assemble", action="store_true", help="skip the assembly measurements (N>1)")
     ap.add_argument("--shim-timing", action="store_true",
-                    help="also time the Level-1 drop-in path (tools/shim_bench.cpp: compiles with g++, writes BMP files, minutes of wall time); "
-                         "off by default so that the driver's line depends on the GPU only")
+                    help="with --full: also time the Level-1 drop-in path (tools/shim_bench.cpp: compiles with g++, writes BMP files, minutes "
+                         "of wall time); off by default so that the driver's line depends on the GPU only")
     ap.add_argument("--one-view-cold-only", action="store_true",
                     help="run only side.one_view_cold (one view per launch, a different resident view each launch: frames from HBM, not from "
                          "the Infinity Cache) and print it -- the command tools/profile.sh puts under rocprofv3 for that figure")
@@ -110,6 +121,8 @@ def parse():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.gpus > 1 or args.idle_only or args.one_view_cold_only or args.families_only):
         ap.error("--dump-outputs writes the outputs of the timed launches of one GPU: not with --gpus > 1 or the *-only modes")
+    if args.shim_timing and not args.full:
+        ap.error("--shim-timing adds to the side figures of --full: give --full as well")
     return args
 
 
@@ -679,7 +692,9 @@ def main():
         torch.cuda.synchronize()
 
     # before anything has warmed the device: 20 launches from idle clocks, no preconditioning (side.cold_20_steps -- how much of
-    # `value` hangs on the preconditioning below is then part of the driver's record)
+    # `value` hangs on the preconditioning below is then part of the driver's record).  A plain run launches them too and only
+    # leaves the figure out of its line: they are part of the set-up the timed steps follow (over a batch of few views, whose masks
+    # are deferred, the first of them is the MASKIN launch that prepares the masks set above), and they take milliseconds
     cold20 = None
     if world == 1:
         sc.timer_start()
@@ -718,7 +733,6 @@ def main():
     launch_s = ev_ms / 1e3 / args.steps
     achieved = alg_bytes_px * px_per_launch / launch_s / 1e9
 
-    kernel_name_clouds = sc.fused_kernel_name(n_views, clouds=True)
     traffic, traffic_src = measured_traffic(px_per_launch) if alg_bytes_px == 60 else (None, None)
 
     out = {
@@ -747,63 +761,65 @@ def main():
     # a side figure, never `value`
     # Every collective of this leg (barrier, MAX over ranks, the all-ranks-ok vote) sits OUTSIDE the per-rank try blocks and is
     # executed by every rank in the same order whatever happened locally: an exception on one rank can never leave the others
-    # in a mismatched collective.
-    def all_ok(ok):
-        return dmod.max_over_ranks(0.0 if ok else 1.0, red_dev) == 0.0
+    # in a mismatched collective.  (--full only: a plain run prints the headline without it.)
+    if args.full:
+        def all_ok(ok):
+            return dmod.max_over_ranks(0.0 if ok else 1.0, red_dev) == 0.0
 
-    cl_err, counts, te, kms = None, [], 0.0, 0.0
-    reps = max(20, args.steps // 10)
-    if args.no_clouds:
-        cl_err = "skipped (--no-clouds)"
-    else:
-        try:
-            for _ in range(20):
-                sc.run_clouds(0, n_views)
-            counts = sc.cloud_counts(0, n_views, want_device_copy=False)[2]
-        except Exception as e:
-            cl_err = repr(e)
-    if all_ok(cl_err is None):
-        barrier()
-        t0 = time.perf_counter()
-        try:
-            for _ in range(reps):
-                sc.run_clouds(0, n_views)
+        kernel_name_clouds = sc.fused_kernel_name(n_views, clouds=True)
+        cl_err, counts, te, kms = None, [], 0.0, 0.0
+        reps = max(20, args.steps // 10)
+        if args.no_clouds:
+            cl_err = "skipped (--no-clouds)"
+        else:
+            try:
+                for _ in range(20):
+                    sc.run_clouds(0, n_views)
                 counts = sc.cloud_counts(0, n_views, want_device_copy=False)[2]
-        except Exception as e:
-            cl_err = repr(e)
-        barrier()
-        te = dmod.max_over_ranks((time.perf_counter() - t0) / reps, red_dev)
-        try:
-            sc.timer_start()
-            for _ in range(reps):
-                sc.run_clouds(0, n_views)
-            kms = sc.timer_stop() / reps
-        except Exception as e:
-            cl_err = cl_err or repr(e)
-        kms = dmod.max_over_ranks(kms, red_dev)
-        if not all_ok(cl_err is None):
+            except Exception as e:
+                cl_err = repr(e)
+        if all_ok(cl_err is None):
+            barrier()
+            t0 = time.perf_counter()
+            try:
+                for _ in range(reps):
+                    sc.run_clouds(0, n_views)
+                    counts = sc.cloud_counts(0, n_views, want_device_copy=False)[2]
+            except Exception as e:
+                cl_err = repr(e)
+            barrier()
+            te = dmod.max_over_ranks((time.perf_counter() - t0) / reps, red_dev)
+            try:
+                sc.timer_start()
+                for _ in range(reps):
+                    sc.run_clouds(0, n_views)
+                kms = sc.timer_stop() / reps
+            except Exception as e:
+                cl_err = cl_err or repr(e)
+            kms = dmod.max_over_ranks(kms, red_dev)
+            if not all_ok(cl_err is None):
+                cl_err = cl_err or "another rank failed"
+        else:
             cl_err = cl_err or "another rank failed"
-    else:
-        cl_err = cl_err or "another rank failed"
-    if cl_err is None:
-        vf = sum(counts) / float(px_per_launch)
-        cl_bytes_px = 2 * 3 + 4 * N + 1 + 1 + 12 * vf   # frames + mask byte read, valid byte + 12 B per VALID pixel written
-        cl_achieved = cl_bytes_px * px_per_launch / (kms * 1e-3) / 1e9
-        cl_traffic, cl_traffic_src = measured_traffic(px_per_launch, "clouds") if alg_bytes_px == 60 else (None, None)
-        out["to_compacted_clouds"] = {"value": round(px_per_step / te / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(te * 1e3, 4),
-                                      "kernel_only": {"value": round(px_per_step / kms / 1e3, 1), "ms_per_launch": round(kms, 4)},
-                                      "valid_points_per_step_rank0": int(sum(counts)), "valid_fraction_rank0": round(vf, 4),
-                                      "algorithmic_bytes_per_pixel": round(cl_bytes_px, 2),
-                                      "roofline": {"bound": "hbm", "achieved": round(cl_achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                                   "frac": round(cl_achieved / HBM_PEAK_GBS, 4), "traffic": cl_traffic,
-                                                   "traffic_source": cl_traffic_src and f"{cl_traffic_src} (committed PMC run of this command, scaled to this launch; not measured in this run)",
-                                                   "kernel": kernel_name_clouds, "launches": "the fused kernel + k_seg_scan (both between the HIP events)",
-                                                   "avg_launch_ms": round(kms, 4)},
-                                      "how": "sl3d_run_clouds: the fused kernel writes SEGMENTED ordered clouds (every wave compacts its 256 scan pixels into its own "
-                                             "slot: no tile waits for another) + one scan launch for offsets and totals; value = launches + the wait for the "
-                                             "per-view counts; kernel_only = both launches between HIP events"}
-    else:
-        out["to_compacted_clouds"] = {"error": cl_err}
+        if cl_err is None:
+            vf = sum(counts) / float(px_per_launch)
+            cl_bytes_px = 2 * 3 + 4 * N + 1 + 1 + 12 * vf   # frames + mask byte read, valid byte + 12 B per VALID pixel written
+            cl_achieved = cl_bytes_px * px_per_launch / (kms * 1e-3) / 1e9
+            cl_traffic, cl_traffic_src = measured_traffic(px_per_launch, "clouds") if alg_bytes_px == 60 else (None, None)
+            out["to_compacted_clouds"] = {"value": round(px_per_step / te / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(te * 1e3, 4),
+                                          "kernel_only": {"value": round(px_per_step / kms / 1e3, 1), "ms_per_launch": round(kms, 4)},
+                                          "valid_points_per_step_rank0": int(sum(counts)), "valid_fraction_rank0": round(vf, 4),
+                                          "algorithmic_bytes_per_pixel": round(cl_bytes_px, 2),
+                                          "roofline": {"bound": "hbm", "achieved": round(cl_achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                                       "frac": round(cl_achieved / HBM_PEAK_GBS, 4), "traffic": cl_traffic,
+                                                       "traffic_source": cl_traffic_src and f"{cl_traffic_src} (committed PMC run of this command, scaled to this launch; not measured in this run)",
+                                                       "kernel": kernel_name_clouds, "launches": "the fused kernel + k_seg_scan (both between the HIP events)",
+                                                       "avg_launch_ms": round(kms, 4)},
+                                          "how": "sl3d_run_clouds: the fused kernel writes SEGMENTED ordered clouds (every wave compacts its 256 scan pixels into its own "
+                                                 "slot: no tile waits for another) + one scan launch for offsets and totals; value = launches + the wait for the "
+                                                 "per-view counts; kernel_only = both launches between HIP events"}
+        else:
+            out["to_compacted_clouds"] = {"error": cl_err}
 
     digests = {}
     if world > 1 and not args.no_assemble:
@@ -844,7 +860,7 @@ def main():
     if args.check:
         out["check"] = digests
 
-    if rank == 0 and world == 1 and not args.no_side:
+    if rank == 0 and world == 1 and args.full and not args.no_side:
         out["side"] = side_figures(args, scm, syn, np, dev_index)
         out["side"]["cold_20_steps"] = cold20
         try:   # the same roofline against what a device copy reaches on this very box, right now (never `frac`)
@@ -854,7 +870,7 @@ def main():
         except Exception as e:
             out["roofline"]["device_copy"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sc.run(0, n_views)
         xyz, valid = sc.points(0)
         try:
@@ -971,7 +987,9 @@ def measure_assembly(args, torch, dist, dmod, sc, compute_stream, dev, n_views, 
     into chunks of views; chunk k's stripes leave on the communication stream (one grouped batch of sends that land in place
     in the root's dense planes) while the compute stream already runs chunk k+1.  dense = xyz + valid (13 B/px);
     compact = the valid points only, compacted by the fused kernel (counts first).  Also the rotating-roots all_to_all
-    (every rank assembles its share of the views: all links busy), as one blocking collective after the compute."""
+    (every rank assembles its share of the views: all links busy), as one blocking collective after the compute.
+    A plain run times the dense variants only, the candidates for the headline (and compact when --check digests it); --full adds
+    host_parallel, compact, compact on a 19 % selection and the whole-views sharding."""
     res = {}
     nccl = args.backend == "nccl"
     import numpy as np_mod
@@ -1033,84 +1051,87 @@ def measure_assembly(args, torch, dist, dmod, sc, compute_stream, dev, n_views, 
                 h.update(out_val[v][:, :W].contiguous().cpu().numpy().tobytes())
             digests["dense_sha256"] = h.hexdigest()
 
-        # ---- host_parallel: the reference's consumer is the HOST -- every rank downloads its own rows of every view over its own
-        # GPU's PCIe link (what sl3d_group_download_points does for a single-process caller), no xGMI hop to a root ----
-        try:
-            hp = sc.pinned((n_views, rows, W, 3), np_mod.float32)
-            hv = sc.pinned((n_views, rows, W), np_mod.uint8)
-            herr = None
-        except Exception as e:
-            herr = repr(e)
+        if args.full:
+            # ---- host_parallel: the reference's consumer is the HOST -- every rank downloads its own rows of every view over its own
+            # GPU's PCIe link (what sl3d_group_download_points does for a single-process caller), no xGMI hop to a root ----
+            try:
+                hp = sc.pinned((n_views, rows, W, 3), np_mod.float32)
+                hv = sc.pinned((n_views, rows, W), np_mod.uint8)
+                herr = None
+            except Exception as e:
+                herr = repr(e)
 
-        def host_step(first):
-            for k, (f, n) in enumerate(chunks):
-                sc.run(f, n)
+            def host_step(first):
+                for k, (f, n) in enumerate(chunks):
+                    sc.run(f, n)
+                if herr is None:
+                    sc.download_views(0, n_views, hp, hv)     # 2-D copies on the compute stream, then one wait
+
             if herr is None:
-                sc.download_views(0, n_views, hp, hv)     # 2-D copies on the compute stream, then one wait
+                steps_of["host_parallel"] = host_step   # (measured and reported; never a headline candidate: see the end of this function)
+            t = timed(host_step, max(2, reps // 4))
+            res["host_parallel"] = ({"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
+                                     "bytes_to_host_per_rank_per_step": int(n_views * rows * W * 13),
+                                     "note": "every rank: fused kernel, then its own rows of every view D2H into pinned host memory over its own PCIe link"}
+                                    if herr is None else {"error": herr})
 
-        if herr is None:
-            steps_of["host_parallel"] = host_step   # (measured and reported; never a headline candidate: see the end of this function)
-        t = timed(host_step, max(2, reps // 4))
-        res["host_parallel"] = ({"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
-                                 "bytes_to_host_per_rank_per_step": int(n_views * rows * W * 13),
-                                 "note": "every rank: fused kernel, then its own rows of every view D2H into pinned host memory over its own PCIe link"}
-                                if herr is None else {"error": herr})
+        if args.full or args.check:   # (never a headline candidate; --check digests it)
+            # ---- compact: the valid points only, compacted by the fused kernel ----
+            sc.run_clouds(0, n_views)
+            cptr, cstride, _ = sc.cloud_counts(0, n_views)
+            clouds = dev_tensor(torch, cptr, n_views * cstride * 12, torch.float32, dev)
+            out_cloud = torch.empty(n_views * H * pitch * 3, dtype=torch.float32, device=dev) if root else None
+            state = {}
 
-        # ---- compact: the valid points only, compacted by the fused kernel ----
-        sc.run_clouds(0, n_views)
-        cptr, cstride, _ = sc.cloud_counts(0, n_views)
-        clouds = dev_tensor(torch, cptr, n_views * cstride * 12, torch.float32, dev)
-        out_cloud = torch.empty(n_views * H * pitch * 3, dtype=torch.float32, device=dev) if root else None
-        state = {}
+            def compact_step(first):
+                off = 0
+                offs_all, counts_all = [], []
+                for k, (f, n) in enumerate(chunks):
+                    if not first:
+                        compute_stream.wait_event(ev_comm[k])
+                    sc.run_clouds(f, n)
+                    counts = sc.cloud_counts(f, n)[2]                # waits for this chunk's kernel: the payload sizes come from it
+                    with torch.cuda.stream(comm):
+                        allc = asm.gather_counts(counts)
+                        tot = [sum(allc[r][i] for r in range(world)) for i in range(n)]
+                        offs = [3 * (off + sum(tot[:i])) for i in range(n)]
+                        asm.gather_compact(range(f, f + n), clouds, cstride, allc, out_cloud, offs)
+                        ev_comm[k].record(comm)
+                    offs_all += offs
+                    counts_all += tot
+                    off += sum(tot)
+                state["offs"], state["counts"] = offs_all, counts_all
 
-        def compact_step(first):
-            off = 0
-            offs_all, counts_all = [], []
-            for k, (f, n) in enumerate(chunks):
-                if not first:
-                    compute_stream.wait_event(ev_comm[k])
-                sc.run_clouds(f, n)
-                counts = sc.cloud_counts(f, n)[2]                # waits for this chunk's kernel: the payload sizes come from it
-                with torch.cuda.stream(comm):
-                    allc = asm.gather_counts(counts)
-                    tot = [sum(allc[r][i] for r in range(world)) for i in range(n)]
-                    offs = [3 * (off + sum(tot[:i])) for i in range(n)]
-                    asm.gather_compact(range(f, f + n), clouds, cstride, allc, out_cloud, offs)
-                    ev_comm[k].record(comm)
-                offs_all += offs
-                counts_all += tot
-                off += sum(tot)
-            state["offs"], state["counts"] = offs_all, counts_all
-
-        steps_of["compact_root_gather"] = compact_step
-        t = timed(compact_step, reps)
-        res["compact_root_gather"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
-                                      "points_per_step": int(sum(state["counts"])), "chunks": len(chunks), "overlapped_with_compute": True}
-        if args.check and root:
-            h = hashlib.sha256()
-            for o, c in zip(state["offs"], state["counts"]):
-                h.update(out_cloud[o:o + 3 * c].cpu().numpy().tobytes())
-            digests["compact_sha256"] = h.hexdigest()
-
-        # ---- the same on the reference's own kind of selection: 358,580 of 1,920,000 pixels (18.7 %) lie inside the lasso of its real
-        # captures -- the one case in which the north star's SINGLE-root gather carries a fifth of the bytes.
-        # Every view gets a centred rectangle of that share; afterwards the full-frame masks are back.
-        try:
-            share = 358580.0 / 1920000.0
-            mh, mw = int(round(H * share ** 0.5)), int(round(W * share ** 0.5))
-            lasso = np_mod.zeros((H, W), np_mod.uint8)
-            lasso[(H - mh) // 2:(H - mh) // 2 + mh, (W - mw) // 2:(W - mw) // 2 + mw] = 1
-            sc.set_masks(lasso, 0, n_views)
+            steps_of["compact_root_gather"] = compact_step
             t = timed(compact_step, reps)
-            res["compact_root_gather_19pct_selection"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
-                                                          "points_per_step": int(sum(state["counts"])), "selected_fraction": round(float(lasso.mean()), 4),
-                                                          "note": "compact_root_gather with the share of the frame the reference's real captures select; never the headline"}
-        except Exception as e:
-            res["compact_root_gather_19pct_selection"] = {"error": repr(e)}
-        finally:
-            sc.set_masks(syn_full_mask(W, H), 0, n_views)
-            sc.run(0, n_views)
-            sc.synchronize()
+            res["compact_root_gather"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
+                                          "points_per_step": int(sum(state["counts"])), "chunks": len(chunks), "overlapped_with_compute": True}
+            if args.check and root:
+                h = hashlib.sha256()
+                for o, c in zip(state["offs"], state["counts"]):
+                    h.update(out_cloud[o:o + 3 * c].cpu().numpy().tobytes())
+                digests["compact_sha256"] = h.hexdigest()
+
+        if args.full:
+            # ---- the same on the reference's own kind of selection: 358,580 of 1,920,000 pixels (18.7 %) lie inside the lasso of its real
+            # captures -- the one case in which the north star's SINGLE-root gather carries a fifth of the bytes.
+            # Every view gets a centred rectangle of that share; afterwards the full-frame masks are back.
+            try:
+                share = 358580.0 / 1920000.0
+                mh, mw = int(round(H * share ** 0.5)), int(round(W * share ** 0.5))
+                lasso = np_mod.zeros((H, W), np_mod.uint8)
+                lasso[(H - mh) // 2:(H - mh) // 2 + mh, (W - mw) // 2:(W - mw) // 2 + mw] = 1
+                sc.set_masks(lasso, 0, n_views)
+                t = timed(compact_step, reps)
+                res["compact_root_gather_19pct_selection"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
+                                                              "points_per_step": int(sum(state["counts"])), "selected_fraction": round(float(lasso.mean()), 4),
+                                                              "note": "compact_root_gather with the share of the frame the reference's real captures select; never the headline"}
+            except Exception as e:
+                res["compact_root_gather_19pct_selection"] = {"error": repr(e)}
+            finally:
+                sc.set_masks(syn_full_mask(W, H), 0, n_views)
+                sc.run(0, n_views)
+                sc.synchronize()
 
         # ---- rotating roots: one all_to_all after the compute (every rank assembles V of the views) ----
         if nccl and n_views == V * world:   # (a strong-scaled batch that does not divide by N has no equal shares to rotate)
@@ -1145,45 +1166,46 @@ def measure_assembly(args, torch, dist, dmod, sc, compute_stream, dev, n_views, 
                 res["dense_rotating_pipelined"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 3),
                                                    "chunks": len(chunks), "overlapped_with_compute": True,
                                                    "note": "view i of a chunk is assembled on rank i mod N: one all_to_all per chunk on the communication stream"}
-        # ---- the OTHER sharding of a batch of independent views ("implement the specified one, measure both"): whole views
-        # per GPU instead of row stripes -- rank r takes V whole views, every view's dense planes are complete on one GPU (the very
-        # end state of the rotating assemblies above) and NOTHING is exchanged.  Reported beside the row-sharded variants, never the
-        # headline: BASELINE's configs[3] and the north star specify row stripes + a gather
-        try:
-            import importlib
-            syn_ = importlib.import_module("3dscan_amd.synth")
-            scm_ = importlib.import_module("3dscan_amd.scanner")
-            with scm_.Scanner(W, H, W, H, args.ngray, args.ngray, args.fringe_width, args.fringe_width, max_views=V, device=dev.index) as sw:
-                sw.set_calibration(*rig_calibration(syn_, np_mod, args.rig, W, H, W, H))
-                sw.set_masks(syn_.default_mask(W, H), 0, V)
-                for j in range(V):
-                    vid = rank * V + j
-                    sw.synth_view(j, plane=(0.75 * vid, 0.05, 0.05 - 0.003 * vid), view_id=vid, noise=args.noise)
-                for _ in range(5):
-                    sw.run(0, V)
-                sw.synchronize()
-
-                def whole_step(first):
-                    sw.run(0, V)
-                    if first:
-                        sw.synchronize()
-
-                def timed_whole(reps):
-                    whole_step(True)
-                    barrier()
-                    t0 = time.perf_counter()
-                    for _ in range(reps):
-                        whole_step(False)
+        if args.full:
+            # ---- the OTHER sharding of a batch of independent views ("implement the specified one, measure both"): whole views
+            # per GPU instead of row stripes -- rank r takes V whole views, every view's dense planes are complete on one GPU (the very
+            # end state of the rotating assemblies above) and NOTHING is exchanged.  Reported beside the row-sharded variants, never the
+            # headline: BASELINE's configs[3] and the north star specify row stripes + a gather
+            try:
+                import importlib
+                syn_ = importlib.import_module("3dscan_amd.synth")
+                scm_ = importlib.import_module("3dscan_amd.scanner")
+                with scm_.Scanner(W, H, W, H, args.ngray, args.ngray, args.fringe_width, args.fringe_width, max_views=V, device=dev.index) as sw:
+                    sw.set_calibration(*rig_calibration(syn_, np_mod, args.rig, W, H, W, H))
+                    sw.set_masks(syn_.default_mask(W, H), 0, V)
+                    for j in range(V):
+                        vid = rank * V + j
+                        sw.synth_view(j, plane=(0.75 * vid, 0.05, 0.05 - 0.003 * vid), view_id=vid, noise=args.noise)
+                    for _ in range(5):
+                        sw.run(0, V)
                     sw.synchronize()
-                    barrier()
-                    return dmod.max_over_ranks((time.perf_counter() - t0) / reps, dev if nccl else None)
 
-                t = timed_whole(max(reps, args.steps))
-                res["whole_views_no_exchange"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 4),
-                                                  "note": f"the other sharding of the same batch: {V} WHOLE views per GPU instead of row stripes of {n_views}; every view is "
-                                                          "complete on one GPU (the end state of the rotating assemblies) with no exchange at all; not the headline"}
-        except Exception as e:
-            res["whole_views_no_exchange"] = {"error": repr(e)}
+                    def whole_step(first):
+                        sw.run(0, V)
+                        if first:
+                            sw.synchronize()
+
+                    def timed_whole(reps):
+                        whole_step(True)
+                        barrier()
+                        t0 = time.perf_counter()
+                        for _ in range(reps):
+                            whole_step(False)
+                        sw.synchronize()
+                        barrier()
+                        return dmod.max_over_ranks((time.perf_counter() - t0) / reps, dev if nccl else None)
+
+                    t = timed_whole(max(reps, args.steps))
+                    res["whole_views_no_exchange"] = {"value": round(px_per_step / t / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(t * 1e3, 4),
+                                                      "note": f"the other sharding of the same batch: {V} WHOLE views per GPU instead of row stripes of {n_views}; every view is "
+                                                              "complete on one GPU (the end state of the rotating assemblies) with no exchange at all; not the headline"}
+            except Exception as e:
+                res["whole_views_no_exchange"] = {"error": repr(e)}
         # ---- the headline of an N > 1 line: the best ASSEMBLED variant, timed once more over exactly --steps steps between barriers
         # (the calibration runs above decide which; the choice is the same on every rank: the figures are MAX-over-ranks already) ----
         # Candidates: only variants that leave COMPLETE DENSE views on a rank -- the gather to the root and the rotating assemblies.

@@ -31,9 +31,10 @@ COMMON = ["--steps", "3", "--warmup", "1", "--precondition-ms", "0", "--no-cpu-b
 @pytest.mark.parametrize("world,height", [(2, 1080), (3, 1000)])
 def test_bench_spawns_ranks_and_assembly_equals_single_rank(world, height):
     views = 2
-    one = _bench("--gpus", "1", "--views", str(views * world), "--height", str(height), *COMMON)
+    # --full: the compacted clouds leg of the 1-rank run and the assembly variants that are never the headline
+    one = _bench("--gpus", "1", "--views", str(views * world), "--height", str(height), "--full", *COMMON)
     many = _bench("--gpus", str(world), "--backend", "gloo", "--devices", ",".join(["0"] * world), "--views", str(views),
-                  "--height", str(height), "--chunks", "2", *COMMON)
+                  "--height", str(height), "--chunks", "2", "--full", *COMMON)
     assert one["n_gpus"] == 1 and many["n_gpus"] == world and many["scaling"] == "weak"
     assert many["config"]["rows_per_gpu"] == -(-height // world)
     wa = many["with_assembly"]

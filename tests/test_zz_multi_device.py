@@ -172,7 +172,7 @@ def test_bench_two_ranks_strong_scaling_and_rank_identity():
     distinct PCI bus id per rank (what lets the driver confirm N ranks on N GPUs); the 19 % selection variant of the single-root
     compact gather is there and never the headline."""
     common = ["--steps", "3", "--warmup", "1", "--precondition-ms", "0", "--no-cpu-baseline", "--no-side", "--check", "--height", "1080",
-              "--scaling", "strong", "--total-views", "4"]
+              "--scaling", "strong", "--total-views", "4", "--full"]
     one = _bench("--gpus", "1", *common)
     two = _bench("--gpus", "2", "--backend", "nccl", "--chunks", "2", *common)
     assert two["scaling"] == "strong" and two["config"]["views_per_step"] == 4 and two["config"]["rows_per_gpu"] == 540

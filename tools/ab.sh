@@ -10,6 +10,8 @@
 # ab/ is git-ignored but travels with gpurun.  The default library (3dscan_amd/libsl3d.so) is always measured as "base".
 set -u
 cd "$(dirname "$0")/.."
+ERR=${AB_STDERR:-ab/stderr.log}   # the benchmark's stderr of every variant, appended
+mkdir -p "$(dirname "$ERR")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function"
 if [ "$1" = build ]; then
   shift; mkdir -p ab
@@ -35,22 +37,21 @@ elif [ "$1" = run ]; then
   shift
   for lib in 3dscan_amd/libsl3d.so ab/libsl3d_*.so; do
     [ -f "$lib" ] || continue
-    r=$(SL3D_LIB=$PWD/$lib python3 bench.py --no-cpu-baseline --no-side "$@" 2>>gpurun_out/ab_stderr.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); c=d.get('to_compacted_clouds',{}); print(d['value'], d['roofline']['frac'], d['ms_per_step'], '| clouds', c.get('value'), (c.get('kernel_only') or {}).get('value'))")
+    r=$(SL3D_LIB=$PWD/$lib python3 bench.py --full --no-cpu-baseline --no-side "$@" 2>>"$ERR" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); c=d.get('to_compacted_clouds',{}); print(d['value'], d['roofline']['frac'], d['ms_per_step'], '| clouds', c.get('value'), (c.get('kernel_only') or {}).get('value'))")
     echo "$(basename $lib) $r"
   done
 elif [ "$1" = alt ]; then
   shift; reps=$1; shift
-  mkdir -p gpurun_out
   for rep in $(seq 1 $reps); do
     for lib in 3dscan_amd/libsl3d.so ab/libsl3d_*.so; do
       [ -f "$lib" ] || continue
       if [ "${PERSCAN:-0}" = 1 ]; then
-        r=$(SL3D_LIB=$PWD/$lib python3 tools/mask_timing.py 1920 1080 2>>gpurun_out/ab_stderr.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['per_scan_device']; t=d.get('two_kernel_route') or {}; print(d['scan_us'], 'us per scan,', d['kernel'].split('<')[1], '| two-kernel route', t.get('scan_us'), 'us, mask', t.get('mask_us'))")
+        r=$(SL3D_LIB=$PWD/$lib python3 tools/mask_timing.py 1920 1080 2>>"$ERR" | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['per_scan_device']; t=d.get('two_kernel_route') or {}; print(d['scan_us'], 'us per scan,', d['kernel'].split('<')[1], '| two-kernel route', t.get('scan_us'), 'us, mask', t.get('mask_us'))")
       elif [ "${ONEVIEW:-0}" = 1 ]; then
-        r=$(SL3D_LIB=$PWD/$lib python3 bench.py --one-view-cold-only --steps 4000 "$@" 2>>gpurun_out/ab_stderr.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['one_view_cold']; print(d['launch_us'], 'us  frac', d['frac'], ' on moved bytes', d['frac_on_moved_bytes'])")
+        r=$(SL3D_LIB=$PWD/$lib python3 bench.py --one-view-cold-only --steps 4000 "$@" 2>>"$ERR" | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['one_view_cold']; print(d['launch_us'], 'us  frac', d['frac'], ' on moved bytes', d['frac_on_moved_bytes'])")
       else
-        extra="--no-clouds"; [ "${CLOUDS:-0}" = 1 ] && extra=""
-        r=$(SL3D_LIB=$PWD/$lib python3 bench.py --no-cpu-baseline --no-side $extra --steps 1500 --warmup 300 "$@" 2>>gpurun_out/ab_stderr.log | python3 -c "
+        extra="--no-clouds"; [ "${CLOUDS:-0}" = 1 ] && extra="--full"
+        r=$(SL3D_LIB=$PWD/$lib python3 bench.py --no-cpu-baseline --no-side $extra --steps 1500 --warmup 300 "$@" 2>>"$ERR" | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d.get('to_compacted_clouds') or {}; k=(c.get('kernel_only') or {}).get('value')
 print(d['value'], d['roofline']['frac'], d['ms_per_step'], '| clouds', c.get('value'), k)")
       fi

@@ -34,10 +34,10 @@ cp $T/${TAG}_oneview_cold_lanes.out $T/${TAG}_oneview_cold_lanes_under_rocprof.j
 # the 16-view launches of the other kernel families (rig classes 2 / 3 / 0, 9 and 14 Gray planes): one rocprofv3 row per side.* figure
 STATS_LINES=8 stats ${TAG}_families python3 bench.py --families-only
 cp $T/${TAG}_families.out $T/${TAG}_families.json
-STATS_LINES=4 stats ${TAG}_rig3 python3 bench.py --rig radial --no-cpu-baseline --no-side
+STATS_LINES=4 stats ${TAG}_rig3 python3 bench.py --full --rig radial --no-cpu-baseline --no-side
 cp $T/${TAG}_rig3.out $T/${TAG}_rig3_bench_under_rocprof.json
 SL3D_SHIM_TIMING=1 timeout 900 python3 tools/shim_timing.py 7 > $T/${TAG}_shim_scan_ms.json 2> $T/shim_timing.err
-timeout 900 python3 bench.py > $T/${TAG}_bench.json 2> $T/bench.err
+timeout 900 python3 bench.py --full > $T/${TAG}_bench.json 2> $T/bench.err
 timeout 600 python3 bench.py --steps 20 --warmup 5 > $T/${TAG}_bench_driver_args.json 2> $T/bench_driver.err
 python3 -c "
 import json
