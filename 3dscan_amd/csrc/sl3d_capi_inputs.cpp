@@ -261,6 +261,75 @@ SL3D_CATCH(x)
 
 extern "C" int sl3d_set_mask(sl3d_ctx *x, int view, const uint8_t *m, size_t stride) { return sl3d_set_masks(x, view, 1, m, stride, 0); }
 
+// sl3d_set_masks with the fringe-modulation test (sl3d_modulation.h; the reference's check_I_mod_criteria, 3/wrapped_phase.cpp:63-104):
+// the mask hand-over of sl3d_set_masks through the staging plane, one slot per view (a view's selection depends on its own frames);
+// k_modulation_select then rewrites each slot's frame region with the final 0/1 selection from the frames resident at that point of the
+// stream, and the slots go on like any staged mask: deferred to the next MASKIN launch, or through k_mask_prepare.  Whole frames
+// and three fringes only: the 2-pixel halo of a window lies in frames the context does not hold.
+extern "C" int sl3d_set_masks_modulated(sl3d_ctx *x, int first_view, int n_views, double min_modulation, const uint8_t *m, size_t stride,
+                                        size_t view_stride)
+try {
+    int rc = check_view(x, first_view, n_views);
+    if (rc) return rc;
+    if (std::isnan(min_modulation)) return fail(x, SL3D_E_INVALID_ARG, "set_masks_modulated: the threshold is NaN");
+    if (m && stride < (size_t)x->cfg.full_width) return fail(x, SL3D_E_INVALID_ARG, "set_masks_modulated: mask stride < full_width");
+    if (m && view_stride != 0 && view_stride < stride * (size_t)(x->cfg.full_height - 1) + (size_t)x->cfg.full_width)
+        return fail(x, SL3D_E_INVALID_ARG, "set_masks_modulated: view_stride is smaller than one mask (0 = the same mask for every view)");
+    const KParams &P = x->P;
+    if (P.F != 3) return fail(x, SL3D_E_UNSUPPORTED, "set_masks_modulated: the modulation test is defined for n_fringe == 3 only");
+    if (P.W != P.fullW || P.H != P.fullH)
+        return fail(x, SL3D_E_UNSUPPORTED, "set_masks_modulated: whole frames only (the halo of a window or stripe lies in frames the context does not hold)");
+    ON_DEVICE(x);  // (the staging plane is rewritten and the frames are read: behind every launch the lanes hold)
+    MaskSrc S;
+    const MaskRegion g = mask_region(P, S);
+    const int kind = m ? memory_kind(m + (size_t)g.gy0 * stride + (size_t)g.gx0) : 1;
+    rc = ensure_mask_staging(x, n_views);
+    if (rc || (rc = supersede_masks(x, first_view, n_views, n_views))) return rc;
+    for (int k = 0; m && k < n_views; k++) {
+        uint8_t *dst = x->d_mask_raw + (size_t)k * P.mask_view_stride + (size_t)S.r0 * P.mpitch + S.bx0;
+        HIPCHK_DRAIN(x, hipMemcpy2DAsync(dst, P.mpitch, m + (size_t)k * view_stride + (size_t)g.gy0 * stride + g.gx0, stride, (size_t)(g.gx1 - g.gx0),
+                                         (size_t)(g.gy1 - g.gy0), hipMemcpyDefault, x->stream));
+    }
+    rc = launched(x, launch_modulation_select(P, first_view, n_views, x->d_mask_raw, m != nullptr, min_modulation, x->stream));
+    if (rc) {
+        (void)hipStreamSynchronize(x->stream);  // (no copy from the caller's memory still runs when the error is returned)
+        return rc;
+    }
+    S.origin = (uintptr_t)x->d_mask_raw;
+    S.stride = (size_t)P.mpitch;
+    S.view_stride = P.mask_view_stride;
+    if (can_defer(x, n_views, S, 0, P.mpitch)) {
+        defer_masks(x, first_view, n_views, S, true, 0, P.mpitch);
+    } else {
+        rc = prepare_masks(x, first_view, n_views, S);
+        if (rc) return rc;
+    }
+    if (kind == 0) HIPCHK(x, hipStreamSynchronize(x->stream));  // pageable source: consumed before we return
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// gamma of one axis of one view (sl3d_modulation.h), window-sized: k_modulation_gamma into the [col][row] scratch, one 2-D copy out
+extern "C" int sl3d_get_modulation(sl3d_ctx *x, int view, int axis, float *out, size_t stride_elems)
+try {
+    int rc = check_view(x, view);
+    if (rc) return rc;
+    const KParams &P = x->P;
+    if (!out || (axis != 0 && axis != 1) || stride_elems < (size_t)P.W)
+        return fail(x, SL3D_E_INVALID_ARG, "get_modulation: null output, axis not 0 / 1, or stride_elems < width");
+    if (P.F != 3) return fail(x, SL3D_E_UNSUPPORTED, "get_modulation: the modulation is defined for n_fringe == 3 only");
+    ON_DEVICE(x);
+    rc = ensure_colrow(x, (size_t)P.pitch * P.H * sizeof(float));
+    if (rc) return rc;
+    rc = launched(x, launch_modulation_gamma(P, view, axis, (float *)x->d_colrow, x->stream));
+    if (rc) return rc;
+    HIPCHK(x, hipMemcpy2DAsync(out, stride_elems * sizeof(float), x->d_colrow, (size_t)P.pitch * sizeof(float), (size_t)P.W * sizeof(float), (size_t)P.H,
+                               hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
 int ensure_colrow(sl3d_ctx *x, size_t bytes)
 {
     if (x->d_colrow && x->colrow_bytes >= bytes) return SL3D_OK;

@@ -185,6 +185,12 @@ int fused_tiles(const KParams &P);  // number of 1024-pixel tiles per view (KPar
 // k_mask_prepare over views [first_view, first_view + n_views): view k reads S.origin + k * S.view_stride; block b of view v stores
 // {seq, quads with a valid pixel} at partials[v * mask_prepare_blocks(P) + b] (host memory mapped into the device)
 int launch_mask_prepare(const KParams &P, int first_view, int n_views, const MaskSrc &S, unsigned long long *partials, unsigned seq, void *stream);
+// the fringe-modulation test (sl3d_modulation.hip, sl3d_modulation.h): views [first_view, first_view + n_views) -> slot k of the mask staging
+// plane `staging` (mask_view_stride bytes apart) gets view first_view + k's selection, 0/1 bytes over its frame region (has_mask: ANDed
+// with the mask bytes == 1 already staged there); whole frames, F == 3 only
+int launch_modulation_select(const KParams &P, int first_view, int n_views, uint8_t *staging, bool has_mask, double thr, void *stream);
+// gamma of one axis of one view -> out[row * pitch + col] (pitch * H floats, 16-byte aligned)
+int launch_modulation_gamma(const KParams &P, int view, int axis, float *out, void *stream);
 int mask_prepare_blocks(const KParams &P);
 int launch_to_colrow(const KParams &P, int view, int which, void *dst, void *stream);  // a global in the reference's [col][row] layout
 int launch_mask_from_colrow(const KParams &P, const int *sel, int gx0, int gy0, int ncols, int nrows, uint8_t *raw, void *stream);

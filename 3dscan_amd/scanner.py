@@ -22,7 +22,7 @@ VALID_VERTICAL, VALID_HORIZONTAL, VALID_MERGED = 0, 1, 2
 # every symbol include/sl3d.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
     "sl3d_version", "sl3d_strerror", "sl3d_last_error", "sl3d_create", "sl3d_destroy",
-    "sl3d_set_calibration", "sl3d_get_projection_matrices", "sl3d_set_mask", "sl3d_set_masks", "sl3d_set_mask_colrow", "sl3d_set_frames_range", "sl3d_get_global_colrow", "sl3d_set_frames", "sl3d_copy_view", "sl3d_synth_view", "sl3d_get_frames",
+    "sl3d_set_calibration", "sl3d_get_projection_matrices", "sl3d_set_mask", "sl3d_set_masks", "sl3d_set_masks_modulated", "sl3d_get_modulation", "sl3d_set_mask_colrow", "sl3d_set_frames_range", "sl3d_get_global_colrow", "sl3d_set_frames", "sl3d_copy_view", "sl3d_synth_view", "sl3d_get_frames",
     "sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_compute_c_p_map", "sl3d_triangulate",
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
@@ -93,6 +93,12 @@ def load_library(path=None):
         L.sl3d_last_fused_kernel_name.argtypes = [vp, C.c_char_p, C.c_size_t]
         L.sl3d_camera_table_bytes_per_pixel.argtypes = [vp, i]
     except AttributeError:   # an older build of the library under SL3D_LIB (A/B runs against a previous round)
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        L.sl3d_set_masks_modulated.argtypes = [vp, i, i, C.c_double, vp, C.c_size_t, C.c_size_t]
+        L.sl3d_get_modulation.argtypes = [vp, i, i, vp, C.c_size_t]
+    except AttributeError:   # a build before 0.7.0 under SL3D_LIB (A/B runs against the parent): everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -270,6 +276,36 @@ class Scanner:
             assert a.shape == (self.H, self.W), a.shape
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         self._chk(self.L.sl3d_set_frames(self._h, view, axis, ptrs, len(arrs), arrs[0].strides[0]), "sl3d_set_frames")
+
+    def set_masks_modulated(self, min_modulation, masks=None, first_view=0, n_views=None):
+        """set_masks with the fringe-modulation test (sl3d_set_masks_modulated): a pixel stays selected iff its mask byte is 1 (no mask:
+        every pixel) and the modulation gamma of both axes' fringes, as resident now, is > min_modulation.  masks: None, one full-frame
+        mask (every view gets it) or an array [n][full_height][full_width].  Whole-frame contexts with 3 fringes only."""
+        if masks is None:
+            n = self.cfg.max_views - first_view if n_views is None else n_views
+            ptr, stride, vs = None, 0, 0
+        else:
+            m = np.ascontiguousarray(masks, dtype=np.uint8)
+            if m.ndim == 2:
+                assert m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
+                n, vs = (self.cfg.max_views - first_view if n_views is None else n_views), 0
+            else:
+                assert m.shape[1:] == (self.cfg.full_height, self.cfg.full_width), m.shape
+                n, vs = m.shape[0], m.strides[0]
+                assert n_views is None or n_views == n
+            ptr, stride = m.ctypes.data, m.strides[-2]
+        self._chk(self.L.sl3d_set_masks_modulated(self._h, first_view, n, float(min_modulation), ptr, stride, vs), "sl3d_set_masks_modulated")
+
+    def set_masks_modulated_device(self, min_modulation, dev_ptr, stride, view_stride, first_view=0, n_views=1):
+        """set_masks_modulated with masks that already live in device memory (a raw address, e.g. torch.Tensor.data_ptr())."""
+        self._chk(self.L.sl3d_set_masks_modulated(self._h, first_view, n_views, float(min_modulation), C.c_void_p(dev_ptr), stride, view_stride),
+                  "sl3d_set_masks_modulated")
+
+    def modulation(self, axis, view=0):
+        """gamma of one axis (sl3d_get_modulation): float32 [H][W] of the window, NaN where the three fringe bytes are all 0."""
+        out = np.empty((self.H, self.W), dtype=np.float32)
+        self._chk(self.L.sl3d_get_modulation(self._h, view, axis, out.ctypes.data, self.W), "sl3d_get_modulation")
+        return out
 
     def set_mask_colrow(self, selected_region, view=0):
         """selected_region as the reference holds it: int32 array [full_width][full_height] ([col][row]), selected iff == 1."""

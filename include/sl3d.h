@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.6.0"
+#define SL3D_VERSION_STRING "0.7.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -178,6 +178,29 @@ int sl3d_set_mask(sl3d_ctx *ctx, int view, const uint8_t *full_frame_mask, size_
  * (SL3D_FLAG_EAGER_MASK); otherwise the rows go through the staging plane by a device copy.  This is the per-scan device cost of image_scissor()'s result (m_tech_project_console.cpp:366) + stage
  * 3's boundary removal (3/wrapped_phase.cpp:253-279): bench.py `side.per_scan_device`. */
 int sl3d_set_masks(sl3d_ctx *ctx, int first_view, int n_views, const uint8_t *full_frame_masks, size_t stride, size_t view_stride);
+
+/* sl3d_set_masks with the fringe-modulation test that rejects shadow and background pixels (the criterion the reference wrote as
+ * check_I_mod_criteria, 3/wrapped_phase.cpp:63-104, "another criteria to eliminate shadow+background", and left commented out).  Per
+ * pixel and axis, from the three fringe bytes I0, I1, I2 of that axis as they sit in the view's frame stack:
+ *     d = I0 - I2,  e = 2*I1 - I0 - I2,  gamma = sqrtf((float)(3*d*d + e*e)) / (float)(I0 + I1 + I2)     (float; I0 = I1 = I2 = 0: NaN)
+ * and the view's selection is   (full_frame_masks == NULL || mask byte == 1) && (double)gamma_v > min_modulation && (double)gamma_h > min_modulation
+ * (strict, in double, as 3/wrapped_phase.cpp:96; NaN never passes; the reference's default threshold is 0.01).  Stage 3's boundary
+ * removal then runs on that selection exactly as on a lasso.  A deliberate difference from the reference: its (never run) code tests
+ * each axis before that axis' own boundary removal; this library keeps ONE selection per view, so the two axes' tests are ANDed first.
+ * The masks are handed over as for sl3d_set_masks (pageable, pinned or device memory, view_stride == 0: the same mask for every view;
+ * the same lifetime rules) or not at all (NULL: every pixel is selected; stride and view_stride are then ignored), with one launch for
+ * all views of the call.  Each view's selection is made from that view's frames as they are resident when the call is enqueued:
+ * frames replaced afterwards do not change it -- set the frames first.  SL3D_E_UNSUPPORTED unless n_fringe == 3 and the window is the
+ * whole frame (the 2-pixel halo of a window or row stripe lies in frames the context does not hold: derive the mask on a whole-frame
+ * context with sl3d_get_modulation and hand it over with sl3d_set_mask / sl3d_group_set_mask); SL3D_E_INVALID_ARG for a NaN
+ * threshold, bad views or strides.  A refused call leaves every view's previous selection as it was. */
+int sl3d_set_masks_modulated(sl3d_ctx *ctx, int first_view, int n_views, double min_modulation, const uint8_t *full_frame_masks, size_t stride,
+                             size_t view_stride);
+
+/* gamma of one axis (0 = vertical, 1 = horizontal fringes) of one view as sl3d_set_masks_modulated computes it, window-sized row-major
+ * floats (out[row * stride_elems + col], stride_elems >= width); NaN where I0 + I1 + I2 == 0.  Any window (gamma needs no halo);
+ * n_fringe == 3 only (SL3D_E_UNSUPPORTED).  What a caller looks at to choose a threshold.  Synchronises. */
+int sl3d_get_modulation(sl3d_ctx *ctx, int view, int axis, float *out, size_t stride_elems);
 
 /* The captured frames of one axis of one view, window-sized planes in host memory: what
  * read_image() 3/wrapped_phase.cpp:29-58 (n_fringe planes) and read_captured_images()
