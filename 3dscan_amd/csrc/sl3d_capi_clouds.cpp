@@ -1,5 +1,5 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
-// downloads, registration), the compaction of a dense result with colour, turntable registration.
+// downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
 #include "sl3d_capi_internal.h"
 
 // ---- compacted clouds straight from the fused kernel ----------------------------------------------------------------
@@ -444,6 +444,94 @@ try {
     *total = off;
     const int64_t m = off < capacity ? off : capacity;
     if (xyz && m > 0) HIPCHK(x, hipMemcpyAsync(xyz, x->d_reg, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// ---- the mesh over a dense result (sl3d_mesh.h: the definition; sl3d_mesh.hip: the kernels) ---------------------------------------
+static int ensure_mesh_buffers(sl3d_ctx *x)
+{
+    if (x->mesh_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, nb = (P.px_view_stride + 1023) / 1024, nc = (size_t)mesh_chunks(P);
+    x->mesh_face_stride = std::max<size_t>(1, 2 * (size_t)(P.W - 1) * (size_t)(P.H - 1));
+    int rc = SL3D_OK;
+    if (!x->d_mesh_cnt) rc = dev_alloc(x, &x->d_mesh_cnt, mv * 2 * nc);
+    if (!rc && !x->d_mesh_off) rc = dev_alloc(x, &x->d_mesh_off, mv * 2 * nc);
+    if (!rc && !x->d_mesh_tot) rc = dev_alloc(x, &x->d_mesh_tot, mv * 2);
+    if (!rc && !x->d_mesh_blk_cnt) rc = dev_alloc(x, &x->d_mesh_blk_cnt, mv * nb);
+    if (!rc && !x->d_mesh_blk_off) rc = dev_alloc(x, &x->d_mesh_blk_off, mv * nb);
+    if (!rc && !x->d_mesh_blk_tot) rc = dev_alloc(x, &x->d_mesh_blk_tot, mv);
+    if (!rc && !x->d_mesh_xyz) rc = dev_alloc(x, &x->d_mesh_xyz, mv * P.px_view_stride * 3);
+    if (!rc && !x->d_mesh_faces) rc = dev_alloc(x, &x->d_mesh_faces, mv * x->mesh_face_stride * 3);
+    if (rc) return rc;
+    x->mesh_ready = true;
+    return SL3D_OK;
+}
+
+static int check_mesh_args(sl3d_ctx *x, int first_view, int n_views, float max_edge, const int64_t *n_vertices, const int64_t *n_faces)
+{
+    const int rc = check_view(x, first_view, n_views);
+    if (rc) return rc;
+    if (!n_vertices || !n_faces) return fail(x, SL3D_E_INVALID_ARG, "null argument");
+    if (!(max_edge > 0.0f)) return fail(x, SL3D_E_INVALID_ARG, "max_edge must be > 0 (+inf: no edge-length test)");
+    return SL3D_OK;
+}
+
+// Vertices: the batched compaction as it stands, into the mesh's own cloud buffer.  Faces: count, scan (k_compact_scan over the 2
+// count arrays of every view), emit.  Six launches, one read-back of the 2 totals per view.
+extern "C" int sl3d_mesh_views(sl3d_ctx *x, int first_view, int n_views, float max_edge, sl3d_mesh *device_mesh, int64_t *n_vertices,
+                               int64_t *n_faces)
+try {
+    int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_faces);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    rc = ensure_mesh_buffers(x);
+    if (rc) return rc;
+    float *xyz = x->d_mesh_xyz + 3 * (size_t)first_view * P.px_view_stride;
+    rc = launched(x, launch_compact_views(P, first_view, n_views, x->d_mesh_blk_cnt, x->d_mesh_blk_off, x->d_mesh_blk_tot + first_view, xyz, x->stream));
+    if (rc) return rc;
+    rc = launched(x, launch_mesh_views(P, first_view, n_views, max_edge, x->d_mesh_cnt, x->d_mesh_off, x->d_mesh_tot, x->d_mesh_faces,
+                                       x->mesh_face_stride, x->stream));
+    if (rc) return rc;
+    std::vector<unsigned long long> t(2 * (size_t)n_views);
+    HIPCHK(x, hipMemcpyAsync(t.data(), x->d_mesh_tot + 2 * (size_t)first_view, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    for (int v = 0; v < n_views; v++) {
+        n_vertices[v] = (int64_t)t[2 * (size_t)v];
+        n_faces[v] = (int64_t)t[2 * (size_t)v + 1];
+    }
+    if (device_mesh) {
+        device_mesh->xyz = xyz;
+        device_mesh->faces = x->d_mesh_faces + 3 * (size_t)first_view * x->mesh_face_stride;
+        device_mesh->view_stride_points = P.px_view_stride;
+        device_mesh->view_stride_faces = x->mesh_face_stride;
+    }
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: the clouds of the views back to back in xyz, their faces back to back in faces (ids relative to the view's own cloud)
+extern "C" int sl3d_get_meshes(sl3d_ctx *x, int first_view, int n_views, float max_edge, float *xyz, int64_t vertex_capacity, int32_t *faces,
+                               int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces)
+try {
+    int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_faces);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    sl3d_mesh m;
+    rc = sl3d_mesh_views(x, first_view, n_views, max_edge, &m, n_vertices, n_faces);
+    if (rc) return rc;
+    int64_t voff = 0, foff = 0;
+    for (int v = 0; v < n_views; v++) {
+        const int64_t nv = xyz ? std::min<int64_t>(n_vertices[v], vertex_capacity - voff) : 0;
+        const int64_t nf = faces ? std::min<int64_t>(n_faces[v], face_capacity - foff) : 0;
+        if (nv > 0) HIPCHK_DRAIN(x, hipMemcpyAsync(xyz + 3 * voff, m.xyz + 3 * (size_t)v * m.view_stride_points, (size_t)nv * 12, hipMemcpyDeviceToHost, x->stream));
+        if (nf > 0) HIPCHK_DRAIN(x, hipMemcpyAsync(faces + 3 * foff, m.faces + 3 * (size_t)v * m.view_stride_faces, (size_t)nf * 12, hipMemcpyDeviceToHost, x->stream));
+        voff += nv > 0 ? nv : 0;
+        foff += nf > 0 ? nf : 0;
+    }
     SYNC_FOR_CALLER(x);
     return SL3D_OK;
 }

@@ -92,6 +92,16 @@ struct sl3d_ctx {
     // per view, after sl3d_run_clouds: 0 = k_seg_scan has run (offsets and total valid), 1 = not scanned -- a launch of a few views
     // leaves the scan to the consumer (k_seg_close<.., SCAN>), 2 = a scanning consumer has left the total, the offsets are still unset
     std::vector<uint8_t> scan_state;
+    // sl3d_mesh_views (all allocated on first use): [max_views][2][mesh_chunks] counts of valid pixels / faces per chunk, their
+    // exclusive scans, [max_views][2] totals; the faces: [max_views][mesh_face_stride][3] vertex ids into the view's cloud in d_mesh_xyz
+    // ([max_views][px_view_stride][3], written by launch_compact_views with block scratch of its own: nothing another call handed out
+    // is overwritten)
+    unsigned *d_mesh_cnt = nullptr, *d_mesh_blk_cnt = nullptr;
+    unsigned long long *d_mesh_off = nullptr, *d_mesh_tot = nullptr, *d_mesh_blk_off = nullptr, *d_mesh_blk_tot = nullptr;
+    int32_t *d_mesh_faces = nullptr;
+    float *d_mesh_xyz = nullptr;
+    size_t mesh_face_stride = 0;
+    bool mesh_ready = false;                  // ensure_mesh_buffers ran to its end
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     uint8_t *d_texture = nullptr;             // [view][row][pitch][3] BGR texture of save_point_cloud (allocated by sl3d_set_texture)

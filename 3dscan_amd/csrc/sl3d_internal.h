@@ -207,6 +207,13 @@ int launch_compact(const KParams &P, int view, unsigned *block_counts, unsigned 
                    float *cloud, const uint8_t *texture, uint8_t *rgb_out, void *stream);
 int launch_compact_views(const KParams &P, int first_view, int n_views, unsigned *block_counts, unsigned long long *block_offsets,
                          unsigned long long *totals, float *clouds, void *stream);
+int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, int n_arrays, unsigned long long *totals, void *stream);
+// the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A view has
+// mesh_chunks(P) chunks (1024 pixels of one row); counts / offsets: [max_views][2][chunks] (valid pixels, faces) and their exclusive scans,
+// totals: [max_views][2], faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)
+int mesh_chunks(const KParams &P);
+int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
+                      unsigned long long *totals, int *faces, size_t face_stride, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

@@ -675,6 +675,13 @@ int launch_compact_views(const KParams &P, int first_view, int n_views, unsigned
     return (int)hipGetLastError();
 }
 
+// k_compact_scan for another unit (sl3d_mesh.hip): n_arrays independent arrays of n counts each, back to back
+int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, int n_arrays, unsigned long long *totals, void *stream)
+{
+    hipLaunchKernelGGL(k_compact_scan, dim3(n_arrays), dim3(1024), 0, (hipStream_t)stream, counts, offsets, n, totals);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Consumers of the SEGMENTED clouds the fused kernel writes (k_fused<..., CMODE = 2>): a view's cloud is the concatenation of
 // its segments' first `count` points.  One wave per segment, one point (12 bytes) per lane and step.

@@ -1,0 +1,163 @@
+// sl3d_mesh.hip -- the mesh stage: ordered triangles over the organized point grid of a dense result (sl3d_mesh_views; the
+// definition and its arithmetic: sl3d_mesh.h).  The vertices are the compacted cloud launch_compact_views writes; this unit adds
+//   k_mesh_count : per chunk (1024 pixels of ONE row) the valid pixels of the chunk and the faces of the cells whose corner a lies in it
+//   (k_compact_scan over the 2 count arrays of every view: sl3d_kernels.hip)
+//   k_mesh_emit  : the same cells again, every face ranked by wave prefixes and written at face_offset[chunk] + rank
+// A lane owns one quad of row r -- 4 cells: its own 4 pixels of rows r and r + 1 (one dword of valid bytes and three 16-byte loads of
+// points per row) and the pixel right of them (the corners b / e of its last cell), which the neighbouring lane has requested too: those
+// loads hit the cache the neighbour's lines are in.  No index plane: the vertex id of a pixel is its chunk's offset plus the valid
+// pixels of the chunk in front of it, for row r + 1 from ITS chunk's offset -- both are prefixes over bytes the block holds anyway.
+// No atomics: every output position follows from the scans, so the result does not depend on the launch shape, the batch or the run.
+#include <hip/hip_runtime.h>
+
+#include "sl3d_internal.h"
+#include "sl3d_mesh.h"
+
+namespace sl3d {
+
+#define MESH_CHUNK 1024  // pixels of a row per block: 256 lanes x one quad
+
+// the lane's 4 cells (a = pixel c0 + k of row r): v0 / v1 = valid bits of pixels c0 .. c0 + 4 of rows r / r + 1 (bit 4: the pixel right
+// of the quad; 0 beyond the window), cell[k] = mesh_cell of cell k.  row0 / pts0: row r of the valid / points plane.
+__device__ __forceinline__ void mesh_lane(const uint8_t *__restrict__ row0, const float *__restrict__ pts0, int W, int pitch, int c0, bool next_row,
+                                          double thr2, unsigned &v0, unsigned &v1, unsigned cell[4])
+{
+    v0 = v1 = 0u;
+    cell[0] = cell[1] = cell[2] = cell[3] = 0u;
+    if (c0 >= W) return;
+    const unsigned in_w = W - c0 >= 4 ? 15u : (1u << (W - c0)) - 1u;
+    const bool right = c0 + 4 < W;
+    // every valid byte the lane needs, requested before the first is looked at
+    const unsigned w0 = *(const unsigned *)(row0 + c0);
+    const unsigned w1 = next_row ? *(const unsigned *)(row0 + pitch + c0) : 0u;
+    const unsigned r0 = right ? row0[c0 + 4] : 0u;
+    const unsigned r1 = right && next_row ? row0[pitch + c0 + 4] : 0u;
+    v0 = (((w0 & 1u) | (w0 >> 7 & 2u) | (w0 >> 14 & 4u) | (w0 >> 21 & 8u)) & in_w) | (r0 & 1u) << 4;
+    v1 = (((w1 & 1u) | (w1 >> 7 & 2u) | (w1 >> 14 & 4u) | (w1 >> 21 & 8u)) & in_w) | (r1 & 1u) << 4;
+    if (!v0 || !v1) return;  // a face has a corner in either row
+    const float4 *p0 = (const float4 *)(pts0 + 3 * (size_t)c0);
+    const float4 *p1 = (const float4 *)(pts0 + 3 * ((size_t)pitch + c0));
+    const float4 a0 = p0[0], a1 = p0[1], a2 = p0[2], b0 = p1[0], b1 = p1[1], b2 = p1[2];
+    float q0[15] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, 0.0f, 0.0f, 0.0f};
+    float q1[15] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, 0.0f, 0.0f, 0.0f};
+    if (v0 & 16u) {
+        const float *s = pts0 + 3 * (size_t)(c0 + 4);
+        q0[12] = s[0], q0[13] = s[1], q0[14] = s[2];
+    }
+    if (v1 & 16u) {
+        const float *s = pts0 + 3 * ((size_t)pitch + c0 + 4);
+        q1[12] = s[0], q1[13] = s[1], q1[14] = s[2];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const unsigned vb = (v0 >> k & 3u) | (v1 >> k & 3u) << 2;  // a, b, d, e
+        cell[k] = mesh_cell(vb, &q0[3 * k], &q0[3 * k + 3], &q1[3 * k], &q1[3 * k + 3], thr2);
+    }
+}
+
+// grid (chunks of a row, H, views); counts: [view][2][H * chunks]: valid pixels, faces
+__global__ __launch_bounds__(256) void k_mesh_count(const uint8_t *__restrict__ valid, const float *__restrict__ points, int W, int H, int pitch,
+                                                    size_t view_stride, double thr2, unsigned *__restrict__ counts)
+{
+    const int r = blockIdx.y, nck = gridDim.x, chunk = r * nck + blockIdx.x, n_chunks = H * nck;
+    valid += (size_t)blockIdx.z * view_stride + (size_t)r * pitch;
+    points += 3 * ((size_t)blockIdx.z * view_stride + (size_t)r * pitch);
+    counts += (size_t)blockIdx.z * 2 * n_chunks;
+    __shared__ unsigned s_cnt[4];
+    unsigned v0, v1, cell[4];
+    mesh_lane(valid, points, W, pitch, blockIdx.x * MESH_CHUNK + threadIdx.x * 4, r + 1 < H, thr2, v0, v1, cell);
+    // both counts in one word: at most 1024 pixels and 2048 faces per chunk
+    unsigned c = __popc(v0 & 15u) | ((cell[0] & 3u) + (cell[1] & 3u) + (cell[2] & 3u) + (cell[3] & 3u)) << 16;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned t = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        counts[chunk] = t & 0xffffu;
+        counts[n_chunks + chunk] = t >> 16;
+    }
+}
+
+// grid (chunks of a row, H - 1, views); offsets: [view][2][H * chunks] exclusive scans of the counts; faces: [view][face_stride][3]
+__global__ __launch_bounds__(256) void k_mesh_emit(const uint8_t *__restrict__ valid, const float *__restrict__ points, int W, int H, int pitch,
+                                                   size_t view_stride, double thr2, const unsigned *__restrict__ counts,
+                                                   const unsigned long long *__restrict__ offsets, int *__restrict__ faces, size_t face_stride)
+{
+    const int r = blockIdx.y, nck = gridDim.x, chunk = r * nck + blockIdx.x, n_chunks = H * nck;
+    counts += (size_t)blockIdx.z * 2 * n_chunks;
+    if (counts[n_chunks + chunk] == 0) return;  // (the whole block: nothing to write)
+    valid += (size_t)blockIdx.z * view_stride + (size_t)r * pitch;
+    points += 3 * ((size_t)blockIdx.z * view_stride + (size_t)r * pitch);
+    offsets += (size_t)blockIdx.z * 2 * n_chunks;
+    faces += 3 * (size_t)blockIdx.z * face_stride;
+    __shared__ unsigned s_wave_v[4], s_wave_f[4];
+    __shared__ int s_faces[2 * MESH_CHUNK * 3];  // the block's faces in output order
+    unsigned v0, v1, cell[4];
+    mesh_lane(valid, points, W, pitch, blockIdx.x * MESH_CHUNK + threadIdx.x * 4, true, thr2, v0, v1, cell);
+    // exclusive prefixes over the block: valid pixels of row r (low half) and of row r + 1 (high half) in one word, faces in another
+    const unsigned cv = __popc(v0 & 15u) | __popc(v1 & 15u) << 16;
+    const unsigned cf = (cell[0] & 3u) + (cell[1] & 3u) + (cell[2] & 3u) + (cell[3] & 3u);
+    unsigned iv = cv, jf = cf;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned tv = __shfl_up(iv, off, 64), tf = __shfl_up(jf, off, 64);
+        if ((threadIdx.x & 63) >= off) iv += tv, jf += tf;
+    }
+    if ((threadIdx.x & 63) == 63) s_wave_v[threadIdx.x >> 6] = iv, s_wave_f[threadIdx.x >> 6] = jf;
+    __syncthreads();
+    unsigned base_v = 0, base_f = 0;
+    for (int i = 0; i < (int)(threadIdx.x >> 6); i++) base_v += s_wave_v[i], base_f += s_wave_f[i];
+    const unsigned block_faces = s_wave_f[0] + s_wave_f[1] + s_wave_f[2] + s_wave_f[3];
+    if (cf) {
+        const unsigned ev = base_v + (iv - cv);
+        // vertex ids of pixels c0 .. c0 + 4 of both rows; the pixel right of the block's last quad is the next chunk's first, whose
+        // offset is this chunk's offset plus this chunk's count: the same expression
+        const int id0 = (int)offsets[chunk] + (int)(ev & 0xffffu), id1 = (int)offsets[chunk + nck] + (int)(ev >> 16);
+        int id[2][5];
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            id[0][j] = id0 + __popc(v0 & ((1u << j) - 1u));
+            id[1][j] = id1 + __popc(v1 & ((1u << j) - 1u));
+        }
+        unsigned rank = base_f + (jf - cf);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+#pragma unroll
+            for (int f = 0; f < 2; f++)
+                if ((int)(cell[k] & 3u) > f) {
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        const unsigned cn = mesh_corner(cell[k], f, j);
+                        const int lo = (cn & 2u) ? id[1][k] : id[0][k], hi = (cn & 2u) ? id[1][k + 1] : id[0][k + 1];
+                        s_faces[3 * rank + j] = (cn & 1u) ? hi : lo;
+                    }
+                    rank++;
+                }
+    }
+    __syncthreads();
+    // the block's faces are contiguous in the output: coalesced dword stores
+    int *dst = faces + 3 * offsets[n_chunks + chunk];
+    for (unsigned i = threadIdx.x; i < 3 * block_faces; i += 256) dst[i] = s_faces[i];
+}
+
+int mesh_chunks(const KParams &P) { return P.H * ((P.W + MESH_CHUNK - 1) / MESH_CHUNK); }
+
+int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
+                      unsigned long long *totals, int *faces, size_t face_stride, void *stream)
+{
+    const int nck = (P.W + MESH_CHUNK - 1) / MESH_CHUNK, n_chunks = P.H * nck;
+    const uint8_t *valid = P.valid + (size_t)first_view * P.px_view_stride;
+    const float *points = P.points + 3 * (size_t)first_view * P.px_view_stride;
+    counts += (size_t)first_view * 2 * n_chunks;
+    offsets += (size_t)first_view * 2 * n_chunks;
+    const double thr2 = mesh_thr2(max_edge);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_mesh_count, dim3(nck, P.H, n_views), dim3(256), 0, st, valid, points, P.W, P.H, P.pitch, P.px_view_stride, thr2, counts);
+    int rc = launch_compact_scan(counts, offsets, n_chunks, 2 * n_views, totals + 2 * (size_t)first_view, stream);
+    if (rc) return rc;
+    if (P.H > 1)
+        hipLaunchKernelGGL(k_mesh_emit, dim3(nck, P.H - 1, n_views), dim3(256), 0, st, valid, points, P.W, P.H, P.pitch, P.px_view_stride, thr2,
+                           (const unsigned *)counts, (const unsigned long long *)offsets, faces + 3 * (size_t)first_view * face_stride, face_stride);
+    return (int)hipGetLastError();
+}
+
+}  // namespace sl3d

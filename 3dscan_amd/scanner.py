@@ -27,7 +27,7 @@ ABI_SYMBOLS = (
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
-    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
+    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
     "sl3d_get_device_buffers", "sl3d_download", "sl3d_download_2d",
     "sl3d_group_create", "sl3d_group_destroy", "sl3d_group_last_error", "sl3d_group_size", "sl3d_group_stripe", "sl3d_group_transport",
     "sl3d_group_set_calibration", "sl3d_group_set_mask", "sl3d_group_set_frames", "sl3d_group_run", "sl3d_group_gather",
@@ -60,6 +60,11 @@ class DeviceBuffers(C.Structure):
 class CloudSegments(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("counts", C.c_void_p), ("offsets", C.c_void_p), ("n_segments", C.c_int32), ("segment_points", C.c_int32),
                 ("view_stride_points", C.c_size_t), ("view_stride_segments", C.c_size_t)]
+
+
+class Mesh(C.Structure):
+    """sl3d_mesh: device addresses of the clouds and faces sl3d_mesh_views left in HBM"""
+    _fields_ = [("xyz", C.c_void_p), ("faces", C.c_void_p), ("view_stride_points", C.c_size_t), ("view_stride_faces", C.c_size_t)]
 
 
 _lib = None
@@ -99,6 +104,12 @@ def load_library(path=None):
         L.sl3d_set_masks_modulated.argtypes = [vp, i, i, C.c_double, vp, C.c_size_t, C.c_size_t]
         L.sl3d_get_modulation.argtypes = [vp, i, i, vp, C.c_size_t]
     except AttributeError:   # a build before 0.7.0 under SL3D_LIB (A/B runs against the parent): everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        L.sl3d_mesh_views.argtypes = [vp, i, i, C.c_float, C.POINTER(Mesh), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.sl3d_get_meshes.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    except AttributeError:   # a build before 0.8.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -571,6 +582,32 @@ class Scanner:
             out.append(flat[off:off + n])
             off += n
         return out
+
+    def mesh_device(self, max_edge, first_view=0, n_views=1):
+        """sl3d_mesh_views: the meshes of a batch of views left in HBM; returns (Mesh, vertex counts, face counts)."""
+        m, nv, nf = Mesh(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_mesh_views(self._h, first_view, n_views, float(max_edge), C.byref(m), nv, nf), "sl3d_mesh_views")
+        return m, [int(c) for c in nv], [int(c) for c in nf]
+
+    def meshes(self, max_edge, first_view=0, n_views=1):
+        """The meshes of a batch of views: a list of (xyz float32 (n, 3), faces int32 (m, 3)); xyz is the view's compacted cloud (the
+        valid pixels in scan order), a face three indices into it.  Neighbouring valid pixels are connected unless an edge longer than
+        max_edge (mm; float('inf'): no test) lies between them (include/sl3d.h: the exact definition)."""
+        nv, nf = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_get_meshes(self._h, first_view, n_views, float(max_edge), None, 0, None, 0, nv, nf), "sl3d_get_meshes")
+        tv, tf = sum(nv), sum(nf)
+        xyz, faces = np.empty((tv, 3), dtype=np.float32), np.empty((tf, 3), dtype=np.int32)
+        self._chk(self.L.sl3d_get_meshes(self._h, first_view, n_views, float(max_edge), xyz.ctypes.data, tv, faces.ctypes.data, tf, nv, nf),
+                  "sl3d_get_meshes")
+        out, vo, fo = [], 0, 0
+        for a, b in zip(nv, nf):
+            out.append((xyz[vo:vo + a], faces[fo:fo + b]))
+            vo, fo = vo + a, fo + b
+        return out
+
+    def mesh(self, max_edge, view=0):
+        """(xyz, faces) of one view (meshes)."""
+        return self.meshes(max_edge, view, 1)[0]
 
     def set_texture(self, bgr, view=0):
         """The colour image save_point_cloud() takes r,g,b from: (H, W, 3) uint8, B,G,R order (cvLoadImage)."""

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.7.0"
+#define SL3D_VERSION_STRING "0.8.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -375,6 +375,36 @@ int sl3d_compact_views(sl3d_ctx *ctx, int first_view, int n_views, const float *
 /* the same with a host copy: the clouds back to back in xyz (at most `capacity` points in all; xyz may be NULL) */
 int sl3d_get_clouds(sl3d_ctx *ctx, int first_view, int n_views, float *xyz, int64_t capacity, int64_t *counts);
 
+/* ---- the mesh of a view: ordered faces over the compacted cloud (0.8.0) ------------------------------------------
+ * The dense result of a view is an organized grid, one point per camera pixel; the mesh connects neighbouring valid pixels
+ * unless an edge longer than max_edge (mm, > 0, +inf allowed) lies between them.  The reference has no such stage (its user
+ * meshed the PLY of stage 8 by hand); the definition is this library's own and exact:
+ *   vertices  the compacted cloud of sl3d_get_cloud: the valid pixels in row-major scan order, id = position in that cloud
+ *   len2(p,q) (dx*dx + dy*dy) + dz*dz of the float coordinates widened to double; an edge is short iff len2 <= max_edge^2
+ *             (in double; NaN is not short)
+ *   cells     r in [0, height-1), c in [0, width-1): corners a = (r,c), b = (r,c+1), d = (r+1,c), e = (r+1,c+1).
+ *             4 valid corners: diagonal a-e iff len2(a,e) <= len2(b,d), candidates (a,d,e) then (a,e,b); else b-d, candidates
+ *             (a,d,b) then (b,d,e).  3 valid corners: e missing (a,d,b); a missing (b,d,e); b missing (a,d,e); d missing (a,e,b).
+ *   faces     the candidates whose three edges are short, cell by cell in row-major order, a cell's faces in the order above;
+ *             three int32 vertex ids each, at most 2*(width-1)*(height-1) per view.  One orientation throughout.
+ * Deterministic: the result does not depend on the batch a view is meshed in or on the run.
+ * Works wherever sl3d_compact_views works (every context with a dense result: timed, parity, windows); ids are relative to the
+ * view's own cloud; points, valid and whatever sl3d_compact* / sl3d_run_clouds handed out are not modified.
+ * Not covered: groups (sl3d_group_*: the cells across a stripe seam need the neighbour's row), a mesh straight from the segments of
+ * sl3d_run_clouds, registration of meshes, vertex normals, the drop-in shim (the reference has nothing to mirror). */
+typedef struct sl3d_mesh {            /* device-resident, valid until the next sl3d_mesh_views / sl3d_get_meshes on this context */
+    const float *xyz;                 /* view first_view+k: n_vertices[k] points  at xyz   + 3*k*view_stride_points */
+    const int32_t *faces;             /* view first_view+k: n_faces[k] id triples at faces + 3*k*view_stride_faces  */
+    size_t view_stride_points, view_stride_faces;
+} sl3d_mesh;
+/* meshes views [first_view, first_view+n_views) on the device (six launches, one read-back of the counts); device_mesh may be NULL.
+ * A NaN or non-positive max_edge, a bad view range or NULL counts: SL3D_E_INVALID_ARG, and nothing on the device changes. */
+int sl3d_mesh_views(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, sl3d_mesh *device_mesh, int64_t *n_vertices, int64_t *n_faces);
+/* the same with a host copy: the clouds back to back in xyz (at most vertex_capacity points in all), then the faces back to back
+ * in faces (at most face_capacity triples in all); xyz / faces may be NULL; the per-view counts are always returned */
+int sl3d_get_meshes(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, float *xyz, int64_t vertex_capacity, int32_t *faces,
+                    int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces);
+
 /* register_point_clouds(unsigned, float tx, float ty, float tz, float rot_step)  9/register_point_clouds.cpp:23:
  * the compacted clouds of views [first_view, first_view+n_views) are rotated about the Y axis through (tx,ty,tz)
  * by 0, rot_step, 2*rot_step ... degrees and concatenated in view order; writes at most `capacity` points to xyz
@@ -437,7 +467,7 @@ int sl3d_transform_cloud(sl3d_ctx *ctx, const float *xyz_in, int64_t n, float th
  * 3 pixels of the frame border (a second plane the kernels read for those quads). */
 int sl3d_get_device_buffers(sl3d_ctx *ctx, sl3d_device_buffers *out);
 /* Copy `bytes` from a device address this library handed out (sl3d_get_cloud_counts, sl3d_compact, sl3d_compact_views,
- * sl3d_get_device_buffers) to host memory, ordered after the context's work; synchronises. */
+ * sl3d_mesh_views, sl3d_get_device_buffers) to host memory, ordered after the context's work; synchronises. */
 int sl3d_download(sl3d_ctx *ctx, void *host_dst, const void *device_src, size_t bytes);
 /* the same for a pitched region (`height` rows of `width_bytes`), ENQUEUED on the context's stream: asynchronous for pinned host
  * memory (the caller waits with sl3d_synchronize), so many regions can be queued behind one wait */

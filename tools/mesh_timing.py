@@ -1,0 +1,91 @@
+"""sl3d_mesh_views at the BASELINE frame sizes: 1 and 16 views of 1920x1080, 3 views of 4096x3000; the default mask and the 19 % lasso;
+max_edge = +inf and a value at the median of the candidates' edge lengths.  After warm-up, the host clock around REPS back-to-back calls
+(every call ends in its own synchronise), per view; beside it the bytes the design moves (from the shapes and the returned counts), bytes
+over time against the 6.3 TB/s achievable and the 8 TB/s peak, and -- for scale -- sl3d_compact_views on the same views (same reads,
+vertices only).  One JSON line.  Under `rocprofv3 --kernel-trace --stats` (a run of its own) the kernel table gives the per-kernel split.
+usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3]"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+
+try:
+    import torch  # noqa: F401  (its ROCm stack first, as tests/conftest.py)
+except Exception:
+    pass
+from mesh_reference import np_mesh  # the NumPy restatement of the definition: the source of the median edge length
+
+ACHIEVABLE_TBS, PEAK_TBS = 6.3, 8.0
+CONFIGS = {"1080p_1": (1920, 1080, 1920, 1080, 1), "1080p_16": (1920, 1080, 1920, 1080, 16), "12mp_3": (4096, 3000, 2048, 2048, 3)}
+N, FW = 10, 2
+
+
+def lasso(W, H, share=358580.0 / 1920000.0):
+    mh, mw = int(round(H * share ** 0.5)), int(round(W * share ** 0.5))
+    m = np.zeros((H, W), np.uint8)
+    m[(H - mh) // 2:(H - mh) // 2 + mh, (W - mw) // 2:(W - mw) // 2 + mw] = 1
+    return m
+
+
+def clock(fn, reps):
+    for _ in range(20):
+        fn()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--only", default="")
+    a = ap.parse_args()
+    syn = importlib.import_module("3dscan_amd.synth")
+    scm = importlib.import_module("3dscan_amd.scanner")
+    out = {"tool": "mesh_timing", "reps": a.reps, "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
+           "bytes_note": "design = valid 4x (compaction count + scatter, mesh count + emit; the second row of a block counted as an L2 hit) + "
+                         "points 12 B per vertex 3x (scatter, count, emit) + 12 B per vertex and per face written; algorithmic = 13 B/px read once "
+                         "+ 12 B per vertex and per face written", "runs": []}
+    for name, (W, H, PW, PH, V) in CONFIGS.items():
+        if a.only and a.only != name:
+            continue
+        with scm.Scanner(W, H, PW, PH, N, N, FW, FW, max_views=V) as sc:
+            sc.set_calibration(*syn.cal_tuple(syn.synth_rig(W, H, PW, PH)))
+            for sel, mask in (("default", syn.default_mask(W, H)), ("lasso_19pct", lasso(W, H))):
+                for v in range(V):
+                    sc.set_mask(mask, view=v)
+                    sc.synth_view(v, plane=(0.75 * (v % 16), 0.05, 0.05 - 0.003 * (v % 16)), view_id=v, noise=2)
+                sc.run(0, V)
+                sc.synchronize()
+                xyz, valid = sc.points(0)
+                r0 = H // 2 - 100
+                st = {}
+                np_mesh(np.ascontiguousarray(xyz[r0:r0 + 200]), np.ascontiguousarray(valid[r0:r0 + 200]), float("inf"), st)
+                med = float(np.float32(np.sqrt(np.median(st["len2"]))))
+                t_compact = clock(lambda: sc.compact_views(0, V), a.reps)
+                for label, max_edge in (("inf", float("inf")), ("median", med)):
+                    _, nv, nf = sc.mesh_device(max_edge, 0, V)
+                    t = clock(lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                    design = 4 * W * H * V + 48 * sum(nv) + 12 * sum(nf)
+                    algorithmic = 13 * W * H * V + 12 * sum(nv) + 12 * sum(nf)
+                    out["runs"].append({
+                        "config": name, "size": [W, H], "views": V, "selection": sel, "max_edge": label, "max_edge_mm": None if label == "inf" else round(med, 6),
+                        "vertices_per_view": round(sum(nv) / V), "faces_per_view": round(sum(nf) / V),
+                        "mesh_us_per_call": round(t * 1e6, 1), "mesh_us_per_view": round(t * 1e6 / V, 2),
+                        "compact_views_us_per_call": round(t_compact * 1e6, 1), "mesh_over_compact": round(t / t_compact, 2),
+                        "design_bytes_per_view": design // V, "algorithmic_bytes_per_view": algorithmic // V,
+                        "design_tbs": round(design / t / 1e12, 3), "design_over_achievable": round(design / t / 1e12 / ACHIEVABLE_TBS, 3),
+                        "design_over_peak": round(design / t / 1e12 / PEAK_TBS, 3)})
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
