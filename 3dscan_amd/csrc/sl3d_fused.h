@@ -24,7 +24,7 @@
 #include "sl3d_device.h"
 #include "sl3d_maskbits.h"
 
-#define SL3D_OCC 4     /* waves per SIMD the fused kernel is compiled for (128 VGPRs; SL3D_BLOCK / SL3D_SMALL_BLOCK: sl3d_internal.h) */
+#define SL3D_OCC 4     /* waves per SIMD the fused kernel is compiled for (128 VGPRs; SL3D_BLOCK / SL3D_SMALL_BLOCK: sl3d_fused_choice.h) */
 
 // measurement only (tools/ab.sh builds with -DSL3D_MEASURE -DSL3D_ABLATE=n): 2 = no mask reads, 4 = no xyz stores.  Results are wrong
 // by construction; the shipped build has neither the compile-time switch nor the run-time hooks (SL3D_VPT / SL3D_CAMTAB
@@ -41,7 +41,7 @@
 #define SL3D_STAMP(k)                                                                                                               \
     do {                                                                                                                            \
         /* every lane of the wave stores the same (scalar) clock to the same word: no divergent branch in the instrumented code */   \
-        if ((CMODE & 2) == 0 && !KEEP && P.dbg)                                                                                           \
+        if (!SEG && !KEEP && P.dbg)                                                                                                       \
             P.dbg[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 8 + (k)] = wall_clock64();              \
     } while (0)
 #else
@@ -67,6 +67,18 @@ namespace sl3d {
 //      calibrations are): the undistorted point is pixel + (pixel - principal point) * s(r0^2), s from a 4-KB table of node
 //      quadratics over r0^2 (RadEntry, k_radial_table) that every block copies into LDS -- no global gather in stage 7, so it runs
 //      under the next view's plane loads like rig 1 (rig 2's four gathers sit BEHIND those loads in the in-order vmcnt queue)
+
+// The template arguments of k_fused as one type: the key (sl3d_fused_choice.h: the arguments as values) and what it implies
+// (fused_traits: every derived switch, stated once).  The kernel builds it from its arguments and reads its switches from `is`.
+// (The helpers below keep the switches they need as template arguments of their own, fed from it.  Taking this type instead was built:
+// a helper then exists once per kernel instead of once per combination of its switches, and although every one is inlined, 14 kernels
+// of the dense rig-0 unit and 41 of the general / clouds units came out with other schedules -- profiles/r07_isa_identity_refactor.txt.)
+template <bool KEEP, int NMAX, bool FGEN, bool EXACT, int RIG, int CMODE, bool RCPT, bool EARLY>
+struct FusedKernel {
+    static constexpr FusedKey key = {KEEP, NMAX, FGEN, EXACT, RIG, CMODE, RCPT, EARLY};
+    static constexpr FusedTraits is = fused_traits(key);
+    static_assert(is.legal, "not a combination k_fused compiles (sl3d_fused_choice.h: fused_traits)");
+};
 
 // ---- parity mode: one pixel, everything after the byte loads (stage 4 unwrap, stage 5, stage 7, stage 8 cast), every
 // stage-boundary value stored where the reference keeps it.  (cu,cv) = undistorted camera pixel coordinates of this pixel
@@ -202,7 +214,7 @@ struct Item {
 // instantiation can put its plane requests in between.
 // KIND2 = false (the MASKIN instantiations): the two-double kind is not compiled in -- its 16 registers between request and use are
 // what the launch's mask words live in; a calibration with tangential camera terms keeps the two-kernel route (sl3d_fused_choice.h: fused_key).
-template <bool KIND2 = true>
+template <bool KIND2>
 __device__ __forceinline__ void cam_table_request(const KParams &P, const Item &it, double (&t)[8])
 {
     const size_t i0 = (size_t)it.row * P.pitch + (size_t)it.cq * 4;
@@ -220,7 +232,7 @@ __device__ __forceinline__ void cam_table_request(const KParams &P, const Item &
 // table entries -> the camera coordinates stage 7 uses (normalised for the camera-frame rigs, re-projected pixels for RIG 0), kept
 // in LDS so that the rolled pixel loops can index them (each lane reads back only what it wrote: no barrier).  The doubles are the
 // ones the in-kernel iteration produces.
-template <int RIG, bool KIND2 = true>
+template <int RIG, bool KIND2>
 __device__ __forceinline__ void cam_table_finish(const KParams &P, const DevCal *Cglobal, const Item &it, const double (&t)[8], double *my_cam)
 {
     const auto &I = opaque_const(Cglobal)->cam;
@@ -341,13 +353,24 @@ __device__ __forceinline__ unsigned mrow_own(const MaskInLane &m, mrow_t w) { re
 __device__ __forceinline__ unsigned mrow_left(const MaskInLane &m, mrow_t w) { return mb_quad_left(w.x, w.y, m.delta); }
 __device__ __forceinline__ unsigned mrow_right(const MaskInLane &m, mrow_t w) { return mb_quad_right(w.x, w.y, m.delta); }
 
+// The MASKIN state of a lane between maskin_request and maskin_finish: the 8 selection bytes around its quad of rows y-2 .. y+2 (w0 .. w4)
+struct MaskInRows {
+    bool fast = false;  // maskin_request's verdict on the wave (set by item_begin, wave-uniform): maskin_finish evaluates the short form
+    // (the rows are declared last one first on purpose: the optimiser splits the struct into its members back to front, and the order in
+    // which the rows become values decides how the boolean algebra of mb_quad_valid is associated -- declared w0 .. w4, every MASKIN
+    // kernel has two VALU instructions more; so has one whose maskin_request / maskin_finish use the members where they need them
+    // instead of unpacking them first.  In this form the instruction stream is the one five loose variables give)
+    mrow_t w4 = {0u, 0u}, w3 = {0u, 0u}, w2 = {0u, 0u}, w1 = {0u, 0u}, w0 = {0u, 0u};
+};
+
 // The selection bytes the lane needs of view slot `slot` of the launch: rows y-1, y, y+1 in w1..w3; row y-2 (w0) and row y+2 (w4)
 // only where they matter -- the window's first / last row (halo duties), frame row 2 and the frame's first / last column (mb_quad_top_needed).
 // Everything is asked for HERE, in front of the planes: a load behind them would have to wait for all 46.  Returns true (wave-uniform) if
 // every lane of the wave is plain and without halo duties: such a wave asked without a predicate (every byte is a source pixel) and
 // evaluates the short form (maskin_finish).
-__device__ __forceinline__ bool maskin_request(const KParams &P, const Item &it, int slot, mrow_t &w0, mrow_t &w1, mrow_t &w2, mrow_t &w3, mrow_t &w4)
+__device__ __forceinline__ bool maskin_request(const KParams &P, const Item &it, int slot, MaskInRows &r)
 {
+    mrow_t &w0 = r.w0, &w1 = r.w1, &w2 = r.w2, &w3 = r.w3, &w4 = r.w4;  // (unpacked HERE, and in maskin_finish: see MaskInRows)
     const MaskInArgs A = maskin_read_args(slot);
     {
         const MaskInLane m = maskin_lane<false>(P, A, it);
@@ -391,8 +414,10 @@ __device__ __forceinline__ void maskin_emit(const KParams &P, uint8_t *mask_view
 // The same form on 64-bit lane masks -- 4 ballots per row, the recurrences on the scalar unit -- was built too, bit-identical and 1.4 us
 // SLOWER: all 16 waves of a CU run this prologue at the same time and share ONE scalar unit for ~140 dependent instructions each,
 // where the vector form spreads over four SIMDs; profiles/r06_fused_mask_ab.txt.)
-__device__ __forceinline__ unsigned maskin_finish(const KParams &P, const Item &it, int view, int slot, mrow_t w0, mrow_t w1, mrow_t w2, mrow_t w3, mrow_t w4, bool fast)
+__device__ __forceinline__ unsigned maskin_finish(const KParams &P, const Item &it, int view, int slot, const MaskInRows &r)
 {
+    const mrow_t w0 = r.w0, w1 = r.w1, w2 = r.w2, w3 = r.w3, w4 = r.w4;
+    const bool fast = r.fast;
     if (fast) {
         // ... and most plain waves need no arithmetic at all: a wave whose 3 x 8 bytes are ALL 1 lies inside the selection (every pixel
         // valid), one whose bytes are all 0 outside it (none is) -- 14 instructions instead of ~70; only the waves the selection's
@@ -440,13 +465,13 @@ __device__ __forceinline__ void maskin_count(const KParams &P, const Item &it, i
 }
 
 // Everything of an item that depends on the pixel only; false if this lane has nothing to do.
-// EARLY (the small-launch instantiation): the camera-table entries are only REQUESTED here (camt); the caller issues the first
-// view's plane loads right behind them and then calls cam_table_finish -- one round trip instead of two in front of the first
+// PIPE (the pipelined kernels): the camera-table entries are only REQUESTED here (camt); the caller issues the first view's plane
+// loads right behind them (EARLY) and then calls cam_table_finish -- one round trip instead of two in front of the first
 // decode.  (Round 3 measured the other order for large launches -- set-up loads before the reciprocal-table fill, consumed behind
 // the plane loads: 16 views +-0, profiles/r03_prologue_ab.txt.)
-template <int RIG, bool SEG, bool EARLY, int BLK = SL3D_BLOCK, bool MASKIN = false>
+template <int RIG, bool SEG, bool PIPE, int BLK, bool MASKIN>
 __device__ __forceinline__ bool item_begin(const KParams &P, const DevCal *Cglobal, unsigned tile_, int group, int first_view, int n_views, int vpt, Item &it,
-                                           MaskQuad &mq_first, double (&camt)[8], double *my_cam, mrow_t &w0, mrow_t &w1, mrow_t &w2, mrow_t &w3, mrow_t &w4, bool &mfast)
+                                           MaskQuad &mq_first, double (&camt)[8], double *my_cam, MaskInRows &mrows)
 {
     const unsigned qpr = (unsigned)P.pitch >> 2;  // quads per row, pitch padding included
     it.tile = tile_;
@@ -459,11 +484,11 @@ __device__ __forceinline__ bool item_begin(const KParams &P, const DevCal *Cglob
     it.cq = (int)(q - (unsigned)row_q * qpr);
     // SEG: a wave stores its segment with all 64 lanes (whole 16-byte chunks, lane after lane), so the lanes past the last row
     // stay, without a valid pixel; only the blocks the grid was padded with leave (they own no segment)
-    // EARLY keeps them too, until the block's barrier (their requests go to the last row: one code path, one wait count)
+    // a pipelined kernel keeps them too, until the block's barrier (their requests go to the last row: one code path, one wait count)
     if (SEG && tile_ >= (unsigned)P.n_tiles) return false;
-    if (!SEG && !EARLY && row_q >= P.H) return false;
+    if (!SEG && !PIPE && row_q >= P.H) return false;
     it.alive = row_q < P.H;
-    it.row = (SEG || EARLY) ? min(row_q, P.H - 1) : row_q;
+    it.row = (SEG || PIPE) ? min(row_q, P.H - 1) : row_q;
     it.gx0 = P.col0 + it.cq * 4;
     it.gy = P.row0 + it.row;
     it.lane_off = (unsigned)it.row * (unsigned)P.pitch + (unsigned)it.cq * 4u;
@@ -473,12 +498,12 @@ __device__ __forceinline__ bool item_begin(const KParams &P, const DevCal *Cglob
     if (MASKIN) {
         mq_first.band = 0u;
         bool f = false;
-        if (it.alive) f = maskin_request(P, it, min(it.v_begin, first_view + n_views - 1) - first_view, w0, w1, w2, w3, w4);
-        mfast = __ballot(f) != 0ull;  // (wave-uniform by construction: a wave with a lane past the last row is never fast)
+        if (it.alive) f = maskin_request(P, it, min(it.v_begin, first_view + n_views - 1) - first_view, mrows);
+        mrows.fast = __ballot(f) != 0ull;  // (wave-uniform by construction: a wave with a lane past the last row is never fast)
     } else {
         mq_first = load_mask_quad(P, min(it.v_begin, first_view + n_views - 1), it.lane_off);
     }
-    if (EARLY && P.use_cam_table) {
+    if (PIPE && P.use_cam_table) {
         cam_table_request<!MASKIN>(P, it, camt);
         return true;
     }
@@ -600,13 +625,22 @@ __device__ __forceinline__ void issue_gray(const KParams &P, int view, unsigned 
     }
 }
 
+// all planes of a view, requested back to back
+template <bool FGEN, int NMAX, int PLANES>
+__device__ __forceinline__ void request_planes(const KParams &P, int view, unsigned lane_off, int F, int Nv, int Nh, unsigned (&f)[2][4],
+                                               unsigned (&g)[2][NMAX], unsigned (&iv)[2][NMAX])
+{
+    issue_fringe<FGEN>(P, view, lane_off, F, Nv, f);
+    issue_gray<NMAX, PLANES>(P, view, lane_off, F, Nv, Nh, g, iv);
+}
+
 // ---- S4b: Gray decode, byte-parallel over the 4 pixels of the lane ---------------------------------------------------------------
 // G_i = (gray - inverse >= 0) (4/phase_unwrap.cpp:183) for 4 bytes at once: the low 7 bits are compared by a
 // borrow-protected subtraction, bit 7 decides unless the top bits are equal (one v_bitop3 on x, y, t).
 // B_0 = G_0, B_i = B_{i-1} xor G_i (:187-191) is a running xor of the masks; the code sum B_i 2^(N-1-i) (:193) is
 // accumulated per byte, the LAST 8 planes in `lo`, the ones before them in `hi`, so that the 16-bit code of a pixel
 // is (hi byte, lo byte) and one v_perm per pixel pair builds it: code[a][j] = codes of pixels 2j (low half), 2j+1.
-// PLANES == 2 (padded, see issue_gray): NMAX positions; the NMAX - N padded planes in front are xored in with a zero mask (a scalar
+// PLANES >= 2 (padded, see issue_gray): NMAX positions; the NMAX - N padded planes in front are xored in with a zero mask (a scalar
 // select feeds the third operand of the v_bitop3 that the plain decode feeds with the constant).
 template <int NMAX, int PLANES>
 __device__ __forceinline__ void decode_gray(const unsigned (&g)[2][NMAX], const unsigned (&iv)[2][NMAX], int Nv, int Nh, unsigned (&code)[2][2])
@@ -617,32 +651,22 @@ __device__ __forceinline__ void decode_gray(const unsigned (&g)[2][NMAX], const 
         const unsigned H = 0x80808080u;
         unsigned bacc = 0;  // running binary bit of pixel k at bit 8k+7
         unsigned hi = 0, lo = 0;
+        int pad = 0;
         if (PLANES >= 2) {
-            int pad = NMAX - N;
+            pad = NMAX - N;
             if (PLANES == 3) pad = __builtin_amdgcn_readfirstlane(pad);
             asm volatile("" : "+s"(pad));
-#pragma unroll
-            for (int i = 0; i < NMAX; i++) {
-                const unsigned x = g[a][i], y = iv[a][i];
-                const unsigned t = (x | H) - (y & ~H);
-                const unsigned ge = __builtin_amdgcn_bitop3_b32(x, y, t, 0xB2);
-                const unsigned Hm = i >= pad ? H : 0u;  // (wave-uniform: an SGPR operand)
-                bacc = __builtin_amdgcn_bitop3_b32(bacc, ge, Hm, 0x78);
-                if (i < NMAX - 8) hi = (hi << 1) | (bacc >> 7);
-                else lo = (lo << 1) | (bacc >> 7);
-            }
-            code[a][0] = __builtin_amdgcn_perm(hi, lo, 0x05010400u);
-            code[a][1] = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
-            continue;
         }
+        const int n = PLANES >= 2 ? NMAX : N;  // positions that hold a plane
 #pragma unroll
         for (int i = 0; i < NMAX; i++) {
-            if (i < N) {
+            if (i < n) {
                 const unsigned x = g[a][i], y = iv[a][i];
                 const unsigned t = (x | H) - (y & ~H);                           // bit 8k+7: (x & 0x7f) >= (y & 0x7f)
                 const unsigned ge = __builtin_amdgcn_bitop3_b32(x, y, t, 0xB2);  // (x & ~y) | (~(x ^ y) & t): byte x >= byte y
-                bacc = __builtin_amdgcn_bitop3_b32(bacc, ge, H, 0x78);           // bacc ^ (ge & H)
-                if (i < N - 8) hi = (hi << 1) | (bacc >> 7);
+                const unsigned Hm = (PLANES < 2 || i >= pad) ? H : 0u;           // (wave-uniform: an SGPR operand)
+                bacc = __builtin_amdgcn_bitop3_b32(bacc, ge, Hm, 0x78);          // bacc ^ (ge & Hm)
+                if (i < n - 8) hi = (hi << 1) | (bacc >> 7);
                 else lo = (lo << 1) | (bacc >> 7);
             }
         }
@@ -650,6 +674,15 @@ __device__ __forceinline__ void decode_gray(const unsigned (&g)[2][NMAX], const 
         code[a][1] = __builtin_amdgcn_perm(hi, lo, 0x07030602u);  // bytes (lo2, hi2, lo3, hi3)
     }
 }
+
+// ---- sub-dword unpacking: pixel k of the lane (0..3) has byte k of every fringe dword of an axis (sh = 8 * k: where that byte begins)
+// -> its wrapped phase (stage 3), and half-word k of the axis' two code words (decode_gray) -> its Gray code
+template <bool RCP_TAB>
+__device__ __forceinline__ float wrapped_px(int F, const unsigned (&fa)[4], int sh, const double *s_rcp, const AtanK &AK)
+{
+    return wrapped_phase<RCP_TAB>(F, (fa[0] >> sh) & 255, (fa[1] >> sh) & 255, (fa[2] >> sh) & 255, (fa[3] >> sh) & 255, s_rcp, AK);
+}
+__device__ __forceinline__ int code_px(const unsigned (&ca)[2], int k) { return (int)((ca[k >> 1] >> (16 * (k & 1))) & 0xffffu); }
 
 // ---- phase A: stages 3..5 of the lane's 4 pixels ---------------------------------------------------------------------------------
 // The correspondences are parked in the LDS staging area (slots 3k, 3k+1 of pixel k, which its own result overwrites later).
@@ -663,11 +696,9 @@ __device__ __forceinline__ unsigned pixel_A(const KParams &P, const Item &it, in
                                             const unsigned (&code)[2][2], const double *s_rcp, int *pair_cp)
 {
     const int sh = 8 * i;
-    const int code_v = (int)((code[0][0] >> (16 * i)) & 0xffffu);
-    const int code_h = (int)((code[1][0] >> (16 * i)) & 0xffffu);
+    const int code_v = code_px(code[0], i), code_h = code_px(code[1], i);
     const AtanK AK = atan_consts<true>();
-    float wv = wrapped_phase<RCP_TAB>(F, (f[0][0] >> sh) & 255, (f[0][1] >> sh) & 255, (f[0][2] >> sh) & 255, (f[0][3] >> sh) & 255, s_rcp, AK);
-    float wh = wrapped_phase<RCP_TAB>(F, (f[1][0] >> sh) & 255, (f[1][1] >> sh) & 255, (f[1][2] >> sh) & 255, (f[1][3] >> sh) & 255, s_rcp, AK);
+    float wv = wrapped_px<RCP_TAB>(F, f[0], sh, s_rcp, AK), wh = wrapped_px<RCP_TAB>(F, f[1], sh, s_rcp, AK);
     // stage 4 shifts by +Pi only inside its loop range (4/phase_unwrap.cpp:285,290,304,308); outside it the unwrapped value is 0
     // whatever the wrapped one is (correspond_px), and the timed mode does not keep wrapped
     wv = shift_pi(wv);
@@ -728,10 +759,8 @@ __device__ __forceinline__ void wrapped_quad(int F, const unsigned (&f)[2][4], c
     const AtanK AK = atan_consts<true>();
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int sh = 8 * k;
 #pragma unroll
-        for (int a = 0; a < 2; a++)
-            w[a][k] = shift_pi(wrapped_phase<RCP_TAB>(F, (f[a][0] >> sh) & 255, (f[a][1] >> sh) & 255, (f[a][2] >> sh) & 255, (f[a][3] >> sh) & 255, s_rcp, AK));
+        for (int a = 0; a < 2; a++) w[a][k] = shift_pi(wrapped_px<RCP_TAB>(F, f[a], 8 * k, s_rcp, AK));
     }
 }
 
@@ -741,10 +770,8 @@ __device__ __forceinline__ unsigned correspond_quad(const KParams &P, const Item
     unsigned vout = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int code_v = (int)((code[0][k >> 1] >> (16 * (k & 1))) & 0xffffu);
-        const int code_h = (int)((code[1][k >> 1] >> (16 * (k & 1))) & 0xffffu);
         int cx, cy;
-        const bool ok = correspond_px(P, it.gx0 + k, it.gy, w[0][k], w[1][k], code_v, code_h, cx, cy) && ((vbits >> k) & 1u);
+        const bool ok = correspond_px(P, it.gx0 + k, it.gy, w[0][k], w[1][k], code_px(code[0], k), code_px(code[1], k), cx, cy) && ((vbits >> k) & 1u);
         my_cp[3 * k] = ok ? cx : 0;
         my_cp[3 * k + 1] = ok ? cy : 0;
         vout |= (ok ? 1u : 0u) << (8 * k);
@@ -813,12 +840,10 @@ __device__ __forceinline__ unsigned parity_pixels(const KParams &P, const DevCal
     for (int k = 0; k < 4; k++) {
         if ((vbits >> k) & 1u) {
             const int sh = 8 * k;
-            const int code_v = (int)((code[0][k >> 1] >> (16 * (k & 1))) & 0xffffu);
-            const int code_h = (int)((code[1][k >> 1] >> (16 * (k & 1))) & 0xffffu);
+            const int code_v = code_px(code[0], k), code_h = code_px(code[1], k);
             // stage 3: wrapped phase of both axes; stage 4 shifts it by +Pi inside its loop range
             const AtanK AK = atan_consts<true>();
-            float wv = wrapped_phase<RCP_TAB>(F, (f[0][0] >> sh) & 255, (f[0][1] >> sh) & 255, (f[0][2] >> sh) & 255, (f[0][3] >> sh) & 255, s_rcp, AK);
-            float wh = wrapped_phase<RCP_TAB>(F, (f[1][0] >> sh) & 255, (f[1][1] >> sh) & 255, (f[1][2] >> sh) & 255, (f[1][3] >> sh) & 255, s_rcp, AK);
+            float wv = wrapped_px<RCP_TAB>(F, f[0], sh, s_rcp, AK), wh = wrapped_px<RCP_TAB>(F, f[1], sh, s_rcp, AK);
             wv = shift_pi_if(wv, it.gx0 + k >= 1 && it.gx0 + k <= P.fullW - 2);  // 4/phase_unwrap.cpp:285,290
             wh = shift_pi_if(wh, it.gy >= 1 && it.gy <= P.fullH - 2);            // 4/phase_unwrap.cpp:304,308
             const double cu = my_cam[2 * k], cv = my_cam[2 * k + 1];
@@ -1008,36 +1033,28 @@ struct RadialLds<3> {
 //       (launch_fused) -- a block's prologue is one memory round trip shorter: 16 views +1.4 %, 8 views +1.7 %, clouds +0.8 %
 //       (profiles/r04_early_large_ab.txt); EARLY = false is the large-launch kernel for sparse selections, whose every request
 //       waits for the valid bits.
-template <bool KEEP, int NMAX, bool FGEN, bool EXACT, int RIG, int CMODE, bool RCPT, bool EARLY_>
-__global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) void k_fused(const KParams P, const DevCal *__restrict__ Cglobal, int first_view, int n_views, int vpt)
+template <bool KEEP, int NMAX, bool FGEN, bool EXACT, int RIG, int CMODE, bool RCPT, bool EARLY>
+__global__ __launch_bounds__((FusedKernel<KEEP, NMAX, FGEN, EXACT, RIG, CMODE, RCPT, EARLY>::is.block), SL3D_OCC) void k_fused(const KParams P, const DevCal *__restrict__ Cglobal, int first_view, int n_views, int vpt)
 {
-    constexpr bool SEG = (CMODE & 2) != 0;
-    constexpr bool MASKIN = (CMODE & 4) != 0;
-    constexpr int BLK = RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK;
-    static_assert((CMODE & ~6) == 0, "0 = dense planes, 2 = segmented clouds (1 was round 2's look-back compaction), + 4 = MASKIN");
-    static_assert(!MASKIN || (!KEEP && RIG != 0 && (RCPT ? !EARLY_ : EARLY_)),
-                  "MASKIN: the pipelined small-launch instantiations, and the gated large-launch ones (views known to be sparsely selected)");
-    static_assert(!(KEEP && CMODE != 0), "the parity mode writes dense planes");
-    static_assert(!(KEEP && RIG != 0), "the parity mode evaluates everything with the reference's operation order");
+    // the derived switches (sl3d_fused_choice.h: fused_traits, where the legal combinations are stated too)
+    typedef FusedKernel<KEEP, NMAX, FGEN, EXACT, RIG, CMODE, RCPT, EARLY> K;
+    constexpr bool SEG = K::is.seg, MASKIN = K::is.maskin, PIPE = K::is.pipe, UNROLL = K::is.unroll;
+    constexpr int BLK = K::is.block, PLANES = K::is.planes;
     __shared__ __attribute__((aligned(16))) float s_xyz[BLK * 12];  // staging area: correspondences, then xyz, of the lane's 4 pixels
     __shared__ __attribute__((aligned(16))) double s_cam[BLK * 8];  // undistorted camera coordinates of the lane's 4 pixels
     __shared__ __attribute__((aligned(16))) double s_rcp[RCPT ? SL3D_RCP_TAB : 1];  // 1/d for the atan2 quotient
     RadEntry *const s_rad = RadialLds<RIG>::get();                                  // rig 3: the projector's radial table
     static_assert(RIG != 3 || SL3D_BLOCK == SL3D_RAD_NODES, "one table node per thread");
     SL3D_STAMP(0);
-    constexpr bool PIPE = !KEEP && RIG != 0;  // (see below)
-    static_assert(RCPT || EARLY_ == PIPE, "the small-launch instantiation: early requests iff pipelined");
-    constexpr bool EARLY = EARLY_ && PIPE;
     // rig 3: one of the 8 copies of the table (one per XCD, as consecutive blocks go round the XCDs: all blocks of a launch would
     // otherwise start on the same 32 cache lines of one L2 -- what cost the camera-side radial table 2 us per one-view launch).
-    // REQ_FIRST (every pipelined kernel): the block's LDS tables -- this one, the reciprocal table -- are filled UNDER the item's first
+    // PIPE (every pipelined kernel): the block's LDS tables -- this one, the reciprocal table -- are filled UNDER the item's first
     // memory requests (mask dword, camera-table entries and, with EARLY, the first view's planes): the node is only requested here.
     // The un-pipelined kernels fill them here and now.
-    constexpr bool REQ_FIRST = PIPE;
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // (a node travels as one 16-byte register quad)
     u32x4 rad_node = {0u, 0u, 0u, 0u};
     if (RIG == 3) rad_node = ((const u32x4 *)P.proj_rad)[(blockIdx.x & 7u) * SL3D_RAD_STRIDE + threadIdx.x];
-    if (!REQ_FIRST) {
+    if (!PIPE) {
         if (RIG == 3) ((u32x4 *)s_rad)[threadIdx.x] = rad_node;
         if (RCPT) fill_rcp_table(s_rcp);
         if (RCPT || RIG == 3) __syncthreads();
@@ -1053,16 +1070,14 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
     // EARLY: the first view's planes of an item are requested UNCONDITIONALLY, right behind the item's mask / camera-table requests
     // and before any of those is waited for, at the price of plane loads for quads that turn out to be masked off
     // (profiles/r03_early_planes_ab.txt, r04_early_large_ab.txt)
-    constexpr bool UNROLL = !RCPT;  // the small-launch instantiation: both pixel pairs of phases A and B in one basic block (see phase_A)
 #ifdef SL3D_NO_SPLIT
     constexpr bool SPLIT = false;
 #else
-    constexpr bool SPLIT = EARLY;   // ... and stage 3 ahead of the wait for the Gray planes (wrapped_quad)
+    constexpr bool SPLIT = K::is.split;  // ... and stage 3 ahead of the wait for the Gray planes (wrapped_quad)
 #endif
 
     // EXACT: both axes have exactly NMAX Gray planes (the usual case)
-    // how the axes map onto the NMAX unrolled planes (issue_gray): exact; padded (the timed 3-step kernels up to 12 planes); tests
-    constexpr int PLANES = EXACT ? 1 : (!KEEP && NMAX <= 12) ? ((MASKIN && RCPT) ? 3 : 2) : 0;
+    // (how the axes map onto the NMAX unrolled planes otherwise: PLANES, see issue_gray)
     const int Nv = EXACT ? NMAX : P.Nv, Nh = EXACT ? NMAX : P.Nh;
     const bool proj_table = RIG == 2 || (RIG == 0 && !KEEP && P.proj_disp != nullptr);
 
@@ -1070,22 +1085,20 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
     MaskQuad mq;
     double camt[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // EARLY: the lane's camera-table entries between their request and cam_table_finish
     unsigned mbits = 0u;                         // MASKIN: valid bits (0..3) and own selection bits (4..7) of the quad
-    mrow_t mw0 = {0u, 0u}, mw1 = mw0, mw2 = mw0, mw3 = mw0, mw4 = mw0;  // MASKIN: the selection bytes around the quad (maskin_request)
-    bool mfast = false;                          // MASKIN: the wave evaluates the short form (maskin_request)  // MASKIN: the selection bytes around the quad between their request and maskin_finish
+    MaskInRows mrows;                            // MASKIN: the selection bytes around the quad between their request and maskin_finish
     unsigned f[2][4], g[2][NMAX], iv[2][NMAX], code[2][2];
     // gridDim.x is a multiple of 8 (launch_fused): consecutive tiles go round-robin over the 8 XCDs on purpose (the XCD-banded
     // order was measured at -4 %: DRAM locality across XCDs beats L2 locality for 2 % of shared bytes)
-    // (false: a lane past the last row, or a block the grid was padded with.  REQ_FIRST: block-uniform, only the latter -- a lane past
+    // (false: a lane past the last row, or a block the grid was padded with.  PIPE: block-uniform, only the latter -- a lane past
     // the last row stays until the block's barrier, its requests go to the last row.)
-    if (!item_begin<RIG, SEG, REQ_FIRST, BLK, MASKIN>(P, Cglobal, blockIdx.x, (int)blockIdx.y, first_view, n_views, vpt, it, mq, camt, my_cam, mw0, mw1, mw2, mw3, mw4, mfast)) return;
+    if (!item_begin<RIG, SEG, PIPE, BLK, MASKIN>(P, Cglobal, blockIdx.x, (int)blockIdx.y, first_view, n_views, vpt, it, mq, camt, my_cam, mrows)) return;
     if (MASKIN) it.v_end = it.v_begin + 1;  // (one view per item: launch_fused makes the grid so; a compile-time trip count of the loop below)
-    if (REQ_FIRST) {
+    if (PIPE) {
         // EARLY: planes of the first view right behind the set-up requests.  The block's LDS tables are filled while all of that
         // travels (the radial node requested at the very top is the oldest request: its store waits for nothing else); then the
         // set-up results are consumed
         if (EARLY) {
-            issue_fringe<FGEN>(P, it.v_begin, it.lane_off, F, Nv, f);
-            issue_gray<NMAX, PLANES>(P, it.v_begin, it.lane_off, F, Nv, Nh, g, iv);
+            request_planes<FGEN, NMAX, PLANES>(P, it.v_begin, it.lane_off, F, Nv, Nh, f, g, iv);
         }
         if (RCPT) fill_rcp_table(s_rcp);
         if (RIG == 3) ((u32x4 *)s_rad)[threadIdx.x] = rad_node;
@@ -1093,7 +1106,7 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
         if (!SEG && !it.alive) return;
         // MASKIN: the selection bytes were requested first, so they are here first: evaluated while the planes travel
         if (MASKIN) {
-            if (it.alive) mbits = maskin_finish(P, it, it.v_begin, it.v_begin - first_view, mw0, mw1, mw2, mw3, mw4, mfast);
+            if (it.alive) mbits = maskin_finish(P, it, it.v_begin, it.v_begin - first_view, mrows);
             maskin_count(P, it, it.v_begin, mbits);
         }
         if (P.use_cam_table) cam_table_finish<RIG, !MASKIN>(P, Cglobal, it, camt, my_cam);
@@ -1108,18 +1121,16 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
         vb_next = MASKIN ? (mbits & 0xfu) : valid_bits<KEEP, FGEN, SEG>(it, F, mq);
         if (!MASKIN && it.v_begin + 1 < it.v_end) mq = load_mask_quad(P, it.v_begin + 1, it.lane_off);
         if (!EARLY && vb_next != 0) {  // (EARLY: they are in flight already)
-            issue_fringe<FGEN>(P, it.v_begin, it.lane_off, F, Nv, f);
-            issue_gray<NMAX, PLANES>(P, it.v_begin, it.lane_off, F, Nv, Nh, g, iv);
+            request_planes<FGEN, NMAX, PLANES>(P, it.v_begin, it.lane_off, F, Nv, Nh, f, g, iv);
         }
     }
     const PinnedRows PR = pinned_rows<RIG>(Cglobal);  // (stage 7 needs them; by now the item's first memory requests are on their way)
-    // DEFER: the results of view v leave AFTER the decode of view v + 1 instead of right behind stage 7.  gfx950 has ONE in-order
+    // PIPE also defers the stores: the results of view v leave AFTER the decode of view v + 1 instead of right behind stage 7.  gfx950 has ONE in-order
     // vmcnt for loads and stores: stores issued behind the next view's plane loads are what that view's decode ends up waiting for
     // (its last s_waitcnt vmcnt(0) = planes landed AND those stores acknowledged).  Deferred, they are issued once the planes have
     // been consumed and have a whole view's arithmetic to complete: 4 views per launch +0.7 %, 12 Mpx x 3 views +1 %, 16 views
     // and the table rig +0.3 % (profiles/r04_pipeline_point_ab.txt); the staged results wait in LDS, which phase A of the next view
     // only touches after the store.
-    constexpr bool DEFER = PIPE;
     unsigned pvout = 0;
     auto store_view = [&](int v, unsigned vo) {
         const size_t p = (size_t)v * P.px_view_stride + (size_t)it.lane_off;
@@ -1138,10 +1149,9 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
         const size_t px = (size_t)view * P.px_view_stride + (size_t)it.lane_off;  // first pixel of the quad
         unsigned vout = 0;
         if (KEEP) parity_init(P, px, vbits);
-        if (!DEFER && !SEG && (KEEP || vbits == 0)) fill_nan(my_xyz);
+        if (!PIPE && !SEG && (KEEP || vbits == 0)) fill_nan(my_xyz);
         if (!PIPE && vbits != 0) {  // every load of the view is issued before the first one is consumed
-            issue_fringe<FGEN>(P, view, it.lane_off, F, Nv, f);
-            issue_gray<NMAX, PLANES>(P, view, it.lane_off, F, Nv, Nh, g, iv);
+            request_planes<FGEN, NMAX, PLANES>(P, view, it.lane_off, F, Nv, Nh, f, g, iv);
         }
         if (view == it.v_begin) SL3D_STAMP(3);
         float w[2][4];
@@ -1159,7 +1169,7 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
             vb_pre = MASKIN ? 0u : valid_bits<KEEP, FGEN, SEG>(it, F, mq);
             asm volatile("" : "+v"(vb_pre));  // (here, not sunk to its use)
         }
-        if (DEFER) {
+        if (PIPE) {
             if (view > it.v_begin) store_view(view - 1, pvout);
             if (!SEG && vbits == 0) fill_nan(my_xyz);
         }
@@ -1181,8 +1191,7 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
             // launch +5 %, 16 views +1 %, the table rig +1.5 %, profiles/r04_pipeline_point_ab.txt)
             if (!MASKIN) mq = load_mask_quad(P, min(view + 2, it.v_end - 1), it.lane_off);
             if (vb_next != 0) {
-                issue_fringe<FGEN>(P, view + 1, it.lane_off, F, Nv, f);
-                issue_gray<NMAX, PLANES>(P, view + 1, it.lane_off, F, Nv, Nh, g, iv);
+                request_planes<FGEN, NMAX, PLANES>(P, view + 1, it.lane_off, F, Nv, Nh, f, g, iv);
             }
         }
         if (!KEEP && vbits != 0) {
@@ -1190,7 +1199,7 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
             gather_B(P, proj_table, my_cp, d);
             phase_B<RIG, UNROLL>(P, Cglobal, PR, proj_table, vout, d, my_cam, my_cp, my_xyz, s_rad);
         }
-        if (DEFER) {
+        if (PIPE) {
             if (view == it.v_begin) SL3D_STAMP(6);
             pvout = vout;
             continue;
@@ -1203,7 +1212,7 @@ __global__ __launch_bounds__(RCPT ? SL3D_BLOCK : SL3D_SMALL_BLOCK, SL3D_OCC) voi
         store_quad<KEEP>(P, s_xyz, my_xyz, px, vout);
         if (view == it.v_begin) SL3D_STAMP(7);
     }
-    if (DEFER) {
+    if (PIPE) {
         store_view(it.v_end - 1, pvout);
         SL3D_STAMP(7);  // (trace builds: with deferred stores, the LAST view's)
     }

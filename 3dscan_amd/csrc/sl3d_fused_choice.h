@@ -13,6 +13,8 @@
 
 #define SL3D_MAX_GRAY 16
 #define SL3D_SMALL_LAUNCH_VIEWS 4  // launches of at most this many views take the small-launch instantiation (sl3d_fused.h)
+#define SL3D_BLOCK 256 /* threads per block of the fused kernel: a block is a 1024-pixel tile of the scan, 4 waves = 4 segments of 256 pixels */
+#define SL3D_SMALL_BLOCK SL3D_BLOCK /* the small-launch instantiation keeps 256-thread blocks too (round 4: 128 / 64 threads +-0.5 %) */
 
 namespace sl3d {
 
@@ -28,6 +30,42 @@ constexpr bool operator==(const FusedKey &a, const FusedKey &b)
 {
     return a.keep == b.keep && a.nmax == b.nmax && a.fgen == b.fgen && a.exact == b.exact && a.rig == b.rig && a.cmode == b.cmode && a.rcpt == b.rcpt &&
            a.early == b.early;
+}
+
+// what a key implies: every switch k_fused derives from its template arguments, stated once -- the kernel and its helpers read it
+// (sl3d_fused.h: FusedKernel), launch_fused takes the block size from it, and the CPU check asserts `legal` for every compiled key
+struct FusedTraits {
+    bool seg;     // CMODE bit 2: segmented clouds instead of dense planes
+    bool maskin;  // CMODE bit 4: the launch evaluates the views' raw selection itself
+    bool pipe;    // the timed kernels of the camera-frame rigs: the planes of view v + 1 are requested in the middle of view v, the
+                  // block's LDS tables are filled under the item's first requests, the results of view v leave behind the decode of v + 1
+    bool early;   // the first view's planes of an item are requested before its mask is known
+    bool split;   // ... and stage 3 runs ahead of the wait for the Gray planes
+    bool unroll;  // the small-launch instantiation: both pixel pairs of phases A and B in one basic block
+    int block;    // threads per block
+    int planes;   // how an axis with N Gray planes maps onto the NMAX unrolled ones (sl3d_fused.h: issue_gray)
+    bool legal;   // a combination k_fused compiles
+};
+constexpr FusedTraits fused_traits(const FusedKey &k)
+{
+    FusedTraits t = {};
+    t.seg = (k.cmode & 2) != 0;
+    t.maskin = (k.cmode & 4) != 0;
+    t.pipe = !k.keep && k.rig != 0;
+    t.early = k.early;
+    t.split = k.early;
+    t.unroll = !k.rcpt;
+    t.block = k.rcpt ? SL3D_BLOCK : SL3D_SMALL_BLOCK;
+    // exact; padded (the timed kernels up to 12 planes; 3: the pad count through v_readfirstlane, the gated MASKIN kernels); tests
+    t.planes = k.exact ? 1 : (!k.keep && k.nmax <= 12) ? ((t.maskin && k.rcpt) ? 3 : 2) : 0;
+    t.legal = (k.cmode & ~6) == 0 &&  // 0 = dense planes, 2 = segmented clouds (1 was round 2's look-back compaction), + 4 = MASKIN
+              // MASKIN: the pipelined small-launch instantiations, and the gated large-launch ones (views known to be sparsely selected)
+              (!t.maskin || (t.pipe && (k.rcpt ? !k.early : k.early))) &&
+              !(k.keep && k.cmode != 0) &&  // the parity mode writes dense planes
+              !(k.keep && k.rig != 0) &&    // the parity mode evaluates everything with the reference's operation order
+              // early requests: the pipelined kernels only; the small-launch instantiation: early requests iff pipelined
+              (k.early ? t.pipe : (k.rcpt || !t.pipe));
+    return t;
 }
 
 // what the rule looks at: the launch, and the calibration facts the rig classes need
@@ -53,6 +91,10 @@ constexpr int fused_rig(const FusedShape &s)
     return s.rig == 1 ? 1 : (s.rig == 2 && s.proj_disp) ? 2 : (s.rig == 3 && s.proj_rad && s.F == 3) ? 3 : 0;
 }
 
+// the SIZE of the launch: a handful of views of the reference's own fringes (one scan per call).  Such a launch takes the small-launch
+// instantiation unless its views are sparsely selected (fused_key), and the views-per-lane rule of small launches either way (launch_fused)
+constexpr bool fused_small_launch(const FusedShape &s) { return !s.keep && s.F == 3 && s.n_views <= SL3D_SMALL_LAUNCH_VIEWS; }
+
 // THE rule.  prefer_gated: the views of the launch are sparsely selected -- a small launch then takes the large-launch instantiation,
 // whose plane requests wait for the valid bits instead of going out first (one view of 1080p with 19 % of the frame selected, as in the
 // reference's real captures: 15.8 us against 22.2; a full frame: 26.9 against 24.6 -- profiles/r04_sparse_mask.txt).
@@ -75,7 +117,7 @@ constexpr FusedKey fused_key(const FusedShape &s)
     else if (!s.keep && m <= 12 && s.nv > 0 && s.nh > 0) k.nmax = m < 6 ? 6 : m;  // padded (4-/5-step fringes: always)
     else if (!s.keep) k.nmax = SL3D_MAX_GRAY;  // more than 12 planes, or an axis with NONE (sl3d_config allows 0): the per-plane tests
     else k.nmax = m <= 8 ? 8 : (m <= 12 ? 12 : SL3D_MAX_GRAY);
-    const bool small = !s.keep && !fgen && s.n_views <= SL3D_SMALL_LAUNCH_VIEWS && !s.prefer_gated;
+    const bool small = fused_small_launch(s) && !s.prefer_gated;
     k.rcpt = !small;
     // (early requests: the pipelined kernels only -- rig class 0 is the un-pipelined general kernel)
     k.early = small ? rig != 0 : rig != 0 && !fgen && !s.prefer_gated;

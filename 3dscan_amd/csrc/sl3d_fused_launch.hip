@@ -40,14 +40,20 @@ static int views_per_lane(unsigned bx, int n_views, int cam_table_kind, bool sma
     return vpt;
 }
 
+// what the rule looks at (sl3d_fused_choice.h)
+static FusedShape fused_shape(const KParams &P, int rig, int n_views, bool keep, int cmode, bool prefer_gated, bool maskin)
+{
+    return {keep, P.F, P.Nv, P.Nh, n_views, rig, cmode, prefer_gated, maskin, P.proj_disp != nullptr, P.proj_rad != nullptr,
+            P.cam_tab != nullptr && P.cam_tab_kind == 2};
+}
+
 FusedKey fused_choice(const KParams &P, int rig, int n_views, bool keep, int cmode, bool prefer_gated, bool maskin)
 {
 #ifdef SL3D_MEASURE
     // (every launch takes the large-launch instantiation, as if it had more views)
     if (getenv("SL3D_NO_SMALL") && n_views <= SL3D_SMALL_LAUNCH_VIEWS) n_views = SL3D_SMALL_LAUNCH_VIEWS + 1;
 #endif
-    return fused_key({keep, P.F, P.Nv, P.Nh, n_views, rig, cmode, prefer_gated, maskin, P.proj_disp != nullptr, P.proj_rad != nullptr,
-                      P.cam_tab != nullptr && P.cam_tab_kind == 2});
+    return fused_key(fused_shape(P, rig, n_views, keep, cmode, prefer_gated, maskin));
 }
 
 // the launcher of key k: from its family's table (a family no unit instantiates is a null weak reference: sl3d_internal.h)
@@ -85,8 +91,9 @@ int launch_fused(const KParams &P_, const DevCal *d_cal, int rig, int first_view
     // selections, profiles/r04_sparse_mask.txt, was measured with it; following the kernel instead is 5-12 % slower at 19 % / 5 %
     // coverage with 4 views per launch, 1-4 % faster at 50 %: profiles/r05_sparse_small_launch_vpt_ab.txt)
     // (a MASKIN launch: one view per item -- nothing of a next view is in flight beside the selection bytes)
-    const int vpt = mi ? 1 : views_per_lane(bx, n_views, P.cam_tab != nullptr ? P.cam_tab_kind : 0, !keep && P.F == 3 && n_views <= SL3D_SMALL_LAUNCH_VIEWS);
-    const unsigned block = k.rcpt ? SL3D_BLOCK : SL3D_SMALL_BLOCK;
+    const bool small = fused_small_launch(fused_shape(P, rig, n_views, keep, cmode, prefer_gated, mi != nullptr));
+    const int vpt = mi ? 1 : views_per_lane(bx, n_views, P.cam_tab != nullptr ? P.cam_tab_kind : 0, small);
+    const unsigned block = (unsigned)fused_traits(k).block;
     const unsigned gx = ((unsigned)((quads + block - 1) / block) + 7u) & ~7u;
     // the timed kernels read the camera-side T1 from the per-calibration table whatever the batch is: with 8 views per lane it
     // costs nothing (1 B/px/view), with 1..4 it saves the iteration (+2..13 %), and a view's result does not depend on the

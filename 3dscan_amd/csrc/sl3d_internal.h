@@ -6,15 +6,13 @@
 
 #include <hip/hip_vector_types.h>  // float2
 
-#include "sl3d_fused_choice.h"  // SL3D_MAX_GRAY, SL3D_SMALL_LAUNCH_VIEWS, FusedKey
+#include "sl3d_fused_choice.h"  // SL3D_MAX_GRAY, SL3D_SMALL_LAUNCH_VIEWS, SL3D_BLOCK, SL3D_SMALL_BLOCK, FusedKey
 
 #define SL3D_MASK_HALO 2        // rows / columns of selection mask kept around the window
 #define SL3D_MASK_LPAD 16       // bytes in front of window column 0 in every mask row
 #define SL3D_ATAN_T1 511        // t1 = I0 - I2        in [-255, 255]
 #define SL3D_ATAN_T2 1021       // t2 = 2*I1 - I0 - I2 in [-510, 510]
 #define SL3D_SEG_POINTS 256     // pixels (point slots) per segment of the segmented clouds = one wave of the fused kernel
-#define SL3D_BLOCK 256 /* threads per block of the fused kernel: a block is a 1024-pixel tile of the scan, 4 waves = 4 segments of 256 pixels */
-#define SL3D_SMALL_BLOCK SL3D_BLOCK /* the small-launch instantiation keeps 256-thread blocks too (round 4: 128 / 64 threads +-0.5 %) */
 
 namespace sl3d {
 

@@ -4,7 +4,8 @@
 // sl3d_fused_*.hip units instantiate (fused_family):
 //   * every key the rule returns is compiled;
 //   * every compiled key is reached;
-//   * the families hold 530 keys, each in the family its id names.
+//   * the families hold 530 keys, each in the family its id names;
+//   * every compiled key is a combination k_fused accepts (fused_traits: legal).
 // usage: fused_choice_check [names] -> prints a summary (and with `names`, every compiled key as rocprofv3 spells it); exit code 0 iff
 // no violation
 //        fused_choice_check key -> reads one FusedShape per line from stdin, its twelve fields as integers in declaration order, and
@@ -59,6 +60,7 @@ int main(int argc, char **argv)
         for (int i = 0; i < f.n; i++) {
             if (fused_family_id(f.key[i]) != id) violations++, printf("family %d holds %s\n", id, name(f.key[i]).c_str());
             if (!compiled.insert(name(f.key[i])).second) violations++, printf("family %d repeats %s\n", id, name(f.key[i]).c_str());
+            if (!fused_traits(f.key[i]).legal) violations++, printf("family %d holds %s, which k_fused does not compile\n", id, name(f.key[i]).c_str());
             in_family[code(f.key[i])] = 1;
         }
     }
