@@ -1,6 +1,9 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
+// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces).
 #include "sl3d_capi_internal.h"
+
+typedef sl3d_ctx::Scan Scan;
 
 // ---- compacted clouds straight from the fused kernel ----------------------------------------------------------------
 static int ensure_cloud_buffers(sl3d_ctx *x)
@@ -13,9 +16,9 @@ static int ensure_cloud_buffers(sl3d_ctx *x)
     int rc = SL3D_OK;
     const size_t nb = (P.px_view_stride + 1023) / 1024;
     if (!x->d_clouds) rc = dev_alloc(x, &x->d_clouds, mv * P.px_view_stride * 3);
-    if (!rc && !x->d_blk_cnt_all) rc = dev_alloc(x, &x->d_blk_cnt_all, mv * nb);
-    if (!rc && !x->d_blk_off_all) rc = dev_alloc(x, &x->d_blk_off_all, mv * nb);
-    if (!rc && !x->d_totals) rc = dev_alloc(x, &x->d_totals, mv);
+    if (!rc && !x->blk_all.cnt) rc = dev_alloc(x, &x->blk_all.cnt, mv * nb);
+    if (!rc && !x->blk_all.off) rc = dev_alloc(x, &x->blk_all.off, mv * nb);
+    if (!rc && !x->blk_all.tot) rc = dev_alloc(x, &x->blk_all.tot, mv);
     if (rc) return rc;
     P.n_tiles = fused_tiles(P);
     P.n_segs = 4 * P.n_tiles;
@@ -37,7 +40,7 @@ static int ensure_cloud_buffers(sl3d_ctx *x)
     void *mapped = nullptr;
     HIPCHK(x, hipHostGetDevicePointer(&mapped, x->h_counts, 0));
     P.cloud_totals = (unsigned long long *)mapped;
-    x->scan_state.assign(mv, 0);
+    x->scan_state.assign(mv, Scan::DONE);
     x->clouds_ready = true;
     return SL3D_OK;
 }
@@ -66,10 +69,10 @@ try {
     // kernel boundary behind a 26-us kernel -- between the fused kernel and its consumer; a consumer that wants the offsets as an
     // array (sl3d_get_cloud_segments) gets the scan then.  Large launches scan here, as before: one launch for all views.
     if (n_views <= SL3D_SMALL_LAUNCH_VIEWS) {
-        for (int v = first_view; v < first_view + n_views; v++) x->scan_state[v] = 1;
+        std::fill_n(x->scan_state.begin() + first_view, n_views, Scan::PENDING);
         return SL3D_OK;
     }
-    for (int v = first_view; v < first_view + n_views; v++) x->scan_state[v] = 0;
+    std::fill_n(x->scan_state.begin() + first_view, n_views, Scan::DONE);
     return launched(x, launch_seg_scan(x->P, first_view, n_views, x->stream));
 }
 SL3D_CATCH(x)
@@ -78,9 +81,9 @@ SL3D_CATCH(x)
 static int ensure_scanned(sl3d_ctx *x, int first_view, int n_views)
 {
     for (int v = first_view; v < first_view + n_views;) {
-        if (x->scan_state[v] == 0) { v++; continue; }
+        if (x->scan_state[v] == Scan::DONE) { v++; continue; }
         int e = v;
-        while (e < first_view + n_views && x->scan_state[e] != 0) x->scan_state[e++] = 0;
+        while (e < first_view + n_views && x->scan_state[e] != Scan::DONE) x->scan_state[e++] = Scan::DONE;
         const int rc = launched(x, launch_seg_scan(x->P, v, e - v, x->stream));
         if (rc) return rc;
         v = e;
@@ -94,6 +97,41 @@ static int ensure_packed(sl3d_ctx *x)
     return dev_alloc(x, &x->d_packed, (size_t)x->cfg.max_views * x->P.px_view_stride * 3);
 }
 
+// a scanning consumer (k_seg_close<.., SCAN>) over these views has drained: their totals, and what that leaves of their scan state
+static void read_scanned_totals(sl3d_ctx *x, int first_view, int n_views, int64_t *counts)
+{
+    for (int v = first_view; v < first_view + n_views; v++) {
+        counts[v - first_view] = x->cloud_total(v);
+        if (x->scan_state[v] == Scan::PENDING) x->scan_state[v] = Scan::TOTAL_ONLY;
+    }
+}
+
+// where a kernel may store straight into the caller's host buffer (pinned memory mapped into the device), or NULL: pageable memory, or
+// SL3D_ZEROCOPY=0 in the environment
+static float *mapped_destination(float *xyz)
+{
+    void *mapped = nullptr;
+    const char *zc = getenv("SL3D_ZEROCOPY");
+    if (!(zc && atoi(zc) == 0) && is_pinned_host(xyz) && hipHostGetDevicePointer(&mapped, xyz, 0) == hipSuccess && mapped) return (float *)mapped;
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+// Host copy of per-view device arrays of 12-byte elements (points, faces), `stride` elements apart, back to back: view v's first counts[v]
+// elements, at most `capacity` in all (negative or used up: nothing more is copied; the counts stay the caller's to report in full).
+// host == NULL: nothing.  Enqueued only -- the caller synchronises
+static int download_clamped(sl3d_ctx *x, void *host, const void *dev, size_t stride, int n_views, const int64_t *counts, int64_t capacity)
+{
+    int64_t off = 0;
+    for (int v = 0; v < n_views && host; v++) {
+        const int64_t n = std::min<int64_t>(counts[v], capacity - off);
+        if (n <= 0) continue;
+        HIPCHK_DRAIN(x, hipMemcpyAsync((char *)host + 12 * off, (const char *)dev + 12 * (size_t)v * stride, (size_t)n * 12, hipMemcpyDeviceToHost, x->stream));
+        off += n;
+    }
+    return SL3D_OK;
+}
+
 // counts (and the device address) of the clouds the last sl3d_run_clouds over these views produced; synchronises
 extern "C" int sl3d_get_cloud_counts(sl3d_ctx *x, int first_view, int n_views, const float **device_xyz, size_t *view_stride_points, int64_t *counts)
 try {
@@ -104,39 +142,27 @@ try {
     ON_DEVICE(x);
     bool unscanned = false, no_total = false;
     for (int v = first_view; v < first_view + n_views; v++) {
-        unscanned |= x->scan_state[v] != 0;
-        no_total |= x->scan_state[v] == 1;
+        unscanned |= x->scan_state[v] != Scan::DONE;
+        no_total |= x->scan_state[v] == Scan::PENDING;
     }
-    volatile unsigned long long *t = x->h_counts;
-    if (device_xyz && unscanned) {
-        // the contiguous copy by the gap-closing kernel that scans on entry: it leaves the totals too -- ONE launch, one wait
-        rc = ensure_packed(x);
-        if (rc) return rc;
-        float *dst = x->d_packed + 3 * (size_t)first_view * x->P.px_view_stride;
-        rc = launched(x, launch_seg_close_scan(x->P, first_view, n_views, dst, x->P.px_view_stride, ~0ull, x->stream));
-        if (rc) return rc;
+    // unscanned views whose contiguous copy is wanted: the gap-closing kernel that makes it scans on entry and leaves the totals too --
+    // ONE launch, one wait.  Otherwise the counts first: the scan kernel (or a scanning consumer) stored them into pinned host memory itself
+    const bool scan_on_entry = device_xyz && unscanned;
+    if (!scan_on_entry) {
+        if (no_total && (rc = ensure_scanned(x, first_view, n_views))) return rc;
         SYNC_FOR_CALLER(x);
-        for (int v = 0; v < n_views; v++) {
-            counts[v] = (int64_t)t[first_view + v];
-            if (x->scan_state[first_view + v] == 1) x->scan_state[first_view + v] = 2;
-        }
-        *device_xyz = dst;
-        if (view_stride_points) *view_stride_points = x->P.px_view_stride;
-        return SL3D_OK;
+        for (int v = 0; v < n_views; v++) counts[v] = x->cloud_total(first_view + v);
     }
-    if (no_total && (rc = ensure_scanned(x, first_view, n_views))) return rc;
-    // the scan kernel (or a scanning consumer) stored the counts into pinned host memory itself: wait for it, read them
-    SYNC_FOR_CALLER(x);
-    for (int v = 0; v < n_views; v++) counts[v] = (int64_t)t[first_view + v];
     if (device_xyz) {  // the contiguous copy is made now, by one gap-closing launch over these views
         rc = ensure_packed(x);
         if (rc) return rc;
         float *dst = x->d_packed + 3 * (size_t)first_view * x->P.px_view_stride;
-        rc = launched(x, launch_seg_close(x->P, first_view, n_views, dst, x->P.px_view_stride, x->stream));
+        rc = launched(x, launch_seg_close(x->P, first_view, n_views, SegClose{dst, x->P.px_view_stride, scan_on_entry, ~0ull}, x->stream));
         if (rc) return rc;
         // the copy is handed to consumers on OTHER streams too (a group's communication stream, a caller's RCCL stream):
         // like the counts, it is complete when this call returns
         SYNC_FOR_CALLER(x);
+        if (scan_on_entry) read_scanned_totals(x, first_view, n_views, counts);
         *device_xyz = dst;
     }
     if (view_stride_points) *view_stride_points = x->P.px_view_stride;
@@ -180,22 +206,18 @@ try {
     if (rc) return rc;
     if (!counts) return fail(x, SL3D_E_INVALID_ARG, "null argument");
     if (!x->clouds_ready) return fail(x, SL3D_E_STATE, "sl3d_run_clouds has not been called");
-    if (n_views == 1 && xyz && capacity > 0 && x->scan_state[first_view] != 0) {
+    if (n_views == 1 && xyz && capacity > 0 && x->scan_state[first_view] != Scan::DONE) {
         // ONE unscanned view into pinned host memory -- the reference's own consumer (8/save_point_cloud.cpp:85-104 fills a host cloud
         // per scan): the gap-closing kernel scans on entry, stores straight into the mapped host buffer (clamped to its capacity)
         // and leaves the count -- fused kernel, this kernel, one wait; no scan launch, no wait for the count in between
         ON_DEVICE(x);
-        void *mapped = nullptr;
-        const char *zc = getenv("SL3D_ZEROCOPY");
-        if (!(zc && atoi(zc) == 0) && is_pinned_host(xyz) && hipHostGetDevicePointer(&mapped, xyz, 0) == hipSuccess && mapped) {
-            rc = launched(x, launch_seg_close_scan(x->P, first_view, 1, (float *)mapped, 0, (unsigned long long)capacity, x->stream));
+        if (float *mapped = mapped_destination(xyz)) {
+            rc = launched(x, launch_seg_close(x->P, first_view, 1, SegClose{mapped, 0, true, (unsigned long long)capacity}, x->stream));
             if (rc) return rc;
             SYNC_FOR_CALLER(x);
-            counts[0] = (int64_t)((volatile unsigned long long *)x->h_counts)[first_view];
-            if (x->scan_state[first_view] == 1) x->scan_state[first_view] = 2;
+            read_scanned_totals(x, first_view, 1, counts);
             return SL3D_OK;
         }
-        (void)hipGetLastError();
     }
     rc = sl3d_get_cloud_counts(x, first_view, n_views, nullptr, nullptr, counts);
     if (rc || !xyz) return rc;
@@ -203,18 +225,13 @@ try {
     const KParams &P = x->P;
     int64_t total = 0;
     for (int v = 0; v < n_views; v++) total += counts[v];
-    void *mapped = nullptr;
-    const char *zc = getenv("SL3D_ZEROCOPY");
-    const bool zero_copy = total <= capacity && !(zc && atoi(zc) == 0) && is_pinned_host(xyz) &&
-                           hipHostGetDevicePointer(&mapped, xyz, 0) == hipSuccess && mapped;
-    if (!zero_copy) (void)hipGetLastError();
-    if (zero_copy) {
+    if (float *mapped = total <= capacity ? mapped_destination(xyz) : nullptr) {
         rc = ensure_scanned(x, first_view, n_views);  // (k_seg_close reads the offsets array)
         if (rc) return rc;
         int64_t off = 0;
         for (int v = 0; v < n_views; v++) {
             if (counts[v] > 0) {
-                rc = launched(x, launch_seg_close(P, first_view + v, 1, (float *)mapped + 3 * off, 0, x->stream));
+                rc = launched(x, launch_seg_close(P, first_view + v, 1, SegClose{mapped + 3 * off, 0}, x->stream));
                 if (rc) return rc;
             }
             off += counts[v];
@@ -223,13 +240,7 @@ try {
         const float *dev = nullptr;
         size_t stride = 0;
         rc = sl3d_get_cloud_counts(x, first_view, n_views, &dev, &stride, counts);
-        if (rc) return rc;
-        int64_t off = 0;
-        for (int v = 0; v < n_views && off < capacity; v++) {
-            const int64_t n = std::min<int64_t>(counts[v], capacity - off);
-            if (n > 0) HIPCHK_DRAIN(x, hipMemcpyAsync(xyz + 3 * off, dev + 3 * (size_t)v * stride, (size_t)n * 12, hipMemcpyDeviceToHost, x->stream));
-            off += n;
-        }
+        if (rc || (rc = download_clamped(x, xyz, dev, stride, n_views, counts, capacity))) return rc;
     }
     SYNC_FOR_CALLER(x);
     return SL3D_OK;
@@ -243,11 +254,11 @@ try {
     if (!count) return fail(x, SL3D_E_INVALID_ARG, "null argument");
     ON_DEVICE(x);
     const bool tex = x->d_texture && view < (int)x->have_texture.size() && x->have_texture[view];
-    rc = launched(x, launch_compact(x->P, view, x->d_blk_cnt, x->d_blk_off, x->d_total, x->d_cloud,
-                                    tex ? x->d_texture + (size_t)view * x->P.px_view_stride * 3 : nullptr, x->d_cloud_rgb, x->stream));
+    rc = launched(x, launch_compact_views(x->P, view, 1, x->blk_one, x->d_cloud, tex ? x->d_texture + (size_t)view * x->P.px_view_stride * 3 : nullptr,
+                                          x->d_cloud_rgb, x->stream));
     if (rc) return rc;
     unsigned long long n = 0;
-    HIPCHK(x, hipMemcpyAsync(&n, x->d_total, sizeof n, hipMemcpyDeviceToHost, x->stream));
+    HIPCHK(x, hipMemcpyAsync(&n, x->blk_one.tot + view, sizeof n, hipMemcpyDeviceToHost, x->stream));
     SYNC_FOR_CALLER(x);
     *count = (int64_t)n;
     if (device_xyz) *device_xyz = x->d_cloud;
@@ -255,20 +266,27 @@ try {
 }
 SL3D_CATCH(x)
 
-extern "C" int sl3d_get_cloud(sl3d_ctx *x, int view, float *xyz, int64_t capacity, int64_t *count)
-try {
-    if (!x || !count) return fail(x, SL3D_E_INVALID_ARG, "null argument");
+// sl3d_get_cloud / sl3d_get_cloud_rgb behind their argument checks: the row-major scan over the valid pixels only (8/save_point_cloud.cpp:
+// 85-104), compacted on the device; at most `capacity` points (and their r,g,b) reach the host
+static int get_compacted(sl3d_ctx *x, int view, float *xyz, uint8_t *rgb, int64_t capacity, int64_t *count)
+{
     ON_DEVICE(x);
-    // row-major scan, valid pixels only (8/save_point_cloud.cpp:85-104), compacted on the device
     const float *dev = nullptr;
     int rc = sl3d_compact(x, view, &dev, count);
     if (rc) return rc;
     const int64_t n = *count < capacity ? *count : capacity;
-    if (xyz && n > 0) {
-        HIPCHK(x, hipMemcpyAsync(xyz, dev, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+    if (n > 0 && (xyz || rgb)) {
+        if (xyz) HIPCHK(x, hipMemcpyAsync(xyz, dev, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+        if (rgb) HIPCHK_DRAIN(x, hipMemcpyAsync(rgb, x->d_cloud_rgb, (size_t)n * 3, hipMemcpyDeviceToHost, x->stream));
         SYNC_FOR_CALLER(x);
     }
     return SL3D_OK;
+}
+
+extern "C" int sl3d_get_cloud(sl3d_ctx *x, int view, float *xyz, int64_t capacity, int64_t *count)
+try {
+    if (!x || !count) return fail(x, SL3D_E_INVALID_ARG, "null argument");
+    return get_compacted(x, view, xyz, nullptr, capacity, count);
 }
 SL3D_CATCH(x)
 
@@ -285,11 +303,11 @@ try {
     if (rc) return rc;
     rc = ensure_packed(x);  // (the region sl3d_run_clouds writes is left alone)
     if (rc) return rc;
-    rc = launched(x, launch_compact_views(P, first_view, n_views, x->d_blk_cnt_all, x->d_blk_off_all, x->d_totals + first_view,
-                                          x->d_packed + 3 * (size_t)first_view * P.px_view_stride, x->stream));
+    rc = launched(x, launch_compact_views(P, first_view, n_views, x->blk_all, x->d_packed + 3 * (size_t)first_view * P.px_view_stride, nullptr, nullptr,
+                                          x->stream));
     if (rc) return rc;
     std::vector<unsigned long long> t((size_t)n_views);
-    HIPCHK(x, hipMemcpyAsync(t.data(), x->d_totals + first_view, sizeof(unsigned long long) * (size_t)n_views, hipMemcpyDeviceToHost, x->stream));
+    HIPCHK(x, hipMemcpyAsync(t.data(), x->blk_all.tot + first_view, sizeof(unsigned long long) * (size_t)n_views, hipMemcpyDeviceToHost, x->stream));
     SYNC_FOR_CALLER(x);
     for (int v = 0; v < n_views; v++) counts[v] = (int64_t)t[(size_t)v];
     if (device_xyz) *device_xyz = x->d_packed + 3 * (size_t)first_view * P.px_view_stride;
@@ -306,13 +324,7 @@ try {
     const float *dev = nullptr;
     size_t stride = 0;
     int rc = sl3d_compact_views(x, first_view, n_views, &dev, &stride, counts);
-    if (rc) return rc;
-    int64_t off = 0;
-    for (int v = 0; v < n_views && xyz; v++) {
-        const int64_t n = counts[v] < capacity - off ? counts[v] : capacity - off;
-        if (n > 0) HIPCHK_DRAIN(x, hipMemcpyAsync(xyz + 3 * off, dev + 3 * (size_t)v * stride, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
-        off += n > 0 ? n : 0;
-    }
+    if (rc || (rc = download_clamped(x, xyz, dev, stride, n_views, counts, capacity))) return rc;
     SYNC_FOR_CALLER(x);
     return SL3D_OK;
 }
@@ -347,23 +359,38 @@ try {
     if (!x || !count) return fail(x, SL3D_E_INVALID_ARG, "null argument");
     if (!x->d_texture || view < 0 || view >= (int)x->have_texture.size() || !x->have_texture[view])
         return fail(x, SL3D_E_INVALID_ARG, "no texture set for this view (sl3d_set_texture)");
-    ON_DEVICE(x);
-    const float *dev = nullptr;
-    int rc = sl3d_compact(x, view, &dev, count);
-    if (rc) return rc;
-    const int64_t n = *count < capacity ? *count : capacity;
-    if (n > 0) {
-        if (xyz) HIPCHK(x, hipMemcpyAsync(xyz, dev, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
-        if (rgb) HIPCHK_DRAIN(x, hipMemcpyAsync(rgb, x->d_cloud_rgb, (size_t)n * 3, hipMemcpyDeviceToHost, x->stream));
-        SYNC_FOR_CALLER(x);
-    }
-    return SL3D_OK;
+    return get_compacted(x, view, xyz, rgb, capacity, count);
 }
 SL3D_CATCH(x)
 
-// register_point_clouds(), 9/register_point_clouds.cpp:23-155, without the PLY files: the clouds are the
-// compacted clouds of the resident views, view k is rotated about Y by theta_k around (tx,ty,tz), theta_0 = 0,
-// theta_{k+1} = theta_k + rot_step in float (:145), angles in degrees converted with Pi = 22/7 (:89-93).
+// ---- N3: register_point_clouds(), 9/register_point_clouds.cpp:23-155, without the PLY files ---------------------------------------
+static int ensure_reg(sl3d_ctx *x)
+{
+    if (x->d_reg) return SL3D_OK;
+    return dev_alloc(x, &x->d_reg, (size_t)x->cfg.max_views * x->P.px_view_stride * 3);
+}
+
+// The loop over the views (:83-145): view k, of counts[k] points, is rotated about Y by theta_k around (tx,ty,tz) into d_reg behind the
+// views in front of it -- launch_view(k, counts[k], its place in d_reg, R4) enqueues that; theta_0 = 0, theta_{k+1} = theta_k + rot_step
+// in float (:145).  *total: the points of all views.  No host sync between the launches
+template <typename LaunchView>
+static int register_each(sl3d_ctx *x, int n_views, const int64_t *counts, float rot_step, int64_t *total, LaunchView launch_view)
+{
+    float theta = 0.0f;
+    *total = 0;
+    for (int k = 0; k < n_views; k++) {
+        float R4[4];
+        turntable_R4(theta, R4);
+        const int rc = launched(x, launch_view(k, counts[k], x->d_reg + 3 * *total, R4));
+        if (rc) return rc;
+        *total += counts[k];
+        theta += rot_step;
+    }
+    return SL3D_OK;
+}
+
+// the clouds are the compacted clouds of the resident views' dense results: one batched compaction (three launches, one read-back), then
+// one transform launch per view
 extern "C" int sl3d_register_views(sl3d_ctx *x, int first_view, int n_views, float tx, float ty, float tz, float rot_step, float *xyz,
                                    int64_t capacity, int64_t *total)
 try {
@@ -371,29 +398,18 @@ try {
     if (rc) return rc;
     if (!total) return fail(x, SL3D_E_INVALID_ARG, "null argument");
     ON_DEVICE(x);
-    const KParams &P = x->P;
-    if (!x->d_reg) {
-        rc = dev_alloc(x, &x->d_reg, (size_t)x->cfg.max_views * P.px_view_stride * 3);
-        if (rc) return rc;
-    }
-    // one batched compaction (three launches, one read-back), then one transform launch per view, no host sync between them
+    rc = ensure_reg(x);
+    if (rc) return rc;
     std::vector<int64_t> counts((size_t)n_views);
     const float *clouds = nullptr;
     size_t stride = 0;
     rc = sl3d_compact_views(x, first_view, n_views, &clouds, &stride, counts.data());
     if (rc) return rc;
-    float theta = 0.0f;
     int64_t off = 0;
-    for (int k = 0; k < n_views; k++) {
-        const int64_t n = counts[(size_t)k];
-        // R entries as the reference stores them: double cos/sin of theta*Pi/180.0 (Pi = 22.0/7.0), rounded to float
-        const float R4[4] = {(float)cos(theta * 22.0 / 7.0 / 180.0), (float)(-1.0f * sin(theta * 22.0 / 7.0 / 180.0)),
-                             (float)sin(theta * 22.0 / 7.0 / 180.0), (float)cos(theta * 22.0 / 7.0 / 180.0)};
-        rc = launched(x, launch_register(clouds + 3 * (size_t)k * stride, x->d_reg + 3 * off, (long)n, R4, tx, ty, tz, x->stream));
-        if (rc) return rc;
-        off += n;
-        theta += rot_step;
-    }
+    rc = register_each(x, n_views, counts.data(), rot_step, &off, [&](int k, int64_t n, float *out, const float *R4) {
+        return launch_register(clouds + 3 * (size_t)k * stride, out, (long)n, R4, tx, ty, tz, x->stream);
+    });
+    if (rc) return rc;
     SYNC_FOR_CALLER(x);
     *total = off;
     const int64_t m = off < capacity ? off : capacity;
@@ -423,24 +439,13 @@ try {
     rc = sl3d_get_cloud_counts(x, first_view, n_views, nullptr, nullptr, counts.data());
     if (rc) return rc;
     ON_DEVICE(x);
-    const KParams &P = x->P;
-    if (!x->d_reg) {
-        rc = dev_alloc(x, &x->d_reg, (size_t)x->cfg.max_views * P.px_view_stride * 3);
-        if (rc) return rc;
-    }
-    float theta = 0.0f;
+    rc = ensure_reg(x);
+    if (rc) return rc;
     int64_t off = 0;
-    for (int k = 0; k < n_views; k++) {
-        const int64_t n = counts[(size_t)k];
-        const float R4[4] = {(float)cos(theta * 22.0 / 7.0 / 180.0), (float)(-1.0f * sin(theta * 22.0 / 7.0 / 180.0)),
-                             (float)sin(theta * 22.0 / 7.0 / 180.0), (float)cos(theta * 22.0 / 7.0 / 180.0)};
-        if (n > 0) {
-            rc = launched(x, launch_seg_register(P, first_view + k, x->d_reg + 3 * off, R4, tx, ty, tz, x->stream));
-            if (rc) return rc;
-        }
-        off += n;
-        theta += rot_step;
-    }
+    rc = register_each(x, n_views, counts.data(), rot_step, &off, [&](int k, int64_t n, float *out, const float *R4) {
+        return n > 0 ? launch_seg_close(x->P, first_view + k, 1, SegClose{out, 0, false, 0, R4, tx, ty, tz}, x->stream) : 0;
+    });
+    if (rc) return rc;
     *total = off;
     const int64_t m = off < capacity ? off : capacity;
     if (xyz && m > 0) HIPCHK(x, hipMemcpyAsync(xyz, x->d_reg, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
@@ -460,9 +465,9 @@ static int ensure_mesh_buffers(sl3d_ctx *x)
     if (!x->d_mesh_cnt) rc = dev_alloc(x, &x->d_mesh_cnt, mv * 2 * nc);
     if (!rc && !x->d_mesh_off) rc = dev_alloc(x, &x->d_mesh_off, mv * 2 * nc);
     if (!rc && !x->d_mesh_tot) rc = dev_alloc(x, &x->d_mesh_tot, mv * 2);
-    if (!rc && !x->d_mesh_blk_cnt) rc = dev_alloc(x, &x->d_mesh_blk_cnt, mv * nb);
-    if (!rc && !x->d_mesh_blk_off) rc = dev_alloc(x, &x->d_mesh_blk_off, mv * nb);
-    if (!rc && !x->d_mesh_blk_tot) rc = dev_alloc(x, &x->d_mesh_blk_tot, mv);
+    if (!rc && !x->blk_mesh.cnt) rc = dev_alloc(x, &x->blk_mesh.cnt, mv * nb);
+    if (!rc && !x->blk_mesh.off) rc = dev_alloc(x, &x->blk_mesh.off, mv * nb);
+    if (!rc && !x->blk_mesh.tot) rc = dev_alloc(x, &x->blk_mesh.tot, mv);
     if (!rc && !x->d_mesh_xyz) rc = dev_alloc(x, &x->d_mesh_xyz, mv * P.px_view_stride * 3);
     if (!rc && !x->d_mesh_faces) rc = dev_alloc(x, &x->d_mesh_faces, mv * x->mesh_face_stride * 3);
     if (rc) return rc;
@@ -491,7 +496,7 @@ try {
     rc = ensure_mesh_buffers(x);
     if (rc) return rc;
     float *xyz = x->d_mesh_xyz + 3 * (size_t)first_view * P.px_view_stride;
-    rc = launched(x, launch_compact_views(P, first_view, n_views, x->d_mesh_blk_cnt, x->d_mesh_blk_off, x->d_mesh_blk_tot + first_view, xyz, x->stream));
+    rc = launched(x, launch_compact_views(P, first_view, n_views, x->blk_mesh, xyz, nullptr, nullptr, x->stream));
     if (rc) return rc;
     rc = launched(x, launch_mesh_views(P, first_view, n_views, max_edge, x->d_mesh_cnt, x->d_mesh_off, x->d_mesh_tot, x->d_mesh_faces,
                                        x->mesh_face_stride, x->stream));
@@ -523,15 +528,9 @@ try {
     sl3d_mesh m;
     rc = sl3d_mesh_views(x, first_view, n_views, max_edge, &m, n_vertices, n_faces);
     if (rc) return rc;
-    int64_t voff = 0, foff = 0;
-    for (int v = 0; v < n_views; v++) {
-        const int64_t nv = xyz ? std::min<int64_t>(n_vertices[v], vertex_capacity - voff) : 0;
-        const int64_t nf = faces ? std::min<int64_t>(n_faces[v], face_capacity - foff) : 0;
-        if (nv > 0) HIPCHK_DRAIN(x, hipMemcpyAsync(xyz + 3 * voff, m.xyz + 3 * (size_t)v * m.view_stride_points, (size_t)nv * 12, hipMemcpyDeviceToHost, x->stream));
-        if (nf > 0) HIPCHK_DRAIN(x, hipMemcpyAsync(faces + 3 * foff, m.faces + 3 * (size_t)v * m.view_stride_faces, (size_t)nf * 12, hipMemcpyDeviceToHost, x->stream));
-        voff += nv > 0 ? nv : 0;
-        foff += nf > 0 ? nf : 0;
-    }
+    rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc) rc = download_clamped(x, faces, m.faces, m.view_stride_faces, n_views, n_faces, face_capacity);
+    if (rc) return rc;
     SYNC_FOR_CALLER(x);
     return SL3D_OK;
 }

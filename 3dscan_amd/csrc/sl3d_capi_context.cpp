@@ -172,9 +172,9 @@ try {
     ALLOC(x->d_cal, 1);
     {
         const size_t nb = (P.px_view_stride + 1023) / 1024;
-        ALLOC(x->d_blk_cnt, nb);
-        ALLOC(x->d_blk_off, nb);
-        ALLOC(x->d_total, 1);
+        ALLOC(x->blk_one.cnt, nb);
+        ALLOC(x->blk_one.off, nb);
+        ALLOC(x->blk_one.tot, V);  // (a view's total at its own index, as in every CompactScratch)
         ALLOC(x->d_cloud, P.px_view_stride * 3);
     }
     ALLOC(x->d_band, V * P.px_view_stride);

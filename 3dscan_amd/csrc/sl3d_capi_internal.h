@@ -41,6 +41,7 @@ SL3D_INTERNAL int check_view(sl3d_ctx *x, int view, int n = 1);
 SL3D_INTERNAL int memory_kind(const void *p, int *device = nullptr);
 SL3D_INTERNAL bool is_pinned_host(const void *p);
 SL3D_INTERNAL int ensure_colrow(sl3d_ctx *x, size_t bytes);
+SL3D_INTERNAL void turntable_R4(float theta_deg, float R4[4]);  // the turntable's rotation by theta (sl3d_capi_next.cpp)
 
 // the part of the mask plane that holds source pixels: the window + 2-pixel halo, clipped to the frame
 struct MaskRegion {

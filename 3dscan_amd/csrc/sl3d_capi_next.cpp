@@ -46,6 +46,17 @@ try {
 }
 SL3D_CATCH(x)
 
+#define PI_REF 22.0 / 7.0 /* PROJECT_GLOBAL/global_cv.h:62: unparenthesised on purpose */
+
+// R of 9/register_point_clouds.cpp:89-93 as the reference stores it, {r00, r02, r20, r22} of the rotation about Y: double cos / sin of
+// theta * Pi / 180.0 -- theta a float in degrees, Pi the macro above, hence the expression below -- rounded to float
+void turntable_R4(float theta, float R4[4])
+{
+    R4[0] = R4[3] = (float)cos(theta * 22.0 / 7.0 / 180.0);
+    R4[1] = (float)(-1.0f * sin(theta * 22.0 / 7.0 / 180.0));
+    R4[2] = (float)sin(theta * 22.0 / 7.0 / 180.0);
+}
+
 // One cloud of 9/register_point_clouds.cpp:83-128 that lives in host memory (the reference reads each from a PLY file):
 // p -> R_y(theta) * (p - t) + t with the reference's float / double-accumulator arithmetic (k_register), theta in degrees
 // converted with Pi = 22/7.  The caller advances theta by rot_step IN FLOAT from cloud to cloud, as :145 does.
@@ -56,9 +67,8 @@ try {
     ON_DEVICE(x);
     float *d = nullptr;
     HIPCHK(x, hipMalloc((void **)&d, (size_t)n * 6 * sizeof(float)));
-    const float theta = theta_deg;
-    const float R4[4] = {(float)cos(theta * 22.0 / 7.0 / 180.0), (float)(-1.0f * sin(theta * 22.0 / 7.0 / 180.0)),
-                         (float)sin(theta * 22.0 / 7.0 / 180.0), (float)cos(theta * 22.0 / 7.0 / 180.0)};
+    float R4[4];
+    turntable_R4(theta_deg, R4);
     hipError_t e = hipMemcpyAsync(d, xyz_in, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, x->stream);
     int rc = e == hipSuccess ? launch_register(d, d + 3 * (size_t)n, (long)n, R4, tx, ty, tz, x->stream) : (int)e;
     if (rc == 0) rc = (int)hipMemcpyAsync(xyz_out, d + 3 * (size_t)n, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream);
@@ -70,7 +80,6 @@ try {
 SL3D_CATCH(x)
 
 // ---- N1: projector patterns (1/pattern_generator.cpp) ---------------------------------------------------------------
-#define PI_REF 22.0 / 7.0 /* PROJECT_GLOBAL/global_cv.h:62: unparenthesised on purpose */
 
 extern "C" int sl3d_pattern_counts(int proj_extent, int fringe_width, int *n_codes, int *n_planes)
 try {

@@ -69,9 +69,7 @@ struct sl3d_ctx {
     // the instantiation the fused launch made last on this context RAN (launch_fused; nmax == 0: none yet)
     FusedKey last_fused;
     float *d_points = nullptr;
-    unsigned *d_blk_cnt = nullptr;            // compaction scratch: per-1024-pixel block counts,
-    unsigned long long *d_blk_off = nullptr;  // their exclusive scan, and the total
-    unsigned long long *d_total = nullptr;
+    CompactScratch blk_one{};                 // compaction scratch of sl3d_compact (one view at a time)
     float *d_cloud = nullptr;                 // compacted cloud of one view (capacity = window pixels)
     float *d_reg = nullptr;                   // registered clouds of all views (allocated on first use)
     uint8_t *d_raw = nullptr;  // sl3d_set_frames_raw: the raw planes of one axis + the camera's undistortion map
@@ -83,27 +81,32 @@ struct sl3d_ctx {
     bool und_map_valid = false;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;   // sl3d_process_views: upload and download run beside the compute stream
     std::vector<hipEvent_t> ev_up, ev_done, ev_down;  // per view slot: frames landed / kernel finished / results copied out
-    float *d_clouds = nullptr;                // batched compaction: one region of px_view_stride points per view (first use)
-    unsigned *d_blk_cnt_all = nullptr;
-    unsigned long long *d_blk_off_all = nullptr, *d_totals = nullptr;
+    float *d_clouds = nullptr;                // the segmented clouds sl3d_run_clouds writes: px_view_stride point slots per view (first use)
+    CompactScratch blk_all{};                 // compaction scratch of sl3d_compact_views (the batch goes to d_packed)
     unsigned *d_seg_counts = nullptr;         // sl3d_run_clouds (segmented clouds): [view][n_segs] counts, their exclusive scan,
     unsigned long long *d_seg_offsets = nullptr;
     float *d_packed = nullptr;                // and the contiguous copy made on demand (also the output of sl3d_compact_views)
-    // per view, after sl3d_run_clouds: 0 = k_seg_scan has run (offsets and total valid), 1 = not scanned -- a launch of a few views
-    // leaves the scan to the consumer (k_seg_close<.., SCAN>), 2 = a scanning consumer has left the total, the offsets are still unset
-    std::vector<uint8_t> scan_state;
+    enum class Scan : uint8_t {
+        DONE,        // k_seg_scan has run: offsets and total valid
+        PENDING,     // not scanned: a launch of a few views leaves the scan to the consumer (k_seg_close<.., SCAN>)
+        TOTAL_ONLY,  // a scanning consumer has left the total, the offsets are still unset
+    };
+    std::vector<Scan> scan_state;             // per view, after sl3d_run_clouds
     // sl3d_mesh_views (all allocated on first use): [max_views][2][mesh_chunks] counts of valid pixels / faces per chunk, their
     // exclusive scans, [max_views][2] totals; the faces: [max_views][mesh_face_stride][3] vertex ids into the view's cloud in d_mesh_xyz
     // ([max_views][px_view_stride][3], written by launch_compact_views with block scratch of its own: nothing another call handed out
     // is overwritten)
-    unsigned *d_mesh_cnt = nullptr, *d_mesh_blk_cnt = nullptr;
-    unsigned long long *d_mesh_off = nullptr, *d_mesh_tot = nullptr, *d_mesh_blk_off = nullptr, *d_mesh_blk_tot = nullptr;
+    unsigned *d_mesh_cnt = nullptr;
+    unsigned long long *d_mesh_off = nullptr, *d_mesh_tot = nullptr;
+    CompactScratch blk_mesh{};                // the block scratch of that compaction
     int32_t *d_mesh_faces = nullptr;
     float *d_mesh_xyz = nullptr;
     size_t mesh_face_stride = 0;
     bool mesh_ready = false;                  // ensure_mesh_buffers ran to its end
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
+    // a view's total out of those words (the device stores them: read once the stream has drained)
+    int64_t cloud_total(int view) const { return (int64_t)((volatile unsigned long long *)h_counts)[view]; }
     uint8_t *d_texture = nullptr;             // [view][row][pitch][3] BGR texture of save_point_cloud (allocated by sl3d_set_texture)
     uint8_t *d_cloud_rgb = nullptr;           // r,g,b of the compacted cloud of one view
     std::vector<char> have_texture;

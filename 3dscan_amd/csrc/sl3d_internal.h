@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP
-// kernels (sl3d_kernels.hip).  Not part of the public ABI.
+// kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip).  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -140,9 +140,9 @@ struct KParams {
     // (appended in round 6: the fields above keep their kernel-argument offsets)
     MaskIn mi;                 // MASKIN launches only (read through the kernel-argument segment, sl3d_fused.h: maskin_args)
 };
-static_assert(SL3D_SMALL_LAUNCH_VIEWS == 4, "KParams::mi_origin holds one entry per view of a small launch");
+static_assert(SL3D_SMALL_LAUNCH_VIEWS == 4, "MaskIn::origin holds one entry per view of a small launch");
 
-// launchers (sl3d_fused_launch.hip, sl3d_kernels.hip); `stream` is a hipStream_t
+// launchers (sl3d_fused_launch.hip, sl3d_kernels.hip, sl3d_clouds.hip); `stream` is a hipStream_t
 // cmode: 0 = dense xyz + valid planes, 2 = segmented clouds
 // prefer_gated: the views of a small launch are sparsely selected (sl3d_capi_inputs.cpp: sparse_views)
 // mi != nullptr: a MASKIN launch (the views' valid bits from their raw selection; only where fused_choice has a MASKIN kernel)
@@ -171,14 +171,19 @@ unsigned fused_maskin_part_stride(const KParams &P);
 unsigned fused_maskin_part_words(const KParams &P);
 // segmented clouds: offsets / totals of views [first_view, first_view + n_views) from the counts the fused kernel stored
 int launch_seg_scan(const KParams &P, int first_view, int n_views, void *stream);
-// segments -> contiguous: view first_view+k's points to dst + 3*k*dst_view_stride_points (dst: device memory or mapped host memory)
-int launch_seg_close(const KParams &P, int first_view, int n_views, float *dst, size_t dst_view_stride_points, void *stream);
-// the same when the views' counts have not been scanned: the consumer scans on entry (k_seg_close<.., SCAN>), writes at most
-// capacity_points points per view and leaves the views' totals in P.cloud_totals
-int launch_seg_close_scan(const KParams &P, int first_view, int n_views, float *dst, size_t dst_view_stride_points, unsigned long long capacity_points,
-                          void *stream);
-// register_point_clouds on segmented input: view first_view+k rotated by R4[4*k..], written at out + 3*(out_base[k] + offset)
-int launch_seg_register(const KParams &P, int view, float *out, const float R4[4], float tx, float ty, float tz, void *stream);
+// segments -> contiguous (k_seg_close): view first_view + k's points go to dst + 3 * k * dst_view_stride_points (dst: device memory or
+// mapped host memory).  scan: the views' counts have NOT been scanned -- the kernel scans on entry instead of reading P.seg_offsets, writes
+// at most capacity_points points of each view and leaves the views' totals in P.cloud_totals.  R4 (not together with scan):
+// register_point_clouds on the way -- every point rotated about Y by R4 = {r00, r02, r20, r22} around (tx, ty, tz)
+struct SegClose {
+    float *dst;
+    size_t dst_view_stride_points;
+    bool scan;
+    unsigned long long capacity_points;
+    const float *R4;
+    float tx, ty, tz;
+};
+int launch_seg_close(const KParams &P, int first_view, int n_views, const SegClose &c, void *stream);
 int fused_tiles(const KParams &P);  // number of 1024-pixel tiles per view (KParams::n_tiles)
 // k_mask_prepare over views [first_view, first_view + n_views): view k reads S.origin + k * S.view_stride; block b of view v stores
 // {seq, quads with a valid pixel} at partials[v * mask_prepare_blocks(P) + b] (host memory mapped into the device)
@@ -201,10 +206,14 @@ int launch_wrap(const KParams &P, int view, int axis, void *stream);
 int launch_unwrap(const KParams &P, int view, int axis, void *stream);
 int launch_corr(const KParams &P, int view, void *stream);
 int launch_tri(const KParams &P, const DevCal &C, int view, void *stream);
-int launch_compact(const KParams &P, int view, unsigned *block_counts, unsigned long long *block_offsets, unsigned long long *total,
-                   float *cloud, const uint8_t *texture, uint8_t *rgb_out, void *stream);
-int launch_compact_views(const KParams &P, int first_view, int n_views, unsigned *block_counts, unsigned long long *block_offsets,
-                         unsigned long long *totals, float *clouds, void *stream);
+// the scratch of one compaction (O1 / N2): counts of the valid pixels per 1024-pixel block, their exclusive scan -- one slot per view of
+// a launch -- and the views' totals, [max_views]: view v's at tot[v]
+struct CompactScratch {
+    unsigned *cnt;
+    unsigned long long *off, *tot;
+};
+int launch_compact_views(const KParams &P, int first_view, int n_views, const CompactScratch &s, float *clouds, const uint8_t *texture,
+                         uint8_t *rgb_out, void *stream);
 int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, int n_arrays, unsigned long long *totals, void *stream);
 // the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A view has
 // mesh_chunks(P) chunks (1024 pixels of one row); counts / offsets: [max_views][2][chunks] (valid pixels, faces) and their exclusive scans,

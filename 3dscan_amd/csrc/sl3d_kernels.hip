@@ -1,9 +1,9 @@
-// sl3d_kernels.hip -- gfx950 (MI355X, wave64) kernels beside the fused hot path (which lives in sl3d_fused.h / sl3d_fused_*.hip):
+// sl3d_kernels.hip -- gfx950 (MI355X, wave64) kernels beside the fused hot path (which lives in sl3d_fused.h / sl3d_fused_*.hip) that
+// PRODUCE or prepare something; what consumes a result (compaction, the segmented clouds, registration) is sl3d_clouds.hip:
 //   k_mask_prepare                      : H0 / S3b / S3d -- selection mask -> 0/1 plane + the valid map after the boundary removal
 //   k_wrap / k_unwrap / k_corr / k_tri  : the path cut at the reference's stage boundaries (parity mode; they write the planes
 //                                         the reference keeps in globals, including its 8-bit known-answer debug images)
 //   k_cam_table / k_proj_table          : T1 per calibration (what the reference tabulates per scan)
-//   k_seg_scan / k_seg_close / k_compact_* / k_register : consumers of the clouds (O1, N2, N3)
 //   k_undist_* (N4), k_pattern / k_synth (N1), k_to_colrow / k_mask_from_colrow (the reference's own [col][row] layouts),
 //   k_atan_selfcheck (the device-side proof that the lattice atan2 equals the host's libm)
 // Shared device arithmetic: sl3d_device.h.  Compiled with -ffp-contract=off.
@@ -463,25 +463,10 @@ __global__ __launch_bounds__(256) void k_undist_remap_planes(const uint8_t *__re
     }
 }
 
-int launch_undistort_planes(const uint8_t *src, size_t spitch, size_t splane, uint8_t *dst, size_t dpitch, size_t dplane, int width, int height,
-                            int n_planes, const double K[9], const double dist[5], short *m1, unsigned short *m2, bool build_map, void *stream)
-{
-    UndistParams U;
-    for (int k = 0; k < 9; k++) U.K[k] = K[k];
-    for (int k = 0; k < 5; k++) U.d[k] = dist[k];
-    U.width = width; U.height = height; U.cn = 1;
-    int stripe = 4096 / (width > 1 ? width : 1);
-    U.stripe = stripe < 1 ? 1 : (stripe > height ? height : stripe);
-    hipStream_t st = (hipStream_t)stream;
-    if (build_map) hipLaunchKernelGGL(k_undist_map, dim3((height + 63) / 64), dim3(64), 0, st, U, m1, m2);
-    hipLaunchKernelGGL(k_undist_remap_planes, dim3((width + 255) / 256, height), dim3(256), 0, st, src, spitch, splane, width, height, n_planes, m1, m2,
-                       dst, dpitch, dplane);
-    return (int)hipGetLastError();
-}
-
-// build_map = false: m1 / m2 already hold the map of this (K, dist, width, height) -- every frame of a scan shares it
-int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],
-                     const double dist[5], short *m1, unsigned short *m2, bool build_map, void *stream)
+// the parameters both remap kernels take, and -- build_map: m1 / m2 do not hold the map of this (K, dist, width, height) yet; every
+// frame of a scan shares it -- the map in front of them on the stream.  The stripe is cvUndistort2's: min(max(1, 4096 / width), height) rows
+static UndistParams undist_prepare(int width, int height, int cn, const double K[9], const double dist[5], short *m1, unsigned short *m2,
+                                   bool build_map, hipStream_t st)
 {
     UndistParams U;
     for (int k = 0; k < 9; k++) U.K[k] = K[k];
@@ -489,8 +474,25 @@ int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t ds
     U.width = width; U.height = height; U.cn = cn;
     int stripe = 4096 / (width > 1 ? width : 1);
     U.stripe = stripe < 1 ? 1 : (stripe > height ? height : stripe);
-    hipStream_t st = (hipStream_t)stream;
     if (build_map) hipLaunchKernelGGL(k_undist_map, dim3((height + 63) / 64), dim3(64), 0, st, U, m1, m2);
+    return U;
+}
+
+int launch_undistort_planes(const uint8_t *src, size_t spitch, size_t splane, uint8_t *dst, size_t dpitch, size_t dplane, int width, int height,
+                            int n_planes, const double K[9], const double dist[5], short *m1, unsigned short *m2, bool build_map, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    undist_prepare(width, height, 1, K, dist, m1, m2, build_map, st);
+    hipLaunchKernelGGL(k_undist_remap_planes, dim3((width + 255) / 256, height), dim3(256), 0, st, src, spitch, splane, width, height, n_planes, m1, m2,
+                       dst, dpitch, dplane);
+    return (int)hipGetLastError();
+}
+
+int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],
+                     const double dist[5], short *m1, unsigned short *m2, bool build_map, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const UndistParams U = undist_prepare(width, height, cn, K, dist, m1, m2, build_map, st);
     hipLaunchKernelGGL(k_undist_remap, dim3((width + 255) / 256, height), dim3(256), 0, st, src, sstride, U, m1, m2, dst, dstride);
     return (int)hipGetLastError();
 }
@@ -544,351 +546,6 @@ int launch_atan_selfcheck(const float *tab_phi, const float *tab_shift, unsigned
 {
     const int n = SL3D_ATAN_T1 * SL3D_ATAN_T2;
     hipLaunchKernelGGL(k_atan_selfcheck, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, tab_phi, tab_shift, mismatches);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// O1 / N2: compaction of the dense cloud in the reference's row-major scan order
-// (8/save_point_cloud.cpp:33-37 counts the valid pixels, :85-104 appends them).  Three launches on the
-// context's stream: per-block counts (wave ballots), an exclusive scan of the block counts by one block,
-// and the scatter.  A block covers 1024 consecutive pixels of the pitch-padded plane; padding pixels are
-// never valid, so the scan order of the valid pixels is exactly the reference's.
-// ------------------------------------------------------------------------------------------------
-// blockIdx.y = view of a batch (strides in elements; 0 strides for a single view)
-__global__ __launch_bounds__(256) void k_compact_count(const uint8_t *valid, size_t n_px, unsigned *block_counts, size_t valid_stride, int nb)
-{
-    valid += (size_t)blockIdx.y * valid_stride;
-    block_counts += (size_t)blockIdx.y * nb;
-    __shared__ unsigned s_cnt[4];
-    const size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    unsigned w = base < n_px ? *(const unsigned *)(valid + base) : 0u;  // 4 valid bytes (0/1)
-    unsigned c = __popc(w & 0x01010101u);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
-// exclusive scan of n counts by a single 1024-thread block (n is a few thousand .. tens of thousands)
-__global__ __launch_bounds__(1024) void k_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, unsigned long long *total)
-{
-    counts += (size_t)blockIdx.x * n;   // one block per view of a batch
-    offsets += (size_t)blockIdx.x * n;
-    total += blockIdx.x;
-    __shared__ unsigned long long s_part[1024];
-    const int per = (n + 1023) / 1024, lo = threadIdx.x * per, hi = min(lo + per, n);
-    unsigned long long sum = 0;
-    for (int i = lo; i < hi; i++) sum += counts[i];
-    s_part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {  // Hillis-Steele inclusive scan of the 1024 partial sums
-        unsigned long long v = threadIdx.x >= d ? s_part[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    unsigned long long run = threadIdx.x == 0 ? 0 : s_part[threadIdx.x - 1];
-    for (int i = lo; i < hi; i++) { offsets[i] = run; run += counts[i]; }
-    if (threadIdx.x == 1023) *total = s_part[1023];
-}
-
-// texture (may be NULL): the BGR camera image save_point_cloud() colours the cloud with (8/save_point_cloud.cpp:46-52,
-// 70-72), [row][pitch][3] bytes; rgb_out receives r,g,b per compacted point
-__global__ __launch_bounds__(256) void k_compact_scatter(const uint8_t *valid, const float *points, size_t n_px,
-                                                         const unsigned long long *block_offsets, float *cloud, const uint8_t *texture,
-                                                         uint8_t *rgb_out, size_t view_stride, int nb)
-{
-    valid += (size_t)blockIdx.y * view_stride;
-    points += 3 * (size_t)blockIdx.y * view_stride;
-    cloud += 3 * (size_t)blockIdx.y * view_stride;
-    block_offsets += (size_t)blockIdx.y * nb;
-    __shared__ unsigned s_wave[4];
-    __shared__ __attribute__((aligned(16))) float s_pts[1024 * 3];  // the block's valid points, compacted
-    const size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    const unsigned w = base < n_px ? (*(const unsigned *)(valid + base) & 0x01010101u) : 0u;
-    const unsigned c = __popc(w);
-    // exclusive prefix of c over the block: wave scan by shuffles, then the 4 wave totals
-    unsigned incl = c;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(incl, off, 64);
-        if ((threadIdx.x & 63) >= off) incl += t;
-    }
-    if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned wave_base = 0;
-    for (int i = 0; i < (int)(threadIdx.x >> 6); i++) wave_base += s_wave[i];
-    const unsigned block_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    unsigned local = wave_base + (incl - c);
-    const unsigned long long block_off = block_offsets[blockIdx.x];
-    if (w) {
-        // the 4 pixels of a lane are 48 contiguous bytes: three 16-B loads, then the valid ones go to LDS in scan order
-        const float4 *p4 = (const float4 *)(points + 3 * base);
-        const float4 a = p4[0], b = p4[1], d = p4[2];
-        const float q[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, d.x, d.y, d.z, d.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if ((w >> (8 * k)) & 1u) {
-                s_pts[3 * local + 0] = q[3 * k + 0];
-                s_pts[3 * local + 1] = q[3 * k + 1];
-                s_pts[3 * local + 2] = q[3 * k + 2];
-                if (texture) {
-                    const uint8_t *t = texture + 3 * (base + k);  // b, g, r
-                    uint8_t *o = rgb_out + 3 * (block_off + local);
-                    o[0] = t[2]; o[1] = t[1]; o[2] = t[0];
-                }
-                local++;
-            }
-    }
-    __syncthreads();
-    // the block's segment of the cloud is contiguous: coalesced dword stores
-    float *dst = cloud + 3 * block_off;
-    for (unsigned i = threadIdx.x; i < 3 * block_total; i += 256) dst[i] = s_pts[i];
-}
-
-int launch_compact(const KParams &P, int view, unsigned *block_counts, unsigned long long *block_offsets, unsigned long long *total,
-                   float *cloud, const uint8_t *texture, uint8_t *rgb_out, void *stream)
-{
-    const size_t n_px = P.px_view_stride;
-    const int nb = (int)((n_px + 1023) / 1024);
-    const uint8_t *valid = P.valid + (size_t)view * P.px_view_stride;
-    const float *points = P.points + 3 * (size_t)view * P.px_view_stride;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(256), 0, st, valid, n_px, block_counts, (size_t)0, nb);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, block_counts, block_offsets, nb, total);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(256), 0, st, valid, points, n_px, block_offsets, cloud, texture, rgb_out, (size_t)0, nb);
-    return (int)hipGetLastError();
-}
-
-// the same three kernels over a batch of views: view v's compacted cloud starts at clouds + 3*v*px_view_stride
-int launch_compact_views(const KParams &P, int first_view, int n_views, unsigned *block_counts, unsigned long long *block_offsets,
-                         unsigned long long *totals, float *clouds, void *stream)
-{
-    const size_t n_px = P.px_view_stride;
-    const int nb = (int)((n_px + 1023) / 1024);
-    const uint8_t *valid = P.valid + (size_t)first_view * P.px_view_stride;
-    const float *points = P.points + 3 * (size_t)first_view * P.px_view_stride;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_compact_count, dim3(nb, n_views), dim3(256), 0, st, valid, n_px, block_counts, n_px, nb);
-    hipLaunchKernelGGL(k_compact_scan, dim3(n_views), dim3(1024), 0, st, block_counts, block_offsets, nb, totals);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb, n_views), dim3(256), 0, st, valid, points, n_px, block_offsets, clouds, (const uint8_t *)nullptr,
-                       (uint8_t *)nullptr, n_px, nb);
-    return (int)hipGetLastError();
-}
-
-// k_compact_scan for another unit (sl3d_mesh.hip): n_arrays independent arrays of n counts each, back to back
-int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, int n_arrays, unsigned long long *totals, void *stream)
-{
-    hipLaunchKernelGGL(k_compact_scan, dim3(n_arrays), dim3(1024), 0, (hipStream_t)stream, counts, offsets, n, totals);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Consumers of the SEGMENTED clouds the fused kernel writes (k_fused<..., CMODE = 2>): a view's cloud is the concatenation of
-// its segments' first `count` points.  One wave per segment, one point (12 bytes) per lane and step.
-// ------------------------------------------------------------------------------------------------
-// Exclusive scan of one view's segment counts (1024-thread blocks), behind every segmented launch: it is on the critical path of
-// sl3d_run_clouds, so it is written for latency.  A view's segments are scanned by SL3D_SCAN_PARTS blocks (one block per view was a
-// latency chain of ~10 us on a 256-CU machine): block (view, part) SUMS the counts of the parts in front of it -- the same
-// coalesced reads every one of them does anyway, at most n dwords from the L2 -- and scans its own part from that carry; no block
-// waits for another.  The last part's block leaves the view's total in the mapped host word sl3d_get_cloud_counts reads.
-// ONE memory round trip per block (round 4): it requests its own counts -- 4 consecutive ones per thread, one 16-byte load, a wave
-// reads 1 KB contiguous -- AND the counts in front of its part in the same breath, sums the latter, scans the former in registers
-// (the 4 entries, 6 wave shuffles, the 16 wave totals through LDS: one block barrier per chunk) and writes 4 offsets per thread
-// (32 contiguous bytes); the next chunk of a long part travels while the current one is scanned.  (Until then: the carry first,
-// then the chunk through a padded LDS array with five barriers -- 6.1 us for the 8,100 counts of one 1080p view;
-// profiles/r04_seg_scan_ab.txt.  Rounds 2-3: k_compact_scan, 32 strided dwords per thread, 14.3 us for 16 x 32,400 counts; one
-// block per view with runs of 32: 10.2 us.)
-#define SL3D_SCAN_RUN 4
-#define SL3D_SCAN_PARTS 8
-__global__ __launch_bounds__(1024) void k_seg_scan(const unsigned *__restrict__ counts, unsigned long long *__restrict__ offsets, int n,
-                                                   unsigned long long *total)
-{
-    const int view = (int)blockIdx.y, part = (int)blockIdx.x;
-    counts += (size_t)view * n;   // (n = 4 * tiles: every row of counts is 16-byte aligned, every row of offsets 32-byte aligned)
-    offsets += (size_t)view * n;
-    constexpr int CHUNK = 1024 * SL3D_SCAN_RUN;
-    // parts are whole chunks, so that every chunk of a part is scanned by the same code path
-    const int part_len = (((n + SL3D_SCAN_PARTS - 1) / SL3D_SCAN_PARTS + CHUNK - 1) / CHUNK) * CHUNK;
-    const int begin = min(part * part_len, n), end = min(begin + part_len, n);
-    __shared__ unsigned long long s_part[16];
-    __shared__ unsigned s_wave[2][16];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint4 zero = {0u, 0u, 0u, 0u};
-    auto mine = [&](int base) { return base + SL3D_SCAN_RUN * t < end ? *(const uint4 *)(counts + base + SL3D_SCAN_RUN * t) : zero; };
-    uint4 c = mine(begin);
-    unsigned long long carry;
-    {   // the carry into this part: the sum of everything in front of it (requested together with the part's first chunk)
-        unsigned long long acc = 0ull;
-        for (int i = SL3D_SCAN_RUN * t; i < begin; i += CHUNK) {
-            const uint4 f = *(const uint4 *)(counts + i);
-            acc += (unsigned long long)f.x + f.y + f.z + f.w;
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-        if (lane == 0) s_part[wave] = acc;
-        __syncthreads();
-        carry = 0ull;
-#pragma unroll
-        for (int w = 0; w < 16; w++) carry += s_part[w];
-    }
-    int buf = 0;
-    for (int base = begin;; base += CHUNK, buf ^= 1) {
-        const uint4 next = base + CHUNK < end ? mine(base + CHUNK) : zero;  // (the next chunk travels while this one is scanned)
-        const unsigned e1 = c.x, e2 = e1 + c.y, e3 = e2 + c.z, run = e3 + c.w;
-        unsigned incl = run;  // inclusive scan of the run totals over the wave, then over the 16 waves
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) s_wave[buf][wave] = incl;
-        __syncthreads();  // (two buffers: the next chunk's totals do not overwrite what a slower wave still reads)
-        unsigned wbase = 0, chunk_total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) {
-            const unsigned v = s_wave[buf][w];
-            wbase += w < wave ? v : 0u;
-            chunk_total += v;
-        }
-        if (base + SL3D_SCAN_RUN * t < end) {
-            const unsigned long long o = carry + (unsigned long long)(wbase + (incl - run));
-            ulonglong2 *dst = (ulonglong2 *)(offsets + base + SL3D_SCAN_RUN * t);
-            dst[0] = make_ulonglong2(o, o + e1);
-            dst[1] = make_ulonglong2(o + e2, o + e3);
-        }
-        carry += (unsigned long long)chunk_total;
-        if (base + CHUNK >= end) break;
-        c = next;
-    }
-    if (t == 0 && part == SL3D_SCAN_PARTS - 1) total[view] = carry;
-}
-
-int launch_seg_scan(const KParams &P, int first_view, int n_views, void *stream)
-{
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_seg_scan, dim3(SL3D_SCAN_PARTS, (unsigned)n_views), dim3(1024), 0, (hipStream_t)stream,
-                       P.seg_counts + (size_t)first_view * P.n_segs, P.seg_offsets + (size_t)first_view * P.n_segs, P.n_segs,
-                       P.cloud_totals + first_view);
-    return (int)hipGetLastError();
-}
-
-// REG = false: plain copy (closing the gaps); true: the rigid transform of k_register on the way (9/register_point_clouds.cpp:109-117)
-// SCAN = false: the segments' offsets come from k_seg_scan.  true: the consumer scans on entry -- a block (4 segments) adds up the
-// counts in front of it itself (at most n_segs dwords from the L2, 16 bytes per lane and step: what every part of k_seg_scan does
-// for its carry), so a launch of a few views needs NO scan launch between the fused kernel and its consumer; the last block leaves
-// the view's total in total_out[view] (host memory mapped into the device: sl3d_get_cloud_counts' word).  Points whose index in the
-// closed cloud is >= capacity are not written (a destination smaller than the cloud takes its first `capacity` points).
-template <bool REG, bool SCAN>
-__global__ __launch_bounds__(256) void k_seg_close(const float *__restrict__ seg_xyz, const unsigned *__restrict__ counts,
-                                                   const unsigned long long *__restrict__ offsets, int n_segs, size_t src_view_stride, float *dst,
-                                                   size_t dst_view_stride, float r00, float r02, float r20, float r22, float tx, float ty, float tz,
-                                                   unsigned long long *total_out, unsigned long long capacity)
-{
-    typedef float f32x3 __attribute__((ext_vector_type(3), aligned(4)));
-    const int wave = (int)(threadIdx.x >> 6);
-    const int seg = blockIdx.x * 4 + wave, lane = (int)(threadIdx.x & 63u), v = blockIdx.y;
-    const unsigned cnt = seg < n_segs ? counts[(size_t)v * n_segs + seg] : 0u;
-    unsigned long long off;
-    if (SCAN) {
-        __shared__ unsigned long long s_front[4];
-        __shared__ unsigned s_cnt[4];
-        const unsigned *cv = counts + (size_t)v * n_segs;
-        const int n_front = (int)blockIdx.x * 4;  // (whole 16-byte groups: n_segs = 4 * tiles, every row of counts is 16-byte aligned)
-        unsigned long long acc = 0ull;
-        for (int i = 4 * (int)threadIdx.x; i < n_front; i += 1024) {
-            const uint4 f = *(const uint4 *)(cv + i);
-            acc += (unsigned long long)f.x + f.y + f.z + f.w;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        if (lane == 0) {
-            s_front[wave] = acc;
-            s_cnt[wave] = cnt;
-        }
-        __syncthreads();
-        off = s_front[0] + s_front[1] + s_front[2] + s_front[3];
-#pragma unroll
-        for (int w = 0; w < 4; w++) off += w < wave ? s_cnt[w] : 0u;
-        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 192) total_out[v] = off + cnt;  // (wave 3 of the last block: everything in front + its own)
-    } else {
-        if (seg >= n_segs) return;
-        off = offsets[(size_t)v * n_segs + seg];
-    }
-    // (a 3-float vector type is PADDED to 16 bytes: points are addressed through float pointers, 12 bytes apart)
-    const float *src = seg_xyz + 3 * ((size_t)v * src_view_stride + (size_t)seg * SL3D_SEG_POINTS);
-    float *out = dst + 3 * ((size_t)v * dst_view_stride + (size_t)off);
-    const unsigned long long room = off < capacity ? capacity - off : 0ull;
-    const unsigned n = SCAN ? (unsigned)(room < cnt ? room : cnt) : cnt;
-    for (unsigned i = (unsigned)lane; i < n; i += 64u) {
-        f32x3 p = *(const f32x3 *)(src + 3 * (size_t)i);
-        if (REG) {
-            const float x = p.x - tx, y = p.y - ty, z = p.z - tz;
-            const float X = (float)(((double)r00 * (double)x + 0.0 * (double)y) + (double)r02 * (double)z);
-            const float Y = (float)((0.0 * (double)x + 1.0 * (double)y) + 0.0 * (double)z);
-            const float Z = (float)(((double)r20 * (double)x + 0.0 * (double)y) + (double)r22 * (double)z);
-            p.x = X + tx; p.y = Y + ty; p.z = Z + tz;
-        }
-        *(f32x3 *)(out + 3 * (size_t)i) = p;
-    }
-}
-
-int launch_seg_close(const KParams &P, int first_view, int n_views, float *dst, size_t dst_view_stride_points, void *stream)
-{
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_seg_close<false, false>), dim3((unsigned)((P.n_segs + 3) / 4), (unsigned)n_views), dim3(256), 0, (hipStream_t)stream,
-                       P.clouds + 3 * (size_t)first_view * P.px_view_stride, P.seg_counts + (size_t)first_view * P.n_segs,
-                       P.seg_offsets + (size_t)first_view * P.n_segs, P.n_segs, P.px_view_stride, dst, dst_view_stride_points, 0.f, 0.f, 0.f, 0.f, 0.f,
-                       0.f, 0.f, (unsigned long long *)nullptr, ~0ull);
-    return (int)hipGetLastError();
-}
-
-// the same for views whose segment counts have NOT been scanned (sl3d_run_clouds over a few views leaves the scan to its consumer):
-// view first_view + k to dst + 3 * k * dst_view_stride_points, at most capacity_points points of each; the views' totals go to
-// P.cloud_totals
-int launch_seg_close_scan(const KParams &P, int first_view, int n_views, float *dst, size_t dst_view_stride_points, unsigned long long capacity_points,
-                          void *stream)
-{
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_seg_close<false, true>), dim3((unsigned)((P.n_segs + 3) / 4), (unsigned)n_views), dim3(256), 0, (hipStream_t)stream,
-                       P.clouds + 3 * (size_t)first_view * P.px_view_stride, P.seg_counts + (size_t)first_view * P.n_segs,
-                       (const unsigned long long *)nullptr, P.n_segs, P.px_view_stride, dst, dst_view_stride_points, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
-                       P.cloud_totals + first_view, capacity_points);
-    return (int)hipGetLastError();
-}
-
-int launch_seg_register(const KParams &P, int view, float *out, const float R4[4], float tx, float ty, float tz, void *stream)
-{
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_seg_close<true, false>), dim3((unsigned)((P.n_segs + 3) / 4), 1u), dim3(256), 0, (hipStream_t)stream,
-                       P.clouds + 3 * (size_t)view * P.px_view_stride, P.seg_counts + (size_t)view * P.n_segs, P.seg_offsets + (size_t)view * P.n_segs,
-                       P.n_segs, P.px_view_stride, out, (size_t)0, R4[0], R4[1], R4[2], R4[3], tx, ty, tz, (unsigned long long *)nullptr, ~0ull);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------
-// N3: turntable registration, 9/register_point_clouds.cpp:83-128.  Per point, in the reference's types:
-// p -= t (float), p = R*p with the float GEMM of cvMatMul (double accumulator, k ascending, rounded to float on
-// store), p += t (float).  R = rotation about Y by theta (row 1 and the last column are the identity's).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_register(const float *in, float *out, long n, float r00, float r02, float r20, float r22,
-                                                  float tx, float ty, float tz)
-{
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float x = in[3 * i + 0] - tx, y = in[3 * i + 1] - ty, z = in[3 * i + 2] - tz;  // :109-111
-    // rows of R: (r00, 0, r02, 0), (0, 1, 0, 0), (r20, 0, r22, 0); the products with exact zeros add nothing
-    const float X = (float)(((double)r00 * (double)x + 0.0 * (double)y) + (double)r02 * (double)z);  // :113
-    const float Y = (float)((0.0 * (double)x + 1.0 * (double)y) + 0.0 * (double)z);
-    const float Z = (float)(((double)r20 * (double)x + 0.0 * (double)y) + (double)r22 * (double)z);
-    out[3 * i + 0] = X + tx;  // :115-117
-    out[3 * i + 1] = Y + ty;
-    out[3 * i + 2] = Z + tz;
-}
-
-int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream)
-{
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_register, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, n, R4[0], R4[1], R4[2], R4[3], tx, ty, tz);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // sl3d_mesh.hip -- the mesh stage: ordered triangles over the organized point grid of a dense result (sl3d_mesh_views; the
 // definition and its arithmetic: sl3d_mesh.h).  The vertices are the compacted cloud launch_compact_views writes; this unit adds
 //   k_mesh_count : per chunk (1024 pixels of ONE row) the valid pixels of the chunk and the faces of the cells whose corner a lies in it
-//   (k_compact_scan over the 2 count arrays of every view: sl3d_kernels.hip)
+//   (k_compact_scan over the 2 count arrays of every view: sl3d_clouds.hip)
 //   k_mesh_emit  : the same cells again, every face ranked by wave prefixes and written at face_offset[chunk] + rank
 // A lane owns one quad of row r -- 4 cells: its own 4 pixels of rows r and r + 1 (one dword of valid bytes and three 16-byte loads of
 // points per row) and the pixel right of them (the corners b / e of its last cell), which the neighbouring lane has requested too: those
