@@ -1,6 +1,6 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
-// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces).
+// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals).
 #include "sl3d_capi_internal.h"
 
 typedef sl3d_ctx::Scan Scan;
@@ -475,6 +475,7 @@ static int ensure_mesh_buffers(sl3d_ctx *x)
     return SL3D_OK;
 }
 
+// (n_faces: a call without face counts passes n_vertices twice)
 static int check_mesh_args(sl3d_ctx *x, int first_view, int n_views, float max_edge, const int64_t *n_vertices, const int64_t *n_faces)
 {
     const int rc = check_view(x, first_view, n_views);
@@ -531,6 +532,62 @@ try {
     rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
     if (!rc) rc = download_clamped(x, faces, m.faces, m.view_stride_faces, n_views, n_faces, face_capacity);
     if (rc) return rc;
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// ---- vertex normals of those meshes (sl3d_mesh.h: the definition; sl3d_mesh_normals.hip: the kernels) -----------------------------
+static int ensure_normal_buffers(sl3d_ctx *x)
+{
+    if (x->normals_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, nc = (size_t)mesh_chunks(P);
+    int rc = SL3D_OK;
+    if (!x->d_nrm_cnt) rc = dev_alloc(x, &x->d_nrm_cnt, mv * nc);
+    if (!rc && !x->d_nrm_off) rc = dev_alloc(x, &x->d_nrm_off, mv * nc);
+    if (!rc && !x->d_nrm_tot) rc = dev_alloc(x, &x->d_nrm_tot, mv);
+    if (!rc && !x->d_normals) rc = dev_alloc(x, &x->d_normals, mv * P.px_view_stride * 3);
+    if (rc) return rc;
+    x->normals_ready = true;
+    return SL3D_OK;
+}
+
+// Count, scan (k_compact_scan over the count array of every view), gather: three launches, one read-back of the total per view.  Reads the
+// dense result only: nothing the mesh call or the compactions handed out is touched.
+extern "C" int sl3d_mesh_normals(sl3d_ctx *x, int first_view, int n_views, float max_edge, const float **device_normals, size_t *view_stride_points,
+                                 int64_t *n_vertices)
+try {
+    int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_vertices);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    rc = ensure_normal_buffers(x);
+    if (rc) return rc;
+    rc = launched(x, launch_mesh_normals(P, first_view, n_views, max_edge, x->d_nrm_cnt, x->d_nrm_off, x->d_nrm_tot, x->d_normals, P.px_view_stride,
+                                         x->stream));
+    if (rc) return rc;
+    std::vector<unsigned long long> t((size_t)n_views);
+    HIPCHK(x, hipMemcpyAsync(t.data(), x->d_nrm_tot + first_view, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    for (int v = 0; v < n_views; v++) n_vertices[v] = (int64_t)t[(size_t)v];
+    if (device_normals) *device_normals = x->d_normals + 3 * (size_t)first_view * P.px_view_stride;
+    if (view_stride_points) *view_stride_points = P.px_view_stride;
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: the normals of the views back to back
+extern "C" int sl3d_get_mesh_normals(sl3d_ctx *x, int first_view, int n_views, float max_edge, float *normals, int64_t vertex_capacity,
+                                     int64_t *n_vertices)
+try {
+    int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_vertices);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const float *dev = nullptr;
+    size_t stride = 0;
+    rc = sl3d_mesh_normals(x, first_view, n_views, max_edge, &dev, &stride, n_vertices);
+    if (rc || (rc = download_clamped(x, normals, dev, stride, n_views, n_vertices, vertex_capacity))) return rc;
     SYNC_FOR_CALLER(x);
     return SL3D_OK;
 }

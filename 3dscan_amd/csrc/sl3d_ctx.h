@@ -103,6 +103,12 @@ struct sl3d_ctx {
     float *d_mesh_xyz = nullptr;
     size_t mesh_face_stride = 0;
     bool mesh_ready = false;                  // ensure_mesh_buffers ran to its end
+    // sl3d_mesh_normals (all allocated on first use, nothing shared with the mesh call): [max_views][mesh_chunks] valid pixels per chunk,
+    // their exclusive scan, [max_views] totals; the normals: [max_views][px_view_stride][3], a view's in the order of its cloud
+    unsigned *d_nrm_cnt = nullptr;
+    unsigned long long *d_nrm_off = nullptr, *d_nrm_tot = nullptr;
+    float *d_normals = nullptr;
+    bool normals_ready = false;               // ensure_normal_buffers ran to its end
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP
-// kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip).  Not part of the public ABI.
+// kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip).  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -221,6 +221,10 @@ int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int
 int mesh_chunks(const KParams &P);
 int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
                       unsigned long long *totals, int *faces, size_t face_stride, void *stream);
+// vertex normals of those meshes (sl3d_mesh_normals.hip): counts / offsets: [max_views][chunks] valid pixels per chunk and their exclusive
+// scan, totals: [max_views], normals: [max_views][normal_stride][3], view v's in the order of its compacted cloud
+int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
+                        unsigned long long *totals, float *normals, size_t normal_stride, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

@@ -1,7 +1,7 @@
 // sl3d_mesh.h -- the arithmetic of the mesh stage (sl3d_mesh_views): which triangles one cell of the organized point grid gives.
 //
-// Shared by k_mesh_count / k_mesh_emit (sl3d_mesh.hip) and by the CPU check the test suite runs over whole frames
-// (tests/native/mesh_check.cpp): plain C, no HIP types.  The reference has no mesh stage (its user meshed the PLY of stage 8 in
+// Shared by k_mesh_count / k_mesh_emit (sl3d_mesh.hip), k_mesh_normals (sl3d_mesh_normals.hip) and by the CPU checks the test suite
+// runs over whole frames (tests/native/mesh_check.cpp, mesh_normals_check.cpp): plain C, no HIP types.  The reference has no mesh stage (its user meshed the PLY of stage 8 in
 // MeshLab); the definition is this library's own and every test checks it bit for bit:
 //
 //   cell (r, c), r in [0, H-1), c in [0, W-1): corners a = (r, c), b = (r, c+1), d = (r+1, c), e = (r+1, c+1)
@@ -11,13 +11,27 @@
 //                    a-e: candidates (a, d, e) then (a, e, b);   b-d: candidates (a, d, b) then (b, d, e)
 //   3 valid corners: e missing (a, d, b); a missing (b, d, e); b missing (a, d, e); d missing (a, e, b)
 //   a candidate is a face iff its three edges are short.  All four shapes have the same orientation in pixel space.
+//
+// Vertex normals (sl3d_mesh_normals; k_mesh_normals in sl3d_mesh_normals.hip, tests/native/mesh_normals_check.cpp), equally exact:
+//   face (i, j, k) with points p, q, s widened to double: u = q - p, v = s - p,
+//        fn = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x), every operation one IEEE double operation, no contraction
+//   vertex at pixel (r, c): acc = +0, then acc += fn for every face that contains it in face-list order: cells (r-1, c-1), (r-1, c),
+//        (r, c-1), (r, c), within a cell the cell's face order -- at most 8 faces
+//   ss = (acc.x*acc.x + acc.y*acc.y) + acc.z*acc.z;  0 < ss < +inf: n = (float)(acc / sqrt(ss)) per component (sqrt and division
+//        correctly rounded in double, the cast to nearest even), else n = +0 (no face, degenerate faces, overflow, NaN)
+//   for points (col, row, f(col, row)) this is (f_x, f_y, -1) / |..|: the orientation follows the faces, nothing is flipped
 #pragma once
+#include <math.h>
 
 #ifdef __HIPCC__
 #define SL3D_MESH_FN __host__ __device__ __forceinline__
+#define SL3D_MESH_UNROLL _Pragma("unroll")
 #else
 #define SL3D_MESH_FN static inline
+#define SL3D_MESH_UNROLL
 #endif
+
+#define MESH_CHUNK 1024  // pixels of a row per block of the mesh kernels: 256 lanes x one quad
 
 // corner numbers of a cell, also the bit numbers of `vbits`
 #define MESH_A 0
@@ -83,3 +97,71 @@ SL3D_MESH_FN unsigned mesh_cell(unsigned vbits, const float *a, const float *b, 
 
 // corner number j (0..2) of face k (0..1) of a mesh_cell result
 SL3D_MESH_FN unsigned mesh_corner(unsigned cell, int k, int j) { return (cell >> (2 + 6 * k + 2 * j)) & 3u; }
+
+// ---- vertex normals ------------------------------------------------------------------------------------------------------------------
+// the area-weighted normal of the face (p, q, s), in the order the face list gives its vertices
+SL3D_MESH_FN void mesh_face_vector(const float *p, const float *q, const float *s, double out[3])
+{
+    const double ux = (double)q[0] - (double)p[0], uy = (double)q[1] - (double)p[1], uz = (double)q[2] - (double)p[2];
+    const double vx = (double)s[0] - (double)p[0], vy = (double)s[1] - (double)p[1], vz = (double)s[2] - (double)p[2];
+    out[0] = uy * vz - uz * vy;
+    out[1] = uz * vx - ux * vz;
+    out[2] = ux * vy - uy * vx;
+}
+
+SL3D_MESH_FN void mesh_normal_from_sum(const double acc[3], float out[3])
+{
+    const double ss = (acc[0] * acc[0] + acc[1] * acc[1]) + acc[2] * acc[2];
+    out[0] = out[1] = out[2] = 0.0f;
+    if (ss > 0.0 && ss < (double)INFINITY) {  // (false for NaN)
+        const double len = sqrt(ss);
+        out[0] = (float)(acc[0] / len), out[1] = (float)(acc[1] / len), out[2] = (float)(acc[2] / len);
+    }
+}
+
+// one of two points by a flag (selects on values already loaded, no indexed array: the kernel keeps the points in registers)
+SL3D_MESH_FN void mesh_pick(int first, const float *x, const float *y, float out[3])
+{
+    const float x0 = x[0], x1 = x[1], x2 = x[2], y0 = y[0], y1 = y[1], y2 = y[2];
+    out[0] = first ? x0 : y0, out[1] = first ? x1 : y1, out[2] = first ? x2 : y2;
+}
+
+// The cells of one cell row under a quad's 6 columns, left to right: the cell whose corner a is column j (0..4) adds its faces' vectors
+// to the sums of its corners `left` (pixel j - 1 of the quad) and `right` (pixel j).  vu / vl: valid bits of the cells' upper / lower
+// pixel row, bit j = column j; up / lo: the points of those rows (18 floats each; those of invalid pixels are not looked at).
+SL3D_MESH_FN void mesh_cell_row_sums(unsigned vu, unsigned vl, const float *up, const float *lo, unsigned left, unsigned right, double thr2,
+                                     double acc[12])
+{
+    SL3D_MESH_UNROLL
+    for (int j = 0; j < 5; j++) {
+        const float *a = up + 3 * j, *b = a + 3, *d = lo + 3 * j, *e = d + 3;
+        const unsigned cell = mesh_cell((vu >> j & 3u) | (vl >> j & 3u) << 2, a, b, d, e, thr2);
+        SL3D_MESH_UNROLL
+        for (int f = 0; f < 2; f++)
+            if ((int)(cell & 3u) > f) {
+                const unsigned c0 = mesh_corner(cell, f, 0), c1 = mesh_corner(cell, f, 1), c2 = mesh_corner(cell, f, 2);
+                // the four shapes mesh_cell gives -- (a,d,e) (a,e,b) (a,d,b) (b,d,e) -- start at a or b, go on to d or e and end at e or b
+                float p[3], q[3], s[3];
+                double fn[3];
+                mesh_pick(c0 == MESH_A, a, b, p);
+                mesh_pick(c1 == MESH_D, d, e, q);
+                mesh_pick(c2 == MESH_E, e, b, s);
+                mesh_face_vector(p, q, s, fn);
+                const unsigned has = 1u << c0 | 1u << c1 | 1u << c2;
+                if (j >= 1 && (has >> left & 1u)) acc[3 * j - 3] += fn[0], acc[3 * j - 2] += fn[1], acc[3 * j - 1] += fn[2];
+                if (j <= 3 && (has >> right & 1u)) acc[3 * j] += fn[0], acc[3 * j + 1] += fn[1], acc[3 * j + 2] += fn[2];
+            }
+    }
+}
+
+// The face-vector sums of one quad: pixels c0 .. c0 + 3 of row r.  v[t], t = 0..2: the valid bits of row r - 1 + t, bit j = pixel
+// c0 - 1 + j (j = 0..5; 0 outside the window); pt / pm / pb: the points of those 6 pixels of rows r - 1 / r / r + 1.  acc[3 * k ..]: the
+// sum of pixel c0 + k.  The 5 cells of row r - 1 (the quad's pixels are their corners d / e), then the 5 of row r (corners a / b): for
+// every pixel that is the order (r-1, c-1), (r-1, c), (r, c-1), (r, c) of the definition.
+SL3D_MESH_FN void mesh_quad_sums(const unsigned v[3], const float *pt, const float *pm, const float *pb, double thr2, double acc[12])
+{
+    SL3D_MESH_UNROLL
+    for (int i = 0; i < 12; i++) acc[i] = 0.0;
+    mesh_cell_row_sums(v[0], v[1], pt, pm, MESH_D, MESH_E, thr2, acc);
+    mesh_cell_row_sums(v[1], v[2], pm, pb, MESH_A, MESH_B, thr2, acc);
+}

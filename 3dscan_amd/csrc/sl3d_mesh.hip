@@ -15,8 +15,6 @@
 
 namespace sl3d {
 
-#define MESH_CHUNK 1024  // pixels of a row per block: 256 lanes x one quad
-
 // the lane's 4 cells (a = pixel c0 + k of row r): v0 / v1 = valid bits of pixels c0 .. c0 + 4 of rows r / r + 1 (bit 4: the pixel right
 // of the quad; 0 beyond the window), cell[k] = mesh_cell of cell k.  row0 / pts0: row r of the valid / points plane.
 __device__ __forceinline__ void mesh_lane(const uint8_t *__restrict__ row0, const float *__restrict__ pts0, int W, int pitch, int c0, bool next_row,

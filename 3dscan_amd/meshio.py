@@ -6,14 +6,20 @@ standard layout every mesh tool reads."""
 import numpy as np
 
 
-def write_ply(path, xyz, faces=None, rgb=None, binary=True):
-    """Standard PLY: `element vertex` with float x y z (+ uchar red green blue when rgb is given: (n, 3) uint8, same order as xyz) and,
+def write_ply(path, xyz, faces=None, rgb=None, binary=True, normals=None):
+    """Standard PLY: `element vertex` with float x y z (+ float nx ny nz directly after them when normals is given: (n, 3) float32, what
+    Scanner.mesh_normals returns; + uchar red green blue when rgb is given: (n, 3) uint8; both in the order of xyz) and,
     when faces is given ((m, 3) integer indices into xyz), `element face` with `property list uchar int vertex_indices`.
     binary: binary_little_endian 1.0, else ascii 1.0 (floats written with 9 significant digits: they read back exactly)."""
     v = np.ascontiguousarray(xyz, dtype=np.float32)
     if v.ndim != 2 or v.shape[1] != 3:
         raise ValueError(f"xyz must have shape (n, 3), not {v.shape}")
     n = v.shape[0]
+    nrm = None
+    if normals is not None:
+        nrm = np.asarray(normals)
+        if nrm.shape != (n, 3) or nrm.dtype != np.float32:
+            raise ValueError(f"normals must be float32 of shape ({n}, 3), not {nrm.dtype} {nrm.shape}")
     c = None
     if rgb is not None:
         c = np.asarray(rgb)
@@ -29,6 +35,8 @@ def write_ply(path, xyz, faces=None, rgb=None, binary=True):
         f = f.astype("<i4")
     head = ["ply", "format binary_little_endian 1.0" if binary else "format ascii 1.0", f"element vertex {n}",
             "property float x", "property float y", "property float z"]
+    if nrm is not None:
+        head += ["property float nx", "property float ny", "property float nz"]
     if c is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue"]
     if f is not None:
@@ -37,11 +45,15 @@ def write_ply(path, xyz, faces=None, rgb=None, binary=True):
     with open(path, "wb") as out:
         out.write(("\n".join(head) + "\n").encode("ascii"))
         if binary:
-            if c is None:
+            if c is None and nrm is None:
                 out.write(v.astype("<f4").tobytes())
             else:
-                rec = np.empty(n, dtype=[("p", "<f4", 3), ("c", "u1", 3)])
-                rec["p"], rec["c"] = v, c
+                rec = np.empty(n, dtype=[("p", "<f4", 3)] + ([("n", "<f4", 3)] if nrm is not None else []) + ([("c", "u1", 3)] if c is not None else []))
+                rec["p"] = v
+                if nrm is not None:
+                    rec["n"] = nrm
+                if c is not None:
+                    rec["c"] = c
                 out.write(rec.tobytes())
             if f is not None:
                 rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", 3)])
@@ -50,7 +62,7 @@ def write_ply(path, xyz, faces=None, rgb=None, binary=True):
         else:
             lines = []
             for k in range(n):
-                t = " ".join(f"{float(x):.9g}" for x in v[k])
+                t = " ".join(f"{float(x):.9g}" for x in (v[k] if nrm is None else np.concatenate([v[k], nrm[k]])))
                 lines.append(t if c is None else f"{t} {c[k, 0]} {c[k, 1]} {c[k, 2]}")
             if f is not None:
                 lines += [f"3 {a} {b} {d}" for a, b, d in f.tolist()]

@@ -27,7 +27,7 @@ ABI_SYMBOLS = (
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
-    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
+    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
     "sl3d_get_device_buffers", "sl3d_download", "sl3d_download_2d",
     "sl3d_group_create", "sl3d_group_destroy", "sl3d_group_last_error", "sl3d_group_size", "sl3d_group_stripe", "sl3d_group_transport",
     "sl3d_group_set_calibration", "sl3d_group_set_mask", "sl3d_group_set_frames", "sl3d_group_run", "sl3d_group_gather",
@@ -110,6 +110,12 @@ def load_library(path=None):
         L.sl3d_mesh_views.argtypes = [vp, i, i, C.c_float, C.POINTER(Mesh), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.sl3d_get_meshes.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     except AttributeError:   # a build before 0.8.0 under SL3D_LIB: everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        L.sl3d_mesh_normals.argtypes = [vp, i, i, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
+        L.sl3d_get_mesh_normals.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, C.POINTER(C.c_int64)]
+    except AttributeError:   # a build before 0.9.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -608,6 +614,32 @@ class Scanner:
     def mesh(self, max_edge, view=0):
         """(xyz, faces) of one view (meshes)."""
         return self.meshes(max_edge, view, 1)[0]
+
+    def mesh_normals_device(self, max_edge, first_view=0, n_views=1):
+        """sl3d_mesh_normals: the vertex normals of the meshes of a batch of views left in HBM; returns (device address, stride between
+        the views in float triples, vertex counts)."""
+        dev, stride, nv = C.c_void_p(), C.c_size_t(), (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_mesh_normals(self._h, first_view, n_views, float(max_edge), C.byref(dev), C.byref(stride), nv), "sl3d_mesh_normals")
+        return dev.value, stride.value, [int(c) for c in nv]
+
+    def meshes_normals(self, max_edge, first_view=0, n_views=1):
+        """The vertex normals of meshes(max_edge, first_view, n_views): a list of (n_k, 3) float32 arrays, row i the unit normal of
+        vertex i -- the normalised sum of the area-weighted normals of the faces around it, zero for a vertex in no face.  The
+        orientation follows the faces; nothing is flipped towards the camera (include/sl3d.h: the exact definition)."""
+        nv = (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_get_mesh_normals(self._h, first_view, n_views, float(max_edge), None, 0, nv), "sl3d_get_mesh_normals")
+        tv = sum(nv)
+        flat = np.empty((tv, 3), dtype=np.float32)
+        self._chk(self.L.sl3d_get_mesh_normals(self._h, first_view, n_views, float(max_edge), flat.ctypes.data, tv, nv), "sl3d_get_mesh_normals")
+        out, off = [], 0
+        for n in nv:
+            out.append(flat[off:off + n])
+            off += n
+        return out
+
+    def mesh_normals(self, max_edge, view=0):
+        """(n, 3) float32 normals of the vertices of mesh(max_edge, view) (meshes_normals)."""
+        return self.meshes_normals(max_edge, view, 1)[0]
 
     def set_texture(self, bgr, view=0):
         """The colour image save_point_cloud() takes r,g,b from: (H, W, 3) uint8, B,G,R order (cvLoadImage)."""

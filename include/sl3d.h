@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.8.0"
+#define SL3D_VERSION_STRING "0.9.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -391,7 +391,7 @@ int sl3d_get_clouds(sl3d_ctx *ctx, int first_view, int n_views, float *xyz, int6
  * Works wherever sl3d_compact_views works (every context with a dense result: timed, parity, windows); ids are relative to the
  * view's own cloud; points, valid and whatever sl3d_compact* / sl3d_run_clouds handed out are not modified.
  * Not covered: groups (sl3d_group_*: the cells across a stripe seam need the neighbour's row), a mesh straight from the segments of
- * sl3d_run_clouds, registration of meshes, vertex normals, the drop-in shim (the reference has nothing to mirror). */
+ * sl3d_run_clouds, registration of meshes, the drop-in shim (the reference has nothing to mirror).  Vertex normals: below (0.9.0). */
 typedef struct sl3d_mesh {            /* device-resident, valid until the next sl3d_mesh_views / sl3d_get_meshes on this context */
     const float *xyz;                 /* view first_view+k: n_vertices[k] points  at xyz   + 3*k*view_stride_points */
     const int32_t *faces;             /* view first_view+k: n_faces[k] id triples at faces + 3*k*view_stride_faces  */
@@ -404,6 +404,33 @@ int sl3d_mesh_views(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, 
  * in faces (at most face_capacity triples in all); xyz / faces may be NULL; the per-view counts are always returned */
 int sl3d_get_meshes(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, float *xyz, int64_t vertex_capacity, int32_t *faces,
                     int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces);
+
+/* ---- vertex normals of a view's mesh (0.9.0) ------------------------------------------------------------------------
+ * One normal per vertex of the mesh sl3d_mesh_views(first_view, n_views, max_edge) defines, computed on the device from the dense
+ * result alone (a vertex's faces lie in the four cells around its pixel: a gather, no atomics, no adjacency lists).  Exact:
+ *   face vector  face (i,j,k) in the order the face list gives its ids, points p,q,s widened to double: u = q-p, v = s-p,
+ *                fn = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x), every product and difference one IEEE double
+ *                operation, no contraction: the area-weighted face normal; every vertex of the face accumulates the same value
+ *   vertex sum   acc = (+0,+0,+0), then acc += fn for every face that contains the vertex, in the order of the view's face list: for
+ *                the vertex at pixel (r,c) the cells (r-1,c-1), (r-1,c), (r,c-1), (r,c), within a cell the cell's face order (<= 8 faces)
+ *   normal       ss = (acc.x*acc.x + acc.y*acc.y) + acc.z*acc.z; if 0 < ss < +inf: n = (float)(acc / sqrt(ss)) per component (sqrt and
+ *                division correctly rounded in double, the cast to nearest even); otherwise n = (+0,+0,+0): a vertex in no face,
+ *                degenerate faces, an overflow, a NaN or infinity under a valid pixel
+ *   orientation  follows the faces: for points (x,y,z) = (col, row, f(col,row)) the normal is (f_x, f_y, -1)/|..|.  Nothing is flipped
+ *                towards the camera: that choice is the caller's.
+ *   output       one float triple per vertex in vertex-id order (the order of sl3d_get_cloud); deterministic as the faces are.
+ * Works wherever sl3d_mesh_views works (timed and parity contexts, windows: cells end at the window).  The normals live in a buffer of
+ * their own (allocated on first use): points, valid, the clouds of sl3d_compact* / sl3d_run_clouds and the device mesh of the last
+ * sl3d_mesh_views are not modified and stay valid.  A NaN or non-positive max_edge, a bad view range or NULL n_vertices:
+ * SL3D_E_INVALID_ARG, and nothing on the device changes.  Not covered: as for the mesh. */
+/* normals of the meshes sl3d_mesh_views(first_view, n_views, max_edge) defines; view first_view+k: n_vertices[k] float triples at
+ * *device_normals + 3*k*(*view_stride_points), valid until the next sl3d_mesh_normals / sl3d_get_mesh_normals on this context
+ * (three launches, one read-back of the counts; device_normals / view_stride_points may be NULL) */
+int sl3d_mesh_normals(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, const float **device_normals,
+                      size_t *view_stride_points, int64_t *n_vertices);
+/* the same with a host copy, back to back, at most vertex_capacity triples in all; normals may be NULL (counts only) */
+int sl3d_get_mesh_normals(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, float *normals, int64_t vertex_capacity,
+                          int64_t *n_vertices);
 
 /* register_point_clouds(unsigned, float tx, float ty, float tz, float rot_step)  9/register_point_clouds.cpp:23:
  * the compacted clouds of views [first_view, first_view+n_views) are rotated about the Y axis through (tx,ty,tz)

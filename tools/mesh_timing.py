@@ -3,7 +3,9 @@ max_edge = +inf and a value at the median of the candidates' edge lengths.  Afte
 (every call ends in its own synchronise), per view; beside it the bytes the design moves (from the shapes and the returned counts), bytes
 over time against the 6.3 TB/s achievable and the 8 TB/s peak, and -- for scale -- sl3d_compact_views on the same views (same reads,
 vertices only).  One JSON line.  Under `rocprofv3 --kernel-trace --stats` (a run of its own) the kernel table gives the per-kernel split.
-usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3]"""
+--normals: the normals leg instead -- sl3d_mesh_normals over the same cases, sl3d_mesh_views timed in the same process in alternating
+blocks of calls so that both see the same clocks, the ratio per case (profiles/mesh_normals_timing.json).
+usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals]"""
 import argparse
 import importlib
 import json
@@ -43,17 +45,41 @@ def clock(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def clock_alternating(fa, fb, reps, blocks=4):
+    """reps back-to-back calls of each, in `blocks` alternating blocks after one warm-up of both: seconds per call of fa, of fb"""
+    for _ in range(20):
+        fa()
+        fb()
+    ta = tb = 0.0
+    per = max(1, reps // blocks)
+    for _ in range(blocks):
+        t0 = time.perf_counter()
+        for _ in range(per):
+            fa()
+        t1 = time.perf_counter()
+        for _ in range(per):
+            fb()
+        ta, tb = ta + (t1 - t0), tb + (time.perf_counter() - t1)
+    return ta / (per * blocks), tb / (per * blocks)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--only", default="")
+    ap.add_argument("--normals", action="store_true")
     a = ap.parse_args()
     syn = importlib.import_module("3dscan_amd.synth")
     scm = importlib.import_module("3dscan_amd.scanner")
-    out = {"tool": "mesh_timing", "reps": a.reps, "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
-           "bytes_note": "design = valid 4x (compaction count + scatter, mesh count + emit; the second row of a block counted as an L2 hit) + "
-                         "points 12 B per vertex 3x (scatter, count, emit) + 12 B per vertex and per face written; algorithmic = 13 B/px read once "
-                         "+ 12 B per vertex and per face written", "runs": []}
+    if a.normals:
+        out = {"tool": "mesh_timing --normals", "reps": a.reps, "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
+               "bytes_note": "design = valid 2x (count; the gather's rows r-1 and r+1 counted as L2 hits) + points 12 B per vertex read once "
+                             "(rows r-1 / r+1 likewise) + 12 B per vertex written", "runs": []}
+    else:
+        out = {"tool": "mesh_timing", "reps": a.reps, "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
+               "bytes_note": "design = valid 4x (compaction count + scatter, mesh count + emit; the second row of a block counted as an L2 hit) + "
+                             "points 12 B per vertex 3x (scatter, count, emit) + 12 B per vertex and per face written; algorithmic = 13 B/px read once "
+                             "+ 12 B per vertex and per face written", "runs": []}
     for name, (W, H, PW, PH, V) in CONFIGS.items():
         if a.only and a.only != name:
             continue
@@ -70,8 +96,21 @@ def main():
                 st = {}
                 np_mesh(np.ascontiguousarray(xyz[r0:r0 + 200]), np.ascontiguousarray(valid[r0:r0 + 200]), float("inf"), st)
                 med = float(np.float32(np.sqrt(np.median(st["len2"]))))
-                t_compact = clock(lambda: sc.compact_views(0, V), a.reps)
+                t_compact = 0.0 if a.normals else clock(lambda: sc.compact_views(0, V), a.reps)
                 for label, max_edge in (("inf", float("inf")), ("median", med)):
+                    if a.normals:
+                        _, nv, nf = sc.mesh_device(max_edge, 0, V)
+                        assert sc.mesh_normals_device(max_edge, 0, V)[2] == nv
+                        tn, tm = clock_alternating(lambda: sc.mesh_normals_device(max_edge, 0, V), lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                        design = 2 * W * H * V + 24 * sum(nv)
+                        out["runs"].append({
+                            "config": name, "size": [W, H], "views": V, "selection": sel, "max_edge": label, "max_edge_mm": None if label == "inf" else round(med, 6),
+                            "vertices_per_view": round(sum(nv) / V), "faces_per_view": round(sum(nf) / V),
+                            "normals_us_per_call": round(tn * 1e6, 1), "normals_us_per_view": round(tn * 1e6 / V, 2),
+                            "mesh_us_per_call": round(tm * 1e6, 1), "normals_over_mesh": round(tn / tm, 2),
+                            "design_bytes_per_view": design // V, "design_tbs": round(design / tn / 1e12, 3),
+                            "design_over_achievable": round(design / tn / 1e12 / ACHIEVABLE_TBS, 3)})
+                        continue
                     _, nv, nf = sc.mesh_device(max_edge, 0, V)
                     t = clock(lambda: sc.mesh_device(max_edge, 0, V), a.reps)
                     design = 4 * W * H * V + 48 * sum(nv) + 12 * sum(nf)
