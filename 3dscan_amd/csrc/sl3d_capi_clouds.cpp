@@ -1,6 +1,8 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
-// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals).
+// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals).  Every consumer of a dense result
+// keeps its counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, read_totals
+// brings its totals to the host.
 #include "sl3d_capi_internal.h"
 
 typedef sl3d_ctx::Scan Scan;
@@ -14,11 +16,8 @@ static int ensure_cloud_buffers(sl3d_ctx *x)
     KParams &P = x->P;
     const size_t mv = (size_t)x->cfg.max_views;
     int rc = SL3D_OK;
-    const size_t nb = (P.px_view_stride + 1023) / 1024;
     if (!x->d_clouds) rc = dev_alloc(x, &x->d_clouds, mv * P.px_view_stride * 3);
-    if (!rc && !x->blk_all.cnt) rc = dev_alloc(x, &x->blk_all.cnt, mv * nb);
-    if (!rc && !x->blk_all.off) rc = dev_alloc(x, &x->blk_all.off, mv * nb);
-    if (!rc && !x->blk_all.tot) rc = dev_alloc(x, &x->blk_all.tot, mv);
+    if (!rc) rc = ensure_scratch(x, x->blk_all, mv * compact_blocks(P), mv);
     if (rc) return rc;
     P.n_tiles = fused_tiles(P);
     P.n_segs = 4 * P.n_tiles;
@@ -128,6 +127,20 @@ static int download_clamped(sl3d_ctx *x, void *host, const void *dev, size_t str
         if (n <= 0) continue;
         HIPCHK_DRAIN(x, hipMemcpyAsync((char *)host + 12 * off, (const char *)dev + 12 * (size_t)v * stride, (size_t)n * 12, hipMemcpyDeviceToHost, x->stream));
         off += n;
+    }
+    return SL3D_OK;
+}
+
+// The totals a launch over views [first_view, first_view + n_views) left in tot (k per view: tot[k * v + j]) reach the host: word 0 of
+// view first_view + v widened into n0[v], word 1 (k == 2) into n1[v].  Synchronises for the caller
+static int read_totals(sl3d_ctx *x, const unsigned long long *tot, int k, int first_view, int n_views, int64_t *n0, int64_t *n1 = nullptr)
+{
+    std::vector<unsigned long long> t((size_t)k * (size_t)n_views);
+    HIPCHK(x, hipMemcpyAsync(t.data(), tot + (size_t)k * first_view, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    for (int v = 0; v < n_views; v++) {
+        n0[v] = (int64_t)t[(size_t)k * v];
+        if (n1) n1[v] = (int64_t)t[(size_t)k * v + 1];
     }
     return SL3D_OK;
 }
@@ -257,10 +270,8 @@ try {
     rc = launched(x, launch_compact_views(x->P, view, 1, x->blk_one, x->d_cloud, tex ? x->d_texture + (size_t)view * x->P.px_view_stride * 3 : nullptr,
                                           x->d_cloud_rgb, x->stream));
     if (rc) return rc;
-    unsigned long long n = 0;
-    HIPCHK(x, hipMemcpyAsync(&n, x->blk_one.tot + view, sizeof n, hipMemcpyDeviceToHost, x->stream));
-    SYNC_FOR_CALLER(x);
-    *count = (int64_t)n;
+    rc = read_totals(x, x->blk_one.tot, 1, view, 1, count);
+    if (rc) return rc;
     if (device_xyz) *device_xyz = x->d_cloud;
     return SL3D_OK;
 }
@@ -306,10 +317,8 @@ try {
     rc = launched(x, launch_compact_views(P, first_view, n_views, x->blk_all, x->d_packed + 3 * (size_t)first_view * P.px_view_stride, nullptr, nullptr,
                                           x->stream));
     if (rc) return rc;
-    std::vector<unsigned long long> t((size_t)n_views);
-    HIPCHK(x, hipMemcpyAsync(t.data(), x->blk_all.tot + first_view, sizeof(unsigned long long) * (size_t)n_views, hipMemcpyDeviceToHost, x->stream));
-    SYNC_FOR_CALLER(x);
-    for (int v = 0; v < n_views; v++) counts[v] = (int64_t)t[(size_t)v];
+    rc = read_totals(x, x->blk_all.tot, 1, first_view, n_views, counts);
+    if (rc) return rc;
     if (device_xyz) *device_xyz = x->d_packed + 3 * (size_t)first_view * P.px_view_stride;
     if (view_stride_points) *view_stride_points = P.px_view_stride;
     return SL3D_OK;
@@ -459,15 +468,10 @@ static int ensure_mesh_buffers(sl3d_ctx *x)
 {
     if (x->mesh_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
     const KParams &P = x->P;
-    const size_t mv = (size_t)x->cfg.max_views, nb = (P.px_view_stride + 1023) / 1024, nc = (size_t)mesh_chunks(P);
+    const size_t mv = (size_t)x->cfg.max_views;
     x->mesh_face_stride = std::max<size_t>(1, 2 * (size_t)(P.W - 1) * (size_t)(P.H - 1));
-    int rc = SL3D_OK;
-    if (!x->d_mesh_cnt) rc = dev_alloc(x, &x->d_mesh_cnt, mv * 2 * nc);
-    if (!rc && !x->d_mesh_off) rc = dev_alloc(x, &x->d_mesh_off, mv * 2 * nc);
-    if (!rc && !x->d_mesh_tot) rc = dev_alloc(x, &x->d_mesh_tot, mv * 2);
-    if (!rc && !x->blk_mesh.cnt) rc = dev_alloc(x, &x->blk_mesh.cnt, mv * nb);
-    if (!rc && !x->blk_mesh.off) rc = dev_alloc(x, &x->blk_mesh.off, mv * nb);
-    if (!rc && !x->blk_mesh.tot) rc = dev_alloc(x, &x->blk_mesh.tot, mv);
+    int rc = ensure_scratch(x, x->chk_mesh, mv * 2 * (size_t)mesh_chunks(P), mv * 2);
+    if (!rc) rc = ensure_scratch(x, x->blk_mesh, mv * compact_blocks(P), mv);
     if (!rc && !x->d_mesh_xyz) rc = dev_alloc(x, &x->d_mesh_xyz, mv * P.px_view_stride * 3);
     if (!rc && !x->d_mesh_faces) rc = dev_alloc(x, &x->d_mesh_faces, mv * x->mesh_face_stride * 3);
     if (rc) return rc;
@@ -499,16 +503,9 @@ try {
     float *xyz = x->d_mesh_xyz + 3 * (size_t)first_view * P.px_view_stride;
     rc = launched(x, launch_compact_views(P, first_view, n_views, x->blk_mesh, xyz, nullptr, nullptr, x->stream));
     if (rc) return rc;
-    rc = launched(x, launch_mesh_views(P, first_view, n_views, max_edge, x->d_mesh_cnt, x->d_mesh_off, x->d_mesh_tot, x->d_mesh_faces,
-                                       x->mesh_face_stride, x->stream));
+    rc = launched(x, launch_mesh_views(P, first_view, n_views, max_edge, x->chk_mesh, x->d_mesh_faces, x->mesh_face_stride, x->stream));
+    if (!rc) rc = read_totals(x, x->chk_mesh.tot, 2, first_view, n_views, n_vertices, n_faces);
     if (rc) return rc;
-    std::vector<unsigned long long> t(2 * (size_t)n_views);
-    HIPCHK(x, hipMemcpyAsync(t.data(), x->d_mesh_tot + 2 * (size_t)first_view, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
-    SYNC_FOR_CALLER(x);
-    for (int v = 0; v < n_views; v++) {
-        n_vertices[v] = (int64_t)t[2 * (size_t)v];
-        n_faces[v] = (int64_t)t[2 * (size_t)v + 1];
-    }
     if (device_mesh) {
         device_mesh->xyz = xyz;
         device_mesh->faces = x->d_mesh_faces + 3 * (size_t)first_view * x->mesh_face_stride;
@@ -542,11 +539,8 @@ static int ensure_normal_buffers(sl3d_ctx *x)
 {
     if (x->normals_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
     const KParams &P = x->P;
-    const size_t mv = (size_t)x->cfg.max_views, nc = (size_t)mesh_chunks(P);
-    int rc = SL3D_OK;
-    if (!x->d_nrm_cnt) rc = dev_alloc(x, &x->d_nrm_cnt, mv * nc);
-    if (!rc && !x->d_nrm_off) rc = dev_alloc(x, &x->d_nrm_off, mv * nc);
-    if (!rc && !x->d_nrm_tot) rc = dev_alloc(x, &x->d_nrm_tot, mv);
+    const size_t mv = (size_t)x->cfg.max_views;
+    int rc = ensure_scratch(x, x->chk_nrm, mv * (size_t)mesh_chunks(P), mv);
     if (!rc && !x->d_normals) rc = dev_alloc(x, &x->d_normals, mv * P.px_view_stride * 3);
     if (rc) return rc;
     x->normals_ready = true;
@@ -564,13 +558,9 @@ try {
     const KParams &P = x->P;
     rc = ensure_normal_buffers(x);
     if (rc) return rc;
-    rc = launched(x, launch_mesh_normals(P, first_view, n_views, max_edge, x->d_nrm_cnt, x->d_nrm_off, x->d_nrm_tot, x->d_normals, P.px_view_stride,
-                                         x->stream));
+    rc = launched(x, launch_mesh_normals(P, first_view, n_views, max_edge, x->chk_nrm, x->d_normals, P.px_view_stride, x->stream));
+    if (!rc) rc = read_totals(x, x->chk_nrm.tot, 1, first_view, n_views, n_vertices);
     if (rc) return rc;
-    std::vector<unsigned long long> t((size_t)n_views);
-    HIPCHK(x, hipMemcpyAsync(t.data(), x->d_nrm_tot + first_view, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
-    SYNC_FOR_CALLER(x);
-    for (int v = 0; v < n_views; v++) n_vertices[v] = (int64_t)t[(size_t)v];
     if (device_normals) *device_normals = x->d_normals + 3 * (size_t)first_view * P.px_view_stride;
     if (view_stride_points) *view_stride_points = P.px_view_stride;
     return SL3D_OK;

@@ -160,23 +160,19 @@ try {
     }
     const size_t V = (size_t)c.max_views;
     int rc;
-#define ALLOC(ptr, count)                                              \
-    if ((rc = dev_alloc(x, &(ptr), (count))) != SL3D_OK) {             \
+#define ALLOC_RC(call)                                                 \
+    if ((rc = (call)) != SL3D_OK) {                                    \
         g_create_err = x->err;                                         \
         return rc;                                                     \
     }
+#define ALLOC(ptr, count) ALLOC_RC(dev_alloc(x, &(ptr), (count)))
     ALLOC(x->d_frames, V * P.view_stride);
     ALLOC(x->d_mask, V * P.mask_view_stride);
     ALLOC(x->d_points, V * P.px_view_stride * 3);
     ALLOC(x->d_valid, V * P.px_view_stride);
     ALLOC(x->d_cal, 1);
-    {
-        const size_t nb = (P.px_view_stride + 1023) / 1024;
-        ALLOC(x->blk_one.cnt, nb);
-        ALLOC(x->blk_one.off, nb);
-        ALLOC(x->blk_one.tot, V);  // (a view's total at its own index, as in every CompactScratch)
-        ALLOC(x->d_cloud, P.px_view_stride * 3);
-    }
+    ALLOC_RC(ensure_scratch(x, x->blk_one, compact_blocks(P), V));  // (one slot; a view's total at its own index, as in every CompactScratch)
+    ALLOC(x->d_cloud, P.px_view_stride * 3);
     ALLOC(x->d_band, V * P.px_view_stride);
     ALLOC(x->d_mask_raw, P.mask_view_stride);
     x->mask_raw_slots = 1;
@@ -261,6 +257,7 @@ try {
 #endif
     CREATE_CHK(hipStreamSynchronize(x->stream));
 #undef ALLOC
+#undef ALLOC_RC
 #undef CREATE_CHK
     unwind.p = nullptr;
     *out = x;

@@ -34,6 +34,17 @@ inline int dev_alloc(sl3d_ctx *c, T **p, size_t count)
     return SL3D_OK;
 }
 
+// allocates what a scratch of `counts` counts (and as many scanned offsets) and `totals` totals still lacks: a set-up that failed half way
+// goes on from there at the next call, nothing is allocated twice
+inline int ensure_scratch(sl3d_ctx *c, CompactScratch &s, size_t counts, size_t totals)
+{
+    int rc = SL3D_OK;
+    if (!s.cnt) rc = dev_alloc(c, &s.cnt, counts);
+    if (!rc && !s.off) rc = dev_alloc(c, &s.off, counts);
+    if (!rc && !s.tot) rc = dev_alloc(c, &s.tot, totals);
+    return rc;
+}
+
 SL3D_INTERNAL int launched(sl3d_ctx *x, int hip_err);   // a launch's hipError_t -> status (+ the context's error text)
 SL3D_INTERNAL int need_keep(sl3d_ctx *x);               // SL3D_E_STATE unless the context keeps the stage planes
 SL3D_INTERNAL int check_view(sl3d_ctx *x, int view, int n = 1);

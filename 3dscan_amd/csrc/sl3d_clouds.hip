@@ -4,10 +4,14 @@
 //   k_seg_scan / k_seg_close                             : the segmented clouds the fused kernel writes -> offsets, totals, contiguous
 //                                                          clouds, rotated on the way if asked (launch_seg_scan, launch_seg_close)
 //   k_register                                           : N3 over a contiguous cloud (launch_register)
+// The block idioms of the compaction kernels -- block sum, wave prefix, the waves in front, LDS flush -- live in sl3d_block.h, shared with
+// sl3d_mesh.hip and sl3d_mesh_normals.hip; the planes of a launch's first view: view_planes, blocks per view: compact_blocks
+// (sl3d_internal.h).  k_seg_scan / k_seg_close keep their own 16-wave, 64-bit forms here.
 // Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sl3d_block.h"
 #include "sl3d_internal.h"
 
 namespace sl3d {
@@ -28,10 +32,8 @@ __global__ __launch_bounds__(256) void k_compact_count(const uint8_t *valid, siz
     const size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
     unsigned w = base < n_px ? *(const unsigned *)(valid + base) : 0u;  // 4 valid bytes (0/1)
     unsigned c = __popc(w & 0x01010101u);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    BLOCK_SUM(c, s_cnt);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
 }
 
 // exclusive scan of n counts by a single 1024-thread block (n is a few thousand .. tens of thousands)
@@ -73,16 +75,8 @@ __global__ __launch_bounds__(256) void k_compact_scatter(const uint8_t *valid, c
     const unsigned w = base < n_px ? (*(const unsigned *)(valid + base) & 0x01010101u) : 0u;
     const unsigned c = __popc(w);
     // exclusive prefix of c over the block: wave scan by shuffles, then the 4 wave totals
-    unsigned incl = c;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(incl, off, 64);
-        if ((threadIdx.x & 63) >= off) incl += t;
-    }
-    if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned wave_base = 0;
-    for (int i = 0; i < (int)(threadIdx.x >> 6); i++) wave_base += s_wave[i];
-    const unsigned block_total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    const unsigned incl = wave_prefix(c, s_wave);
+    const unsigned wave_base = waves_before(s_wave, 0u), block_total = BLOCK_SUM_TOTAL(s_wave);
     unsigned local = wave_base + (incl - c);
     const unsigned long long block_off = block_offsets[blockIdx.x];
     if (w) {
@@ -106,8 +100,7 @@ __global__ __launch_bounds__(256) void k_compact_scatter(const uint8_t *valid, c
     }
     __syncthreads();
     // the block's segment of the cloud is contiguous: coalesced dword stores
-    float *dst = cloud + 3 * block_off;
-    for (unsigned i = threadIdx.x; i < 3 * block_total; i += 256) dst[i] = s_pts[i];
+    block_flush(cloud + 3 * block_off, s_pts, 3 * block_total);
 }
 
 // views [first_view, first_view + n_views): view first_view + k's compacted cloud goes to clouds + 3 * k * px_view_stride, its total to
@@ -117,13 +110,12 @@ int launch_compact_views(const KParams &P, int first_view, int n_views, const Co
                          uint8_t *rgb_out, void *stream)
 {
     const size_t n_px = P.px_view_stride;
-    const int nb = (int)((n_px + 1023) / 1024);
-    const uint8_t *valid = P.valid + (size_t)first_view * P.px_view_stride;
-    const float *points = P.points + 3 * (size_t)first_view * P.px_view_stride;
+    const int nb = (int)compact_blocks(P);
+    const ViewPlanes in = view_planes(P, first_view);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_compact_count, dim3(nb, n_views), dim3(256), 0, st, valid, n_px, s.cnt, n_px, nb);
+    hipLaunchKernelGGL(k_compact_count, dim3(nb, n_views), dim3(256), 0, st, in.valid, n_px, s.cnt, n_px, nb);
     hipLaunchKernelGGL(k_compact_scan, dim3(n_views), dim3(1024), 0, st, s.cnt, s.off, nb, s.tot + first_view);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb, n_views), dim3(256), 0, st, valid, points, n_px, s.off, clouds, texture, rgb_out, n_px, nb);
+    hipLaunchKernelGGL(k_compact_scatter, dim3(nb, n_views), dim3(256), 0, st, in.valid, in.points, n_px, s.off, clouds, texture, rgb_out, n_px, nb);
     return (int)hipGetLastError();
 }
 

@@ -92,21 +92,18 @@ struct sl3d_ctx {
         TOTAL_ONLY,  // a scanning consumer has left the total, the offsets are still unset
     };
     std::vector<Scan> scan_state;             // per view, after sl3d_run_clouds
-    // sl3d_mesh_views (all allocated on first use): [max_views][2][mesh_chunks] counts of valid pixels / faces per chunk, their
-    // exclusive scans, [max_views][2] totals; the faces: [max_views][mesh_face_stride][3] vertex ids into the view's cloud in d_mesh_xyz
-    // ([max_views][px_view_stride][3], written by launch_compact_views with block scratch of its own: nothing another call handed out
-    // is overwritten)
-    unsigned *d_mesh_cnt = nullptr;
-    unsigned long long *d_mesh_off = nullptr, *d_mesh_tot = nullptr;
+    // sl3d_mesh_views (all allocated on first use): the chunk scratch in its mesh form (CompactScratch, sl3d_internal.h); the faces:
+    // [max_views][mesh_face_stride][3] vertex ids into the view's cloud in d_mesh_xyz ([max_views][px_view_stride][3], written by
+    // launch_compact_views with block scratch of its own: nothing another call handed out is overwritten)
+    CompactScratch chk_mesh{};
     CompactScratch blk_mesh{};                // the block scratch of that compaction
     int32_t *d_mesh_faces = nullptr;
     float *d_mesh_xyz = nullptr;
     size_t mesh_face_stride = 0;
     bool mesh_ready = false;                  // ensure_mesh_buffers ran to its end
-    // sl3d_mesh_normals (all allocated on first use, nothing shared with the mesh call): [max_views][mesh_chunks] valid pixels per chunk,
-    // their exclusive scan, [max_views] totals; the normals: [max_views][px_view_stride][3], a view's in the order of its cloud
-    unsigned *d_nrm_cnt = nullptr;
-    unsigned long long *d_nrm_off = nullptr, *d_nrm_tot = nullptr;
+    // sl3d_mesh_normals (all allocated on first use, nothing shared with the mesh call): the chunk scratch in its normals form; the
+    // normals: [max_views][px_view_stride][3], a view's in the order of its cloud
+    CompactScratch chk_nrm{};
     float *d_normals = nullptr;
     bool normals_ready = false;               // ensure_normal_buffers ran to its end
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set

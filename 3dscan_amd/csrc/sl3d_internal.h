@@ -1,5 +1,7 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP
 // kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip).  Not part of the public ABI.
+// What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes, mesh_row_chunks);
+// the block idioms of their kernels are in sl3d_block.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -206,25 +208,38 @@ int launch_wrap(const KParams &P, int view, int axis, void *stream);
 int launch_unwrap(const KParams &P, int view, int axis, void *stream);
 int launch_corr(const KParams &P, int view, void *stream);
 int launch_tri(const KParams &P, const DevCal &C, int view, void *stream);
-// the scratch of one compaction (O1 / N2): counts of the valid pixels per 1024-pixel block, their exclusive scan -- one slot per view of
-// a launch -- and the views' totals, [max_views]: view v's at tot[v]
+// counts per block (or chunk) of a launch's views, their exclusive scan (k_compact_scan) and the views' totals: the scratch of every
+// consumer of a dense result.  Compaction (O1 / N2): cnt / off hold one slot per view OF A LAUNCH (slot k: view first_view + k), a slot =
+// the valid pixels of the view's 1024-pixel blocks; tot: [max_views], view v's at tot[v].  Mesh: cnt / off [max_views][2][mesh_chunks]
+// (valid pixels, faces per chunk), tot [max_views][2].  Normals: cnt / off [max_views][mesh_chunks] valid pixels per chunk, tot [max_views]
 struct CompactScratch {
     unsigned *cnt;
     unsigned long long *off, *tot;
 };
+inline size_t compact_blocks(const KParams &P) { return (P.px_view_stride + 1023) / 1024; }  // 1024-pixel blocks of a view: counts per slot
+// the valid / points planes of view first_view of the dense result (the views behind it follow px_view_stride elements apart)
+struct ViewPlanes {
+    const uint8_t *valid;
+    const float *points;
+};
+inline ViewPlanes view_planes(const KParams &P, int first_view)
+{
+    return {P.valid + (size_t)first_view * P.px_view_stride, P.points + 3 * (size_t)first_view * P.px_view_stride};
+}
 int launch_compact_views(const KParams &P, int first_view, int n_views, const CompactScratch &s, float *clouds, const uint8_t *texture,
                          uint8_t *rgb_out, void *stream);
 int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, int n_arrays, unsigned long long *totals, void *stream);
-// the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A view has
-// mesh_chunks(P) chunks (1024 pixels of one row); counts / offsets: [max_views][2][chunks] (valid pixels, faces) and their exclusive scans,
-// totals: [max_views][2], faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)
+// the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A row has
+// mesh_row_chunks(P) chunks (1024 pixels of one row), a view mesh_chunks(P) = H times as many; s: the mesh form of CompactScratch,
+// faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)
+int mesh_row_chunks(const KParams &P);
 int mesh_chunks(const KParams &P);
-int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
-                      unsigned long long *totals, int *faces, size_t face_stride, void *stream);
-// vertex normals of those meshes (sl3d_mesh_normals.hip): counts / offsets: [max_views][chunks] valid pixels per chunk and their exclusive
-// scan, totals: [max_views], normals: [max_views][normal_stride][3], view v's in the order of its compacted cloud
-int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
-                        unsigned long long *totals, float *normals, size_t normal_stride, void *stream);
+int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, int *faces, size_t face_stride,
+                      void *stream);
+// vertex normals of those meshes (sl3d_mesh_normals.hip): s: the normals form of CompactScratch, normals: [max_views][normal_stride][3],
+// view v's in the order of its compacted cloud
+int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, float *normals,
+                        size_t normal_stride, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

@@ -8,8 +8,12 @@
 // loads hit the cache the neighbour's lines are in.  No index plane: the vertex id of a pixel is its chunk's offset plus the valid
 // pixels of the chunk in front of it, for row r + 1 from ITS chunk's offset -- both are prefixes over bytes the block holds anyway.
 // No atomics: every output position follows from the scans, so the result does not depend on the launch shape, the batch or the run.
+// The scheme is the compaction's; its idioms -- valid-bit unpack, window clip, block sum, LDS flush -- live in sl3d_block.h.  Written
+// out here: the two-word wave prefix of k_mesh_emit (vertices and faces in one shuffle loop).  Chunks per row: mesh_row_chunks; the planes
+// of a launch's first view: view_planes (sl3d_internal.h).
 #include <hip/hip_runtime.h>
 
+#include "sl3d_block.h"
 #include "sl3d_internal.h"
 #include "sl3d_mesh.h"
 
@@ -23,15 +27,15 @@ __device__ __forceinline__ void mesh_lane(const uint8_t *__restrict__ row0, cons
     v0 = v1 = 0u;
     cell[0] = cell[1] = cell[2] = cell[3] = 0u;
     if (c0 >= W) return;
-    const unsigned in_w = W - c0 >= 4 ? 15u : (1u << (W - c0)) - 1u;
+    const unsigned in_w = QUAD_IN_WINDOW(W, c0);
     const bool right = c0 + 4 < W;
     // every valid byte the lane needs, requested before the first is looked at
     const unsigned w0 = *(const unsigned *)(row0 + c0);
     const unsigned w1 = next_row ? *(const unsigned *)(row0 + pitch + c0) : 0u;
     const unsigned r0 = right ? row0[c0 + 4] : 0u;
     const unsigned r1 = right && next_row ? row0[pitch + c0 + 4] : 0u;
-    v0 = (((w0 & 1u) | (w0 >> 7 & 2u) | (w0 >> 14 & 4u) | (w0 >> 21 & 8u)) & in_w) | (r0 & 1u) << 4;
-    v1 = (((w1 & 1u) | (w1 >> 7 & 2u) | (w1 >> 14 & 4u) | (w1 >> 21 & 8u)) & in_w) | (r1 & 1u) << 4;
+    v0 = (valid_nibble(w0) & in_w) | (r0 & 1u) << 4;
+    v1 = (valid_nibble(w1) & in_w) | (r1 & 1u) << 4;
     if (!v0 || !v1) return;  // a face has a corner in either row
     const float4 *p0 = (const float4 *)(pts0 + 3 * (size_t)c0);
     const float4 *p1 = (const float4 *)(pts0 + 3 * ((size_t)pitch + c0));
@@ -66,11 +70,9 @@ __global__ __launch_bounds__(256) void k_mesh_count(const uint8_t *__restrict__ 
     mesh_lane(valid, points, W, pitch, blockIdx.x * MESH_CHUNK + threadIdx.x * 4, r + 1 < H, thr2, v0, v1, cell);
     // both counts in one word: at most 1024 pixels and 2048 faces per chunk
     unsigned c = __popc(v0 & 15u) | ((cell[0] & 3u) + (cell[1] & 3u) + (cell[2] & 3u) + (cell[3] & 3u)) << 16;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
+    BLOCK_SUM(c, s_cnt);
     if (threadIdx.x == 0) {
-        const unsigned t = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        const unsigned t = BLOCK_SUM_TOTAL(s_cnt);
         counts[chunk] = t & 0xffffu;
         counts[n_chunks + chunk] = t >> 16;
     }
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void k_mesh_emit(const uint8_t *__restrict__ v
     __syncthreads();
     unsigned base_v = 0, base_f = 0;
     for (int i = 0; i < (int)(threadIdx.x >> 6); i++) base_v += s_wave_v[i], base_f += s_wave_f[i];
-    const unsigned block_faces = s_wave_f[0] + s_wave_f[1] + s_wave_f[2] + s_wave_f[3];
+    const unsigned block_faces = BLOCK_SUM_TOTAL(s_wave_f);
     if (cf) {
         const unsigned ev = base_v + (iv - cv);
         // vertex ids of pixels c0 .. c0 + 4 of both rows; the pixel right of the block's last quad is the next chunk's first, whose
@@ -133,27 +135,26 @@ __global__ __launch_bounds__(256) void k_mesh_emit(const uint8_t *__restrict__ v
     }
     __syncthreads();
     // the block's faces are contiguous in the output: coalesced dword stores
-    int *dst = faces + 3 * offsets[n_chunks + chunk];
-    for (unsigned i = threadIdx.x; i < 3 * block_faces; i += 256) dst[i] = s_faces[i];
+    block_flush(faces + 3 * offsets[n_chunks + chunk], s_faces, 3 * block_faces);
 }
 
-int mesh_chunks(const KParams &P) { return P.H * ((P.W + MESH_CHUNK - 1) / MESH_CHUNK); }
+int mesh_row_chunks(const KParams &P) { return (P.W + MESH_CHUNK - 1) / MESH_CHUNK; }
+int mesh_chunks(const KParams &P) { return P.H * mesh_row_chunks(P); }
 
-int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
-                      unsigned long long *totals, int *faces, size_t face_stride, void *stream)
+int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, int *faces, size_t face_stride,
+                      void *stream)
 {
-    const int nck = (P.W + MESH_CHUNK - 1) / MESH_CHUNK, n_chunks = P.H * nck;
-    const uint8_t *valid = P.valid + (size_t)first_view * P.px_view_stride;
-    const float *points = P.points + 3 * (size_t)first_view * P.px_view_stride;
-    counts += (size_t)first_view * 2 * n_chunks;
-    offsets += (size_t)first_view * 2 * n_chunks;
+    const int nck = mesh_row_chunks(P), n_chunks = P.H * nck;
+    const ViewPlanes in = view_planes(P, first_view);
+    unsigned *counts = s.cnt + (size_t)first_view * 2 * n_chunks;
+    unsigned long long *offsets = s.off + (size_t)first_view * 2 * n_chunks;
     const double thr2 = mesh_thr2(max_edge);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mesh_count, dim3(nck, P.H, n_views), dim3(256), 0, st, valid, points, P.W, P.H, P.pitch, P.px_view_stride, thr2, counts);
-    int rc = launch_compact_scan(counts, offsets, n_chunks, 2 * n_views, totals + 2 * (size_t)first_view, stream);
+    hipLaunchKernelGGL(k_mesh_count, dim3(nck, P.H, n_views), dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, thr2, counts);
+    int rc = launch_compact_scan(counts, offsets, n_chunks, 2 * n_views, s.tot + 2 * (size_t)first_view, stream);
     if (rc) return rc;
     if (P.H > 1)
-        hipLaunchKernelGGL(k_mesh_emit, dim3(nck, P.H - 1, n_views), dim3(256), 0, st, valid, points, P.W, P.H, P.pitch, P.px_view_stride, thr2,
+        hipLaunchKernelGGL(k_mesh_emit, dim3(nck, P.H - 1, n_views), dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, thr2,
                            (const unsigned *)counts, (const unsigned long long *)offsets, faces + 3 * (size_t)first_view * face_stride, face_stride);
     return (int)hipGetLastError();
 }

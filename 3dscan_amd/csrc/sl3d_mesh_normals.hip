@@ -7,15 +7,15 @@
 //                          (vertex offset of the chunk + prefix within the chunk) and leave through LDS as one coalesced run
 // No atomics, no adjacency lists, nothing read that sl3d_mesh_views wrote: the result follows from the planes and the scan alone, so it
 // does not depend on the launch shape, the batch or the run.
+// The scheme is the compaction's; its idioms -- valid-bit unpack, window clip, block sum, wave prefix, the waves in front, LDS flush --
+// live in sl3d_block.h.  Chunks per row: mesh_row_chunks (sl3d_mesh.hip); the planes of a launch's first view: view_planes (sl3d_internal.h).
 #include <hip/hip_runtime.h>
 
+#include "sl3d_block.h"
 #include "sl3d_internal.h"
 #include "sl3d_mesh.h"
 
 namespace sl3d {
-
-// the 4 valid bits of a dword of 0/1 valid bytes
-__device__ __forceinline__ unsigned valid_nibble(unsigned w) { return (w & 1u) | (w >> 7 & 2u) | (w >> 14 & 4u) | (w >> 21 & 8u); }
 
 // grid (chunks of a row, H, views); counts: [view][H * chunks]
 __global__ __launch_bounds__(256) void k_mesh_normals_count(const uint8_t *__restrict__ valid, int W, int pitch, size_t view_stride,
@@ -26,13 +26,11 @@ __global__ __launch_bounds__(256) void k_mesh_normals_count(const uint8_t *__res
     __shared__ unsigned s_cnt[4];
     unsigned c = 0u;
     if (c0 < W) {
-        const unsigned in_w = W - c0 >= 4 ? 15u : (1u << (W - c0)) - 1u;
+        const unsigned in_w = QUAD_IN_WINDOW(W, c0);
         c = __popc(valid_nibble(*(const unsigned *)(valid + c0)) & in_w);
     }
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[((size_t)blockIdx.z * gridDim.y + r) * nck + blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    BLOCK_SUM(c, s_cnt);
+    if (threadIdx.x == 0) counts[((size_t)blockIdx.z * gridDim.y + r) * nck + blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
 }
 
 // grid (chunks of a row, H, views); offsets: [view][H * chunks] exclusive scan of the counts; normals: [view][normal_stride][3]
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const bool row[3] = {r > 0, true, r + 1 < H};
     unsigned v[3] = {0u, 0u, 0u};
     if (c0 < W) {
-        const unsigned in_w = W - c0 >= 4 ? 15u : (1u << (W - c0)) - 1u;
+        const unsigned in_w = QUAD_IN_WINDOW(W, c0);
         const bool left = c0 > 0, right = c0 + 4 < W;
         // every valid byte the lane needs, requested before the first is looked at
         unsigned w[3], l[3], g[3];
@@ -99,15 +97,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     // exclusive prefix of the lane's valid pixels over the block
     const unsigned cv = __popc(own);
-    unsigned iv = cv;
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned tv = __shfl_up(iv, off, 64);
-        if ((threadIdx.x & 63) >= off) iv += tv;
-    }
-    if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = iv;
-    __syncthreads();
-    unsigned rank = iv - cv;
-    for (int i = 0; i < (int)(threadIdx.x >> 6); i++) rank += s_wave[i];
+    unsigned rank = waves_before(s_wave, wave_prefix(cv, s_wave) - cv);
     if (own) {
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -118,24 +108,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
     __syncthreads();
     // the block's normals are contiguous in the output: coalesced dword stores
-    float *dst = normals + 3 * ((size_t)blockIdx.z * normal_stride + offsets[chunk]);
-    for (unsigned i = threadIdx.x; i < 3 * block_vertices; i += 256) dst[i] = s_n[i];
+    block_flush(normals + 3 * ((size_t)blockIdx.z * normal_stride + offsets[chunk]), s_n, 3 * block_vertices);
 }
 
-int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, unsigned *counts, unsigned long long *offsets,
-                        unsigned long long *totals, float *normals, size_t normal_stride, void *stream)
+int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, float *normals,
+                        size_t normal_stride, void *stream)
 {
-    const int nck = (P.W + MESH_CHUNK - 1) / MESH_CHUNK, n_chunks = P.H * nck;
-    const uint8_t *valid = P.valid + (size_t)first_view * P.px_view_stride;
-    const float *points = P.points + 3 * (size_t)first_view * P.px_view_stride;
-    counts += (size_t)first_view * n_chunks;
-    offsets += (size_t)first_view * n_chunks;
+    const int nck = mesh_row_chunks(P), n_chunks = P.H * nck;
+    const ViewPlanes in = view_planes(P, first_view);
+    unsigned *counts = s.cnt + (size_t)first_view * n_chunks;
+    unsigned long long *offsets = s.off + (size_t)first_view * n_chunks;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(nck, P.H, n_views);
-    hipLaunchKernelGGL(k_mesh_normals_count, grid, dim3(256), 0, st, valid, P.W, P.pitch, P.px_view_stride, counts);
-    int rc = launch_compact_scan(counts, offsets, n_chunks, n_views, totals + first_view, stream);
+    hipLaunchKernelGGL(k_mesh_normals_count, grid, dim3(256), 0, st, in.valid, P.W, P.pitch, P.px_view_stride, counts);
+    int rc = launch_compact_scan(counts, offsets, n_chunks, n_views, s.tot + first_view, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mesh_normals, grid, dim3(256), 0, st, valid, points, P.W, P.H, P.pitch, P.px_view_stride, mesh_thr2(max_edge),
+    hipLaunchKernelGGL(k_mesh_normals, grid, dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, mesh_thr2(max_edge),
                        (const unsigned *)counts, (const unsigned long long *)offsets, normals + 3 * (size_t)first_view * normal_stride, normal_stride);
     return (int)hipGetLastError();
 }

@@ -205,6 +205,12 @@ def pattern_counts(proj_extent, fringe_width):
     return nc.value, npl.value
 
 
+def _cut(flat, counts):
+    """The per-view slices of an array that holds the views' rows back to back, counts[k] of view k."""
+    ends = np.cumsum(counts, dtype=np.int64)
+    return [flat[e - n:e] for n, e in zip(counts, ends)]
+
+
 class Scanner:
     """One context = one GPU + one stream + the HBM-resident frame stacks of `max_views` views."""
 
@@ -583,11 +589,7 @@ class Scanner:
         total = sum(counts)
         flat = np.empty((total, 3), dtype=np.float32)
         self._chk(self.L.sl3d_get_clouds(self._h, first_view, n_views, flat.ctypes.data, total, counts), "sl3d_get_clouds")
-        out, off = [], 0
-        for n in counts:
-            out.append(flat[off:off + n])
-            off += n
-        return out
+        return _cut(flat, counts)
 
     def mesh_device(self, max_edge, first_view=0, n_views=1):
         """sl3d_mesh_views: the meshes of a batch of views left in HBM; returns (Mesh, vertex counts, face counts)."""
@@ -605,11 +607,7 @@ class Scanner:
         xyz, faces = np.empty((tv, 3), dtype=np.float32), np.empty((tf, 3), dtype=np.int32)
         self._chk(self.L.sl3d_get_meshes(self._h, first_view, n_views, float(max_edge), xyz.ctypes.data, tv, faces.ctypes.data, tf, nv, nf),
                   "sl3d_get_meshes")
-        out, vo, fo = [], 0, 0
-        for a, b in zip(nv, nf):
-            out.append((xyz[vo:vo + a], faces[fo:fo + b]))
-            vo, fo = vo + a, fo + b
-        return out
+        return list(zip(_cut(xyz, nv), _cut(faces, nf)))
 
     def mesh(self, max_edge, view=0):
         """(xyz, faces) of one view (meshes)."""
@@ -631,11 +629,7 @@ class Scanner:
         tv = sum(nv)
         flat = np.empty((tv, 3), dtype=np.float32)
         self._chk(self.L.sl3d_get_mesh_normals(self._h, first_view, n_views, float(max_edge), flat.ctypes.data, tv, nv), "sl3d_get_mesh_normals")
-        out, off = [], 0
-        for n in nv:
-            out.append(flat[off:off + n])
-            off += n
-        return out
+        return _cut(flat, nv)
 
     def mesh_normals(self, max_edge, view=0):
         """(n, 3) float32 normals of the vertices of mesh(max_edge, view) (meshes_normals)."""
