@@ -1,35 +1,32 @@
 // sl3d_shim.cpp -- drop-in for the reference's stage objects 3/4/5/7: same four C++ entry points, same
 // global arrays, same input files, but the arithmetic runs in the HIP kernels behind the C ABI.
-// See include/sl3d_shim.h.  Plain C++ (no HIP here); links against libsl3d.so.
+// See include/sl3d_shim.h.  Plain C++ (no HIP here); links against libsl3d.so.  The file readers and writers and the host thread
+// pool are in sl3d_shim_io.h / sl3d_shim_pool.h.
 #include "../../include/sl3d_shim.h"
 
 #include <algorithm>
+#include <cctype>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <charconv>
 #include <cstring>
-#include <strings.h>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <exception>
-#include <new>
-#include <functional>
-#include <mutex>
 #include <map>
-#include <fcntl.h>
-#include <sched.h>
+#include <new>
 #include <string>
+#include <strings.h>
 #include <sys/stat.h>
-#include <unistd.h>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sl3d.h"
 #include "sl3d_shim_io.h"
 
 namespace {
+
+using sl3d_pool::parallel_for;
 
 constexpr int W = Camera_imagewidth, H = Camera_imageheight;
 const char *kReferenceRoot = "/home/pranav/Desktop/M_tech_project_console";  // 3/wrapped_phase.cpp:39, 7/triangulation.cpp:152
@@ -52,7 +49,7 @@ struct Shim {
     std::string root;
     bool root_set = false;
     bool write_debug = false;
-    bool host_transpose = false;  // A/B switch: row-major download + the transposes on the host (what the shim did before round 3)
+    bool host_transpose = false;  // A/B switch: row-major download + the transposes on the host
     bool binary_clouds = false;   // save_point_cloud(): binary PCD / PLY instead of the reference's ASCII
     // inputs handed over in memory instead of through the reference's files (sl3d_shim_provide_image / _matrix)
     struct MemImage { const uint8_t *data; int width, height, channels; size_t stride; };
@@ -130,131 +127,15 @@ struct PhaseTimer {
     }
 };
 
-// host threads for the short bursts below (file decode, text formatting: tens of milliseconds): the affinity mask, at most 32.
-// A cgroup CPU quota is an average over its period, not a core count -- on the GPU boxes (256 cores visible, quota 16) 32 threads
-// finish such a burst in 0.6 of the time 16 take -- so it is not applied here.  SL3D_SHIM_THREADS overrides.
-int usable_threads()
-{
-    static int n = [] {
-        int k = (int)std::thread::hardware_concurrency();
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) k = CPU_COUNT(&set);
-        k = std::min(k, 32);
-        if (const char *e = getenv("SL3D_SHIM_THREADS")) k = atoi(e);
-        return std::max(1, std::min(k, 256));
-    }();
-    return n;
-}
-
-// The host threads behind parallel_for: started once, parked on a condition variable between bursts.  (Until round 5 every burst
-// spawned and joined its own std::threads: ~0.1 ms per stage call of a scan that takes 2-4 ms, four times per scan.)
-class WorkerPool {
-public:
-    static WorkerPool &get()
-    {
-        static WorkerPool *p = new WorkerPool(usable_threads() - 1);  // (never destroyed: the workers may outlive static destruction order)
-        return *p;
-    }
-    // runs job(i) for i in [0, n) on the calling thread and up to `helpers` workers; returns when all items are done
-    void run(int n, int helpers, const std::function<void(int)> &job)
-    {
-        std::unique_lock<std::mutex> serial(run_mu_);  // one burst at a time
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            job_ = &job;
-            n_ = n;
-            next_.store(0);
-            pending_ = n;
-            wanted_ = std::min(helpers, (int)workers_.size());
-            generation_++;
-        }
-        cv_.notify_all();
-        work();
-        std::unique_lock<std::mutex> lk(mu_);
-        done_cv_.wait(lk, [&] { return pending_ == 0 && active_ == 0; });
-        wanted_ = 0;  // (a worker that has not woken yet stays parked)
-        job_ = nullptr;
-        if (error_) {
-            std::exception_ptr e = error_;
-            error_ = nullptr;
-            lk.unlock();
-            std::rethrow_exception(e);
-        }
-    }
-
-private:
-    explicit WorkerPool(int k)
-    {
-        for (int i = 0; i < k; i++) workers_.emplace_back([this] { loop(); }), workers_.back().detach();
-    }
-    void work()
-    {
-        int done = 0;
-        for (int i; (i = next_.fetch_add(1)) < n_;) {
-            try {  // (an exception must not leave a worker thread -- std::terminate -- nor stop the burst's bookkeeping: the first one
-                   // is kept and rethrown by run() on the calling thread, inside the stage function's own barrier)
-                (*job_)(i);
-            } catch (...) {
-                std::lock_guard<std::mutex> lk(mu_);
-                if (!error_) error_ = std::current_exception();
-            }
-            done++;
-        }
-        if (done) {
-            std::lock_guard<std::mutex> lk(mu_);
-            pending_ -= done;
-            if (pending_ == 0) done_cv_.notify_all();
-        }
-    }
-    void loop()
-    {
-        unsigned long long seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return generation_ != seen && wanted_ > 0; });
-                seen = generation_;
-                wanted_--;
-                active_++;
-            }
-            work();
-            {
-                std::lock_guard<std::mutex> lk(mu_);
-                active_--;
-                if (pending_ == 0 && active_ == 0) done_cv_.notify_all();
-            }
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex mu_, run_mu_;
-    std::condition_variable cv_, done_cv_;
-    const std::function<void(int)> *job_ = nullptr;
-    std::exception_ptr error_;
-    std::atomic<int> next_{0};
-    int n_ = 0, pending_ = 0, wanted_ = 0, active_ = 0;
-    unsigned long long generation_ = 0;
-};
-
-// fn(i) for i in [0, n) on up to usable_threads() threads (work items are handed out one by one); the calling thread takes part
-template <typename Fn>
-void parallel_for(int n, Fn fn)
-{
-    const int t = std::min(n, usable_threads());
-    if (t <= 1) {
-        for (int i = 0; i < n; i++) fn(i);
-        return;
-    }
-    const std::function<void(int)> job = [&](int i) { fn(i); };
-    WorkerPool::get().run(n, t - 1, job);
-}
+// a stage call that fails abandons the deferred scan in progress: the next stage call opens a new one (it waits for whatever is still
+// running and brings selected_region up again) instead of taking this scan's state for its own
+void abandon_scan() noexcept { g.scan_open = g.mask_fresh = g.scan_done = false; }
 
 bool fail(int code, const std::string &msg)
 {
     g.status = code;
     g.err = msg;
-    // a failed stage call abandons the deferred scan in progress: the next stage call opens a new one (it waits for whatever is still
-    // running and brings selected_region up again) instead of taking this scan's state for its own
-    g.scan_open = g.mask_fresh = g.scan_done = false;
+    abandon_scan();
     fprintf(stderr, "\nsl3d shim: %s", msg.c_str());  // the reference reports with printf and carries on
     return false;
 }
@@ -280,7 +161,7 @@ void shim_caught(const char *where) noexcept
         snprintf(buf, sizeof buf, "%s: unknown C++ exception", where);
     }
     g.status = code;
-    g.scan_open = g.mask_fresh = g.scan_done = false;
+    abandon_scan();
     try {
         g.err = buf;
     } catch (...) {
@@ -288,117 +169,55 @@ void shim_caught(const char *where) noexcept
     fprintf(stderr, "\nsl3d shim: %s", buf);
 }
 
-bool ok(int rc, const char *what)
+// the status of a libsl3d call: a failure is reported with the status' text and the error text of the context the call was made on
+// (NULL: the text the creating calls leave behind)
+bool ok(int rc, const char *what, const sl3d_ctx *ctx)
 {
     if (rc == SL3D_OK) return true;
-    return fail(rc, std::string(what) + ": " + sl3d_strerror(rc) + ": " + sl3d_last_error(g.ctx));
+    return fail(rc, std::string(what) + ": " + sl3d_strerror(rc) + ": " + sl3d_last_error(ctx));
 }
 
-// ---- the readers of the reference's input files (8/24-bit BMP, OpenCV XML matrices, PLY) live in sl3d_shim_io.h: every size a file
-// claims is checked against the file before it is used (tests/test_shim_io.py feeds them malformed files under ASan / UBSan) ----
-using sl3d_io::bgr2gray;
-inline bool read_bmp_gray(const std::string &path, uint8_t *out, std::vector<uint8_t> *scratch = nullptr) { return sl3d_io::read_bmp_gray(path, W, H, out, scratch); }
-inline bool read_bmp_bgr(const std::string &path, std::vector<uint8_t> &out) { return sl3d_io::read_bmp_bgr(path, W, H, out); }
+// which context of a part a walk visits: the one the stage calls drive or its parity twin (Part::twin)
+enum Side { TIMED, TWIN };
 
-// 8-bit palettised BMP exactly as the reference's cvSaveImage (OpenCV 2.4 BMP encoder) writes a 1-channel image:
-// 14 + 40 byte headers with biSizeImage = biClrUsed = 0, 256 grey palette entries, bottom-up rows padded to 4 bytes.
-// (tests/test_gpu_shim.py compares whole files with the SHA-256 of the reference's own pattern images.)
-bool write_bmp_gray(const std::string &path, const uint8_t *img, int w = W, int h = H)
+// fn(context, part) for every part in turn; stops at the first failure, reported with the visited context's error text
+template <typename Fn>
+bool each_part(const char *what, Fn fn, Side side = TIMED)
 {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const uint32_t rowbytes = ((uint32_t)w + 3) & ~3u, off = 54 + 1024, size = off + rowbytes * h;
-    uint8_t hdr[54] = {0};
-    auto put32 = [&](int o, uint32_t v) { hdr[o] = v & 255; hdr[o + 1] = (v >> 8) & 255; hdr[o + 2] = (v >> 16) & 255; hdr[o + 3] = v >> 24; };
-    hdr[0] = 'B'; hdr[1] = 'M';
-    put32(2, size); put32(10, off); put32(14, 40); put32(18, w); put32(22, h);
-    hdr[26] = 1; hdr[28] = 8;
-    fwrite(hdr, 1, 54, f);
-    for (int i = 0; i < 256; i++) { uint8_t q[4] = {(uint8_t)i, (uint8_t)i, (uint8_t)i, 0}; fwrite(q, 1, 4, f); }
-    std::vector<uint8_t> row(rowbytes, 0);
-    for (int y = h - 1; y >= 0; y--) { memcpy(row.data(), img + (size_t)y * w, w); fwrite(row.data(), 1, rowbytes, f); }
-    fclose(f);
+    for (const Part &p : g.parts) {
+        sl3d_ctx *c = side == TWIN ? p.twin : p.ctx;
+        if (!ok(fn(c, p), what, c)) return false;
+    }
     return true;
 }
 
-// The ASCII cloud rows of the reference's PCL writers (8/save_point_cloud.cpp:211-217), built in memory: std::to_chars with
-// chars_format::general and precision 9 yields the digits of printf("%.9g") (the C++17 contract), several times faster than a
-// fprintf per point.  The float -> text conversion is what costs, and the PCD and the PLY row of a point share their "x y z "
-// text: it is formatted ONCE and appended to both (pcd / ply may be NULL); the PCD row ends with one packed 0x00RRGGBB integer,
-// the PLY row with "red green blue".
-void append_cloud_rows(std::string *pcd, std::string *ply, const float *xyz, const uint8_t *rgb, int64_t first, int64_t n)
+bool sync_parts()
 {
-    // rows are written straight into the strings' storage through raw pointers (a row is at most 3 * 16 + 12 bytes), and the
-    // strings are cut to their real length at the end: no per-value append
-    constexpr size_t kRowMax = 64;
-    const size_t pcd0 = pcd ? pcd->size() : 0, ply0 = ply ? ply->size() : 0;
-    if (pcd) pcd->resize(pcd0 + (size_t)n * kRowMax);
-    if (ply) ply->resize(ply0 + (size_t)n * kRowMax);
-    char *pc = pcd ? &(*pcd)[pcd0] : nullptr, *pl = ply ? &(*ply)[ply0] : nullptr;
-    char buf[64];
-    for (int64_t i = first; i < first + n; i++) {
-        char *p = buf;
-        for (int k = 0; k < 3; k++) {
-            p = std::to_chars(p, buf + sizeof buf, xyz[3 * i + k], std::chars_format::general, 9).ptr;
-            *p++ = ' ';
-        }
-        const size_t len = (size_t)(p - buf);
-        if (pc) {
-            memcpy(pc, buf, len);
-            const unsigned packed = ((unsigned)rgb[3 * i] << 16) | ((unsigned)rgb[3 * i + 1] << 8) | (unsigned)rgb[3 * i + 2];
-            pc = std::to_chars(pc + len, pc + len + 12, packed).ptr;
-            *pc++ = '\n';
-        }
-        if (pl) {
-            memcpy(pl, buf, len);
-            pl += len;
-            for (int k = 0; k < 3; k++) {
-                pl = std::to_chars(pl, pl + 4, (unsigned)rgb[3 * i + k]).ptr;
-                *pl++ = k < 2 ? ' ' : '\n';
-            }
-        }
-    }
-    if (pcd) pcd->resize((size_t)(pc - pcd->data()));
-    if (ply) ply->resize((size_t)(pl - ply->data()));
+    return each_part("sl3d_synchronize", [&](sl3d_ctx *c, const Part &) { return sl3d_synchronize(c); });
 }
 
-// header + pieces -> one file, in order.  (Round 4 also tried to give the file its final size, map it and let every thread copy its
-// pieces in: on the GPU boxes' overlay file system the page faults of a shared mapping cost more than write() -- 233 against 155 ms
-// for the two ASCII files of a 1.87-Mpoint cloud -- so the pieces are written one after the other.)
-bool write_pieces(const std::string &path, const std::string &header, const std::vector<std::string> &pieces)
-{
-    const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (fd < 0) return false;
-    bool good = true;
-    auto put = [&](const char *p, size_t n) {
-        while (good && n) {
-            const ssize_t w = write(fd, p, n);
-            if (w <= 0) good = false;
-            else { p += w; n -= (size_t)w; }
-        }
-    };
-    put(header.data(), header.size());
-    for (const auto &q : pieces) put(q.data(), q.size());
-    return close(fd) == 0 && good;
-}
-
-// the rows of a whole cloud for both files (either may be NULL): disjoint point ranges are formatted on all host threads into
-// their own buffers; concatenated in order they are byte for byte what one loop over all points writes
-int cloud_parts(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 16383) / 16384, 4 * usable_threads())); }
-
-void format_cloud(const float *xyz, const uint8_t *rgb, int64_t n, std::vector<std::string> *pcd, std::vector<std::string> *ply)
-{
-    const int parts = cloud_parts(n);
-    // (resize + clear: a buffer that is being reused keeps its capacity, i.e. its already-touched pages)
-    if (pcd) pcd->resize((size_t)parts);
-    if (ply) ply->resize((size_t)parts);
-    parallel_for(parts, [&](int k) {
-        const int64_t a = n * k / parts, b = n * (k + 1) / parts;
-        if (pcd) (*pcd)[(size_t)k].clear();
-        if (ply) (*ply)[(size_t)k].clear();
-        append_cloud_rows(pcd ? &(*pcd)[(size_t)k] : nullptr, ply ? &(*ply)[(size_t)k] : nullptr, xyz, rgb, a, b - a);
-    });
-}
+// One axis of the scan (pattern_type 0 / 1): the reference's four globals of it, their SL3D_G_* ids, its directory name and the number
+// of its Gray planes.  The stage functions and fill_globals read the globals from here.
+struct Axis {
+    int (*&valid)[Camera_imageheight];
+    float (*&wrapped)[Camera_imageheight];
+    float (*&unwrapped)[Camera_imageheight];
+    int (*&code)[Camera_imageheight];
+    int id_valid, id_wrapped, id_unwrapped, id_code;
+    const char *dir;
+    const int &n_gray;
+};
+const Axis kAxis[2] = {
+    {valid_map_vertical, wrapped_phi_vertical, unwrapped_phi_vertical, code_vertical,
+     SL3D_G_VALID_V, SL3D_G_WRAPPED_V, SL3D_G_UNWRAPPED_V, SL3D_G_CODE_V, "Vertical", number_of_patterns_binary_vertical},
+    {valid_map_horizontal, wrapped_phi_horizontal, unwrapped_phi_horizontal, code_horizontal,
+     SL3D_G_VALID_H, SL3D_G_WRAPPED_H, SL3D_G_UNWRAPPED_H, SL3D_G_CODE_H, "Horizontal", number_of_patterns_binary_horizontal},
+};
+// sl3d_shim_globals names a plane global by the bit of its id
+static_assert(SL3D_SHIM_G_VALID_V == 1u << SL3D_G_VALID_V && SL3D_SHIM_G_VALID_H == 1u << SL3D_G_VALID_H && SL3D_SHIM_G_VALID == 1u << SL3D_G_VALID &&
+              SL3D_SHIM_G_WRAPPED_V == 1u << SL3D_G_WRAPPED_V && SL3D_SHIM_G_WRAPPED_H == 1u << SL3D_G_WRAPPED_H &&
+              SL3D_SHIM_G_UNWRAPPED_V == 1u << SL3D_G_UNWRAPPED_V && SL3D_SHIM_G_UNWRAPPED_H == 1u << SL3D_G_UNWRAPPED_H &&
+              SL3D_SHIM_G_CODE_V == 1u << SL3D_G_CODE_V && SL3D_SHIM_G_CODE_H == 1u << SL3D_G_CODE_H, "fill_globals: mask bit = 1 << id");
 
 // One input frame: the caller's memory (sl3d_shim_provide_image under one of the names; no copy) or the first readable file of
 // the given names below the data root, decoded into `storage`.
@@ -412,8 +231,6 @@ struct Frame {
 // ONCE into one pinned staging area, back to back -- so the files cost one decode time instead of their sum, and the planes go up
 // as ONE asynchronous 2-D copy (sl3d_set_frames_range takes back-to-back pinned planes as such).  The staging area is reused by
 // the next stage call: every stage function ends with a synchronising getter, so the copy has long finished.
-bool sync_parts();
-
 // slot0 / capacity: where in the staging area this call's frames go and how many planes the area must hold -- a stage-by-stage scan
 // reuses slots [0, n) in every stage call (after making sure the previous call's copy has finished: an error path may have left it
 // in flight); a deferred scan gives every plane of the scan its own slot, so that no stage call waits for the one before it.
@@ -452,7 +269,7 @@ bool load_frames(const std::vector<std::vector<std::string>> &names, std::vector
         uint8_t *dst = g.staging + (slot0 + i) * (size_t)W * H;   // frames that all come from files end up back to back
         bool got = false;
         for (const auto &nm : names[i])
-            if (!got && read_bmp_gray(root + "/" + nm, dst, &g.decode_scratch[slot0 + i])) got = true;
+            if (!got && sl3d_io::read_bmp_gray(root + "/" + nm, W, H, dst, &g.decode_scratch[slot0 + i])) got = true;
         ok_flag[i] = got;
         out[i].data = dst;
         out[i].stride = (size_t)W;
@@ -484,7 +301,8 @@ void drop_ctx()
 {
     for (Part &p : g.parts)
         if (p.twin) sl3d_destroy(p.twin);
-    g.scan_open = g.mask_fresh = g.scan_done = g.twin_fresh = g.cal_valid = false;
+    abandon_scan();
+    g.twin_fresh = g.cal_valid = false;
     if (g.group) sl3d_group_destroy(g.group);
     else if (g.ctx) sl3d_destroy(g.ctx);
     g.group = nullptr;
@@ -492,15 +310,17 @@ void drop_ctx()
     g.parts.clear();
 }
 
-// every part in turn; stops at the first failure (reported with that part's error text)
-template <typename Fn>
-bool each_part(const char *what, Fn fn)
+// the recorded configuration as a context's: the whole frame on device 0, no flags -- a caller sets what differs
+sl3d_config recorded_config()
 {
-    for (const Part &p : g.parts) {
-        const int rc = fn(p);
-        if (rc != SL3D_OK) return fail(rc, std::string(what) + ": " + sl3d_strerror(rc) + ": " + sl3d_last_error(p.ctx));
-    }
-    return true;
+    sl3d_config c;
+    memset(&c, 0, sizeof c);
+    c.width = W; c.height = H; c.proj_width = Projector_imagewidth; c.proj_height = Projector_imageheight;
+    c.n_fringe = g.F; c.n_gray_v = g.Nv; c.n_gray_h = g.Nh;
+    c.fringe_width_v = g.fwv; c.fringe_width_h = g.fwh;
+    c.n_codes_v = g.ncv; c.n_codes_h = g.nch;
+    c.max_views = 1;
+    return c;
 }
 
 bool ensure_ctx()
@@ -512,17 +332,11 @@ bool ensure_ctx()
     if (same) return true;
     drop_ctx();
     g.ctx_deferred = g.deferred();
-    sl3d_config c;
-    memset(&c, 0, sizeof c);
-    c.width = W; c.height = H; c.proj_width = Projector_imagewidth; c.proj_height = Projector_imageheight;
-    c.n_fringe = g.F = number_of_patterns_fringe;
-    c.n_gray_v = g.Nv = number_of_patterns_binary_vertical;
-    c.n_gray_h = g.Nh = number_of_patterns_binary_horizontal;
-    c.fringe_width_v = g.fwv = fringe_width_pixels_vertical;
-    c.fringe_width_h = g.fwh = fringe_width_pixels_horizontal;
-    c.n_codes_v = g.ncv = number_of_codes_vertical;
-    c.n_codes_h = g.nch = number_of_codes_horizontal;
-    c.max_views = 1;
+    g.F = number_of_patterns_fringe;
+    g.Nv = number_of_patterns_binary_vertical; g.Nh = number_of_patterns_binary_horizontal;
+    g.fwv = fringe_width_pixels_vertical; g.fwh = fringe_width_pixels_horizontal;
+    g.ncv = number_of_codes_vertical; g.nch = number_of_codes_horizontal;
+    sl3d_config c = recorded_config();
     c.device = getenv("SL3D_DEVICE") ? atoi(getenv("SL3D_DEVICE")) : 0;
     c.flags = g.ctx_deferred ? 0u : (unsigned)SL3D_FLAG_KEEP_STAGES;  // deferred: the timed kernels, no stage planes
     std::vector<int> devs;
@@ -536,8 +350,7 @@ bool ensure_ctx()
         }
     }
     if (devs.size() > 1) {
-        const int rc = sl3d_group_create(&c, devs.data(), (int)devs.size(), &g.group);
-        if (rc != SL3D_OK) return fail(rc, std::string("sl3d_group_create: ") + sl3d_strerror(rc) + ": " + sl3d_group_last_error(nullptr));
+        if (!ok(sl3d_group_create(&c, devs.data(), (int)devs.size(), &g.group), "sl3d_group_create", nullptr)) return false;
         for (int i = 0; i < sl3d_group_size(g.group); i++) {
             Part p{nullptr, 0, 0};
             sl3d_group_stripe(g.group, i, &p.row0, &p.rows, &p.device, &p.ctx);
@@ -547,32 +360,17 @@ bool ensure_ctx()
         return true;
     }
     if (devs.size() == 1) c.device = devs[0];
-    const int rc = sl3d_create(&c, &g.ctx);
-    if (rc != SL3D_OK) return fail(rc, std::string("sl3d_create: ") + sl3d_strerror(rc) + ": " + sl3d_last_error(nullptr));
+    if (!ok(sl3d_create(&c, &g.ctx), "sl3d_create", nullptr)) return false;
     Part whole{g.ctx, 0, H};
     whole.device = c.device;
     g.parts.push_back(whole);
     return true;
 }
 
-bool sync_parts()
-{
-    return each_part("sl3d_synchronize", [&](const Part &q) { return sl3d_synchronize(q.ctx); });
-}
-
-template <typename T, typename U>
-void to_col_row(const std::vector<T> &rowmajor, U (*dst)[Camera_imageheight])
-{
-    for (int r = 0; r < H; r++)
-        for (int c = 0; c < W; c++) dst[c][r] = (U)rowmajor[(size_t)r * W + c];
-}
-
-const char *axis_dir(int pattern_type) { return pattern_type == 0 ? "Vertical" : "Horizontal"; }
-
 // planes [first, first + n) of one axis to every part: a part takes its own rows of every plane (a contiguous byte range)
 bool upload_planes(const std::vector<Frame> &img, int pattern_type, int first)
 {
-    return each_part("sl3d_set_frames_range", [&](const Part &q) {
+    return each_part("sl3d_set_frames_range", [&](sl3d_ctx *c, const Part &q) {
         std::vector<const uint8_t *> planes;
         for (auto &f : img) planes.push_back(f.data + (size_t)q.row0 * f.stride);
         // (planes from different sources may have different strides: one call per run of equal strides)
@@ -580,7 +378,7 @@ bool upload_planes(const std::vector<Frame> &img, int pattern_type, int first)
         while (i < planes.size()) {
             size_t j = i + 1;
             while (j < planes.size() && img[j].stride == img[i].stride) j++;
-            const int rc = sl3d_set_frames_range(q.ctx, 0, pattern_type, first + (int)i, planes.data() + i, (int)(j - i), img[i].stride);
+            const int rc = sl3d_set_frames_range(c, 0, pattern_type, first + (int)i, planes.data() + i, (int)(j - i), img[i].stride);
             if (rc != SL3D_OK) return rc;
             i = j;
         }
@@ -589,24 +387,36 @@ bool upload_planes(const std::vector<Frame> &img, int pattern_type, int first)
 }
 
 // The reference allocates its globals with new[] inside the stage functions and never frees them (3/wrapped_phase.cpp:410-424,
-// ...).  The shim is that callee: it allocates them ONCE, in pinned memory, so that each global arrives as one full-rate DMA.
+// 4/phase_unwrap.cpp:282,300,373-376, 5/compute_correspondance.cpp:635,640, 7/triangulation.cpp:1513).  The shim is that callee: it
+// allocates each of them ONCE, in pinned memory, so that it arrives as one full-rate DMA.  count: in elements, not rows.
 template <typename T>
-T *alloc_global(size_t count)
+void ensure_global(T *&p, size_t count)
 {
-    void *p = sl3d_host_alloc(count * sizeof(T));
-    return p ? (T *)p : new T[count];
+    using E = typename std::remove_all_extents<T>::type;
+    if (p) return;
+    void *pinned = sl3d_host_alloc(count * sizeof(E));
+    p = pinned ? (T *)pinned : (T *)new E[count];
 }
+template <typename T>
+auto flat(T *p) { return (typename std::remove_all_extents<T>::type *)p; }
 
-// one of the reference's [col][row] globals from every part: transposed on the device, one contiguous copy per part
-// (sl3d_get_global_colrow); with the A/B switch: the row-major plane and a strided host pass, as before round 3
-template <typename T, typename U, typename GetRowMajor>
-bool fetch_global(const char *what, int which, U (*dst)[Camera_imageheight], GetRowMajor get_rowmajor)
+// one of the reference's [col][row] globals with K values per pixel, from the parts' contexts or their twins: transposed on the
+// device, one contiguous copy per part
+bool get_colrow(const char *what, int id, void *dst, Side side = TIMED)
 {
-    if (!g.host_transpose)
-        return each_part(what, [&](const Part &q) { return sl3d_get_global_colrow(q.ctx, 0, which, dst, H, q.row0); });
-    std::vector<T> tmp((size_t)W * H);
-    if (!each_part(what, [&](const Part &q) { return get_rowmajor(q, tmp.data() + (size_t)q.row0 * W); })) return false;
-    to_col_row(tmp, dst);
+    return each_part(what, [&](sl3d_ctx *c, const Part &q) { return sl3d_get_global_colrow(c, 0, id, dst, H, q.row0); }, side);
+}
+// the same for a stage function; with the A/B switch (sl3d_shim_host_transpose): the row-major plane of T from get_rowmajor and a
+// strided host pass
+template <typename T, int K = 1, typename U, typename GetRowMajor>
+bool fetch_global(const char *what, int id, U *dst, GetRowMajor get_rowmajor, const char *what_rowmajor = nullptr)
+{
+    if (!g.host_transpose) return get_colrow(what, id, dst);
+    std::vector<T> tmp((size_t)W * H * K);
+    if (!each_part(what_rowmajor ? what_rowmajor : what, [&](sl3d_ctx *c, const Part &q) { return get_rowmajor(c, tmp.data() + (size_t)q.row0 * W * K); })) return false;
+    for (int r = 0; r < H; r++)
+        for (int c = 0; c < W; c++)
+            for (int k = 0; k < K; k++) dst[((size_t)c * H + r) * K + k] = (U)tmp[((size_t)r * W + c) * K + k];
     return true;
 }
 
@@ -615,7 +425,7 @@ bool fetch_global(const char *what, int which, U (*dst)[Camera_imageheight], Get
 bool upload_mask()
 {
     if (selected_region && !g.host_transpose)
-        return each_part("sl3d_set_mask_colrow", [&](const Part &p) { return sl3d_set_mask_colrow(p.ctx, 0, &selected_region[0][0]); });
+        return each_part("sl3d_set_mask_colrow", [&](sl3d_ctx *c, const Part &) { return sl3d_set_mask_colrow(c, 0, &selected_region[0][0]); });
     std::vector<uint8_t> tmp;
     const uint8_t *mask = nullptr;
     if (selected_region) {
@@ -630,7 +440,7 @@ bool upload_mask()
         }
         mask = g.default_mask.data();
     }
-    return each_part("sl3d_set_mask", [&](const Part &p) { return sl3d_set_mask(p.ctx, 0, mask, W); });
+    return each_part("sl3d_set_mask", [&](sl3d_ctx *c, const Part &) { return sl3d_set_mask(c, 0, mask, W); });
 }
 
 // the 8 calibration files of read_parameters() / compute_A() as 40 doubles: Kc dc rc tc Kp dp rp tp
@@ -648,6 +458,14 @@ bool read_calibration(double cal[40])
 int set_cal(sl3d_ctx *c, const double cal[40])
 {
     return sl3d_set_calibration(c, cal, cal + 9, cal + 14, cal + 17, cal + 20, cal + 29, cal + 34, cal + 37);
+}
+
+// the names frame i of a capture directory may have: the reference's own and the captured-image variant.  kind: "Fringe_patterns" or
+// "Coded_patterns/Gray_coded"; prefix: "" or "inverse_"
+std::vector<std::string> capture_names(const char *kind, const Axis &axis, const char *prefix, int i)
+{
+    const std::string stem = std::string("Captured_patterns/") + kind + "/" + axis.dir + "/Undistorted/" + prefix, n = std::to_string(i);
+    return {stem + "Captured_image_" + n + ".bmp", stem + "Gray_captured_image_" + n + ".bmp"};
 }
 
 // ---- deferred mode (sl3d_shim_globals) -------------------------------------------------------------------------------------------
@@ -675,14 +493,11 @@ bool run_twins()
     if (!sync_parts()) return false;  // the parts' uploads run on their own streams: they must have landed before they are copied from
     for (Part &q : g.parts) {
         if (!q.twin) {
-            sl3d_config c;
-            memset(&c, 0, sizeof c);
-            c.width = W; c.height = q.rows; c.full_width = W; c.full_height = H; c.row0 = q.row0;
-            c.proj_width = Projector_imagewidth; c.proj_height = Projector_imageheight;
-            c.n_fringe = g.F; c.n_gray_v = g.Nv; c.n_gray_h = g.Nh; c.fringe_width_v = g.fwv; c.fringe_width_h = g.fwh;
-            c.n_codes_v = g.ncv; c.n_codes_h = g.nch; c.max_views = 1; c.device = q.device; c.flags = SL3D_FLAG_KEEP_STAGES;
-            const int rc = sl3d_create(&c, &q.twin);
-            if (rc != SL3D_OK) return fail(rc, std::string("sl3d_create (parity context): ") + sl3d_strerror(rc) + ": " + sl3d_last_error(nullptr));
+            sl3d_config c = recorded_config();
+            c.height = q.rows; c.full_width = W; c.full_height = H; c.row0 = q.row0;
+            c.device = q.device;
+            c.flags = SL3D_FLAG_KEEP_STAGES;
+            if (!ok(sl3d_create(&c, &q.twin), "sl3d_create (parity context)", nullptr)) return false;
         }
         sl3d_device_buffers b;
         int rc = sl3d_get_device_buffers(q.ctx, &b);
@@ -705,59 +520,60 @@ bool run_twins()
         for (int a = 0; a < 2 && rc == SL3D_OK; a++) rc = sl3d_unwrap_phase(q.twin, 0, a);
         if (rc == SL3D_OK) rc = sl3d_compute_c_p_map(q.twin, 0);
         if (rc == SL3D_OK) rc = sl3d_triangulate(q.twin, 0);
-        if (rc != SL3D_OK) return fail(rc, std::string("parity stages: ") + sl3d_strerror(rc) + ": " + sl3d_last_error(q.twin));
+        if (!ok(rc, "parity stages", q.twin)) return false;
     }
     g.twin_fresh = true;
     return true;
 }
 
-template <typename T>
-void ensure_global(T *&p, size_t count)
+// c_p_map is indexed [row*W + col] in the reference too (common_variables.h:15): the row-major plane is the global
+static_assert(sizeof(long int) == sizeof(int64_t), "c_p_map is long[ ][2] on LP64");
+bool fetch_c_p_map(Side side)
 {
-    if (!p) p = (T *)alloc_global<typename std::remove_all_extents<T>::type>(count);
+    return each_part("sl3d_get_c_p_map", [&](sl3d_ctx *c, const Part &q) { return sl3d_get_c_p_map(c, 0, (int64_t *)c_p_map + 2 * (size_t)q.row0 * W); }, side);
 }
 
 // fills the globals `which` names from the finished deferred scan; the stage globals come from the parity contexts
 bool fill_globals(unsigned which)
 {
     const size_t px = (size_t)W * H;
-    auto from = [&](bool twin, int id, void *dst) {
-        for (const Part &q : g.parts) {
-            sl3d_ctx *c = twin ? q.twin : q.ctx;
-            const int rc = sl3d_get_global_colrow(c, 0, id, dst, H, q.row0);
-            if (rc != SL3D_OK) return fail(rc, std::string("sl3d_get_global_colrow: ") + sl3d_strerror(rc) + ": " + sl3d_last_error(c));
-        }
-        return true;
-    };
     const unsigned stage_bits = which & ~(unsigned)(SL3D_SHIM_G_VALID | SL3D_SHIM_G_INTERSECTION_POINTS_F32);
     if (stage_bits && !run_twins()) return false;
-    if (which & SL3D_SHIM_G_VALID) {
-        ensure_global(valid_map, px);
-        if (!from(false, SL3D_G_VALID, valid_map)) return false;
-    }
+    auto plane = [&](auto *&p, int id, Side side) {  // (a plane global nobody asked for counts as filled)
+        if (!(which & 1u << id)) return true;
+        ensure_global(p, px);
+        return get_colrow("sl3d_get_global_colrow", id, p, side);
+    };
+    if (!plane(valid_map, SL3D_G_VALID, TIMED)) return false;
     if (which & (SL3D_SHIM_G_INTERSECTION_POINTS | SL3D_SHIM_G_INTERSECTION_POINTS_F32)) {
         ensure_global(intersection_points, px * 3);
         const bool exact = (which & SL3D_SHIM_G_INTERSECTION_POINTS) != 0;
-        if (!from(exact, exact ? SL3D_G_INTERSECTION_POINTS : SL3D_G_POINTS_F64, intersection_points)) return false;
+        if (!get_colrow("sl3d_get_global_colrow", exact ? SL3D_G_INTERSECTION_POINTS : SL3D_G_POINTS_F64, intersection_points, exact ? TWIN : TIMED)) return false;
     }
-    struct { unsigned bit; int id; void **dst; size_t elem; } planes[] = {
-        {SL3D_SHIM_G_VALID_V, SL3D_G_VALID_V, (void **)&valid_map_vertical, 4},           {SL3D_SHIM_G_VALID_H, SL3D_G_VALID_H, (void **)&valid_map_horizontal, 4},
-        {SL3D_SHIM_G_WRAPPED_V, SL3D_G_WRAPPED_V, (void **)&wrapped_phi_vertical, 4},     {SL3D_SHIM_G_WRAPPED_H, SL3D_G_WRAPPED_H, (void **)&wrapped_phi_horizontal, 4},
-        {SL3D_SHIM_G_UNWRAPPED_V, SL3D_G_UNWRAPPED_V, (void **)&unwrapped_phi_vertical, 4}, {SL3D_SHIM_G_UNWRAPPED_H, SL3D_G_UNWRAPPED_H, (void **)&unwrapped_phi_horizontal, 4},
-        {SL3D_SHIM_G_CODE_V, SL3D_G_CODE_V, (void **)&code_vertical, 4},                  {SL3D_SHIM_G_CODE_H, SL3D_G_CODE_H, (void **)&code_horizontal, 4},
-    };
-    for (auto &e : planes) {
-        if (!(which & e.bit)) continue;
-        if (!*e.dst) *e.dst = alloc_global<int>(px);  // (int and float globals have the same size)
-        if (!from(true, e.id, *e.dst)) return false;
-    }
+    for (const Axis &a : kAxis)
+        if (!plane(a.valid, a.id_valid, TWIN) || !plane(a.wrapped, a.id_wrapped, TWIN) || !plane(a.unwrapped, a.id_unwrapped, TWIN) || !plane(a.code, a.id_code, TWIN)) return false;
     if (which & SL3D_SHIM_G_C_P_MAP) {
-        if (!c_p_map) c_p_map = (long int (*)[2])alloc_global<long int>((size_t)total_camera_pixels * 2);
-        for (const Part &q : g.parts) {
-            const int rc = sl3d_get_c_p_map(q.twin, 0, (int64_t *)c_p_map + 2 * (size_t)q.row0 * W);
-            if (rc != SL3D_OK) return fail(rc, std::string("sl3d_get_c_p_map: ") + sl3d_strerror(rc) + ": " + sl3d_last_error(q.twin));
-        }
+        ensure_global(c_p_map, (size_t)total_camera_pixels * 2);
+        if (!fetch_c_p_map(TWIN)) return false;
     }
+    return true;
+}
+
+// the stage-3 / stage-4 debug image of an axis (save_wrapped_image, 3/wrapped_phase.cpp:346; save_unwrap_phase_image,
+// 4/phase_unwrap.cpp:321-364): where it goes, and fetching it from the parts (or their twins) and writing it
+std::string debug_image_path(int stage, const Axis &axis)
+{
+    if (stage == 3) return data_root() + "/Wrapped_phase_images/" + axis.dir + "/Wrapped_phase_image.bmp";
+    std::string lower = axis.dir;
+    lower[0] = (char)tolower(lower[0]);
+    return data_root() + "/Unwrapped_phase_images/Gray_coded/" + axis.dir + "/Unwrapped_phase_" + lower + ".bmp";
+}
+bool write_debug_image(int stage, int pattern_type, Side side = TIMED)
+{
+    std::vector<uint8_t> d((size_t)W * H);
+    if (!each_part("sl3d_get_debug_image", [&](sl3d_ctx *c, const Part &q) { return sl3d_get_debug_image(c, 0, stage, pattern_type, d.data() + (size_t)q.row0 * W, W); }, side))
+        return false;
+    sl3d_io::write_bmp_gray(debug_image_path(stage, kAxis[pattern_type]), d.data(), W, H);
     return true;
 }
 
@@ -765,18 +581,35 @@ bool fill_globals(unsigned which)
 void write_deferred_debug_images()
 {
     if (!run_twins()) return;
-    std::vector<uint8_t> d((size_t)W * H);
     for (int pt = 0; pt < 2; pt++)
-        for (int stage = 3; stage <= 4; stage++) {
-            if (!each_part("sl3d_get_debug_image", [&](const Part &q) { return sl3d_get_debug_image(q.twin, 0, stage, pt, d.data() + (size_t)q.row0 * W, W); })) return;
-            const std::string path = stage == 3 ? data_root() + "/Wrapped_phase_images/" + axis_dir(pt) + "/Wrapped_phase_image.bmp"
-                                                : data_root() + (pt == 0 ? "/Unwrapped_phase_images/Gray_coded/Vertical/Unwrapped_phase_vertical.bmp"
-                                                                         : "/Unwrapped_phase_images/Gray_coded/Horizontal/Unwrapped_phase_horizontal.bmp");
-            write_bmp_gray(path, d.data());
-        }
+        for (int stage = 3; stage <= 4; stage++)
+            if (!write_debug_image(stage, pt, TWIN)) return;
+}
+
+// A cloud's file or files from its points and colours: the PLY and, with pcd_path, the PCD beside it, in the format
+// sl3d_shim_cloud_format selects.  The pieces of both files are produced on all host threads; then the two files go out side by side,
+// a write() loop each.  (Writers that start on the finished pieces while the rest is still being formatted were measured too: they
+// compete with the formatting threads for the container's CPU quota -- 97 against 83 ms per save.)
+bool write_cloud_files(const float *xyz, const uint8_t *rgb, int64_t n, const std::string *pcd_path, const std::string &ply_path, PhaseTimer *pt = nullptr)
+{
+    const std::string pcd_header = sl3d_io::pcd_header(n, g.binary_clouds), ply_header = sl3d_io::ply_header(n, g.binary_clouds);
+    sl3d_io::format_cloud(xyz, rgb, n, g.binary_clouds, pcd_path ? &g.pcd_rows : nullptr, &g.ply_rows);
+    if (pt) pt->lap("format");
+    // (nothing between the writer thread's start and its join can throw: an exception that unwinds through a joinable std::thread is
+    // std::terminate, past the entry point's barrier)
+    bool pcd_ok = true;
+    std::thread pcd_writer;
+    if (pcd_path) pcd_writer = std::thread([&] { pcd_ok = sl3d_io::write_pieces(*pcd_path, pcd_header, g.pcd_rows); });
+    const bool ply_ok = sl3d_io::write_pieces(ply_path, ply_header, g.ply_rows);
+    if (pcd_path) pcd_writer.join();
+    if (pt) pt->lap("write pcd + ply");
+    if (!pcd_ok) return fail(SL3D_E_INVALID_ARG, "cannot write " + *pcd_path);
+    if (!ply_ok) return fail(SL3D_E_INVALID_ARG, "cannot write " + ply_path);
+    return true;
 }
 
 }  // namespace
+
 
 extern "C" void sl3d_shim_set_data_root(const char *dir)
 try {
@@ -840,27 +673,26 @@ void generate_pattern()
 try {
     g.status = SL3D_OK;
     if (number_of_patterns_fringe < 3 || number_of_patterns_fringe > 5) { fail(SL3D_E_INVALID_ARG, "generate_pattern: 3, 4 or 5 fringe patterns"); return; }
-    if (!ok(sl3d_pattern_counts(Projector_imagewidth, fringe_width_pixels_vertical, &number_of_codes_vertical, &number_of_patterns_binary_vertical), "sl3d_pattern_counts")) return;
-    if (!ok(sl3d_pattern_counts(Projector_imageheight, fringe_width_pixels_horizontal, &number_of_codes_horizontal, &number_of_patterns_binary_horizontal), "sl3d_pattern_counts")) return;
+    if (!ok(sl3d_pattern_counts(Projector_imagewidth, fringe_width_pixels_vertical, &number_of_codes_vertical, &number_of_patterns_binary_vertical), "sl3d_pattern_counts", g.ctx)) return;
+    if (!ok(sl3d_pattern_counts(Projector_imageheight, fringe_width_pixels_horizontal, &number_of_codes_horizontal, &number_of_patterns_binary_horizontal), "sl3d_pattern_counts", g.ctx)) return;
     if (!ensure_ctx()) return;
     const int PWs = Projector_imagewidth, PHs = Projector_imageheight;
     std::vector<uint8_t> img((size_t)PWs * PHs);
     const std::string root = data_root() + "/Generated_patterns";
     auto emit = [&](int kind, int axis, int index, const std::string &rel) {
-        if (!ok(sl3d_generate_pattern(g.ctx, kind, axis, index, img.data(), (size_t)PWs, nullptr, nullptr), "sl3d_generate_pattern")) return false;
+        if (!ok(sl3d_generate_pattern(g.ctx, kind, axis, index, img.data(), (size_t)PWs, nullptr, nullptr), "sl3d_generate_pattern", g.ctx)) return false;
         const std::string path = root + "/" + rel;
         const std::string dir = path.substr(0, path.rfind('/'));
         for (size_t i = 1; i <= dir.size(); i++)
             if (i == dir.size() || dir[i] == '/') mkdir(dir.substr(0, i).c_str(), 0777);
-        if (!write_bmp_gray(path, img.data(), PWs, PHs)) return fail(SL3D_E_INVALID_ARG, "cannot write " + path);
+        if (!sl3d_io::write_bmp_gray(path, img.data(), PWs, PHs)) return fail(SL3D_E_INVALID_ARG, "cannot write " + path);
         return true;
     };
     for (int axis = 0; axis < 2; axis++) {
-        const std::string ax = axis_dir(axis);
-        const int N = axis == 0 ? number_of_patterns_binary_vertical : number_of_patterns_binary_horizontal;
+        const std::string ax = kAxis[axis].dir;
         for (int i = 0; i < number_of_patterns_fringe; i++)  // :419-431
             if (!emit(SL3D_PATTERN_FRINGE, axis, i, "Fringe_patterns/" + ax + "/Pattern_" + std::to_string(i) + ".bmp")) return;
-        for (int j = 0; j < N + 1; j++) {  // :433-465: one image more than there are bit planes
+        for (int j = 0; j < kAxis[axis].n_gray + 1; j++) {  // :433-465: one image more than there are bit planes
             if (!emit(SL3D_PATTERN_BINARY, axis, j, "Coded_patterns/Binary_coded/" + ax + "/Pattern_" + std::to_string(j) + ".bmp")) return;
             if (!emit(SL3D_PATTERN_GRAY, axis, j, "Coded_patterns/Gray_coded/" + ax + "/Pattern_" + std::to_string(j) + ".bmp")) return;
             if (!emit(SL3D_PATTERN_INVERSE_GRAY, axis, j, "Coded_patterns/Gray_coded/" + ax + "/inverse_Pattern_" + std::to_string(j) + ".bmp")) return;
@@ -875,15 +707,12 @@ try {
     g.status = SL3D_OK;
     if (pattern_type != 0 && pattern_type != 1) return;
     if (!ensure_ctx()) return;
+    const Axis &axis = kAxis[pattern_type];
     const int F = number_of_patterns_fringe;
     std::vector<Frame> img;
     std::vector<std::vector<std::string>> names((size_t)F);
-    char name[256], alt[256];
-    for (int i = 0; i < F; i++) {  // read_image: the F fringe frames of this axis (3/wrapped_phase.cpp:29-58); stage 4 brings the Gray / inverse frames
-        snprintf(name, sizeof name, "Captured_patterns/Fringe_patterns/%s/Undistorted/Captured_image_%d.bmp", axis_dir(pattern_type), i);
-        snprintf(alt, sizeof alt, "Captured_patterns/Fringe_patterns/%s/Undistorted/Gray_captured_image_%d.bmp", axis_dir(pattern_type), i);
-        names[(size_t)i] = {name, alt};
-    }
+    // read_image: the F fringe frames of this axis (3/wrapped_phase.cpp:29-58); stage 4 brings the Gray / inverse frames
+    for (int i = 0; i < F; i++) names[(size_t)i] = capture_names("Fringe_patterns", axis, "", i);
     if (g.ctx_deferred) {
         // deferred: the mask (once per scan: main() calls image_scissor once, m_tech_project_console.cpp:366) and this axis' fringe
         // frames go to the GPU; nothing is computed and no global is touched until triangulate()
@@ -896,26 +725,17 @@ try {
         upload_planes(img, pattern_type, 0);
         return;
     }
-    // the reference allocates these with new[] on every call and never frees them (3/wrapped_phase.cpp:410-424)
-    int (*&vm)[Camera_imageheight] = pattern_type == 0 ? valid_map_vertical : valid_map_horizontal;
-    float (*&wp)[Camera_imageheight] = pattern_type == 0 ? wrapped_phi_vertical : wrapped_phi_horizontal;
-    if (!vm) vm = (int (*)[Camera_imageheight])alloc_global<int>((size_t)W * H);
-    if (!wp) wp = (float (*)[Camera_imageheight])alloc_global<float>((size_t)W * H);
+    ensure_global(axis.valid, (size_t)W * H);
+    ensure_global(axis.wrapped, (size_t)W * H);
 
     if (!upload_mask()) return;  // selected_region (image_scissor, m_tech_project_console.cpp:146-238)
     if (!load_frames(names, img)) return;
     if (!upload_planes(img, pattern_type, 0)) return;
-    if (!each_part("sl3d_compute_wrapped_phase", [&](const Part &p) { return sl3d_compute_wrapped_phase(p.ctx, 0, pattern_type); })) return;
+    if (!each_part("sl3d_compute_wrapped_phase", [&](sl3d_ctx *c, const Part &) { return sl3d_compute_wrapped_phase(c, 0, pattern_type); })) return;
 
-    if (!fetch_global<uint8_t>("valid map", pattern_type == 0 ? SL3D_G_VALID_V : SL3D_G_VALID_H, vm,
-                               [&](const Part &q, uint8_t *d) { return sl3d_get_valid_map(q.ctx, 0, pattern_type, d, W); })) return;
-    if (!fetch_global<float>("wrapped phase", pattern_type == 0 ? SL3D_G_WRAPPED_V : SL3D_G_WRAPPED_H, wp,
-                             [&](const Part &q, float *d) { return sl3d_get_wrapped_phase(q.ctx, 0, pattern_type, d, W); })) return;
-    if (g.write_debug) {  // save_wrapped_image :346
-        std::vector<uint8_t> d((size_t)W * H);
-        if (each_part("sl3d_get_debug_image", [&](const Part &q) { return sl3d_get_debug_image(q.ctx, 0, 3, pattern_type, d.data() + (size_t)q.row0 * W, W); }))
-            write_bmp_gray(data_root() + "/Wrapped_phase_images/" + axis_dir(pattern_type) + "/Wrapped_phase_image.bmp", d.data());
-    }
+    if (!fetch_global<uint8_t>("valid map", axis.id_valid, flat(axis.valid), [&](sl3d_ctx *c, uint8_t *d) { return sl3d_get_valid_map(c, 0, pattern_type, d, W); })) return;
+    if (!fetch_global<float>("wrapped phase", axis.id_wrapped, flat(axis.wrapped), [&](sl3d_ctx *c, float *d) { return sl3d_get_wrapped_phase(c, 0, pattern_type, d, W); })) return;
+    if (g.write_debug) write_debug_image(3, pattern_type);
 }
 SHIM_CATCH("compute_wrapped_phase")
 
@@ -926,28 +746,20 @@ try {
     if (pattern_type != 0 && pattern_type != 1) return;
     if (!g.ctx) { fail(SL3D_E_STATE, "unwrap_phase before compute_wrapped_phase"); return; }
     if (g.ctx_deferred && !open_deferred_scan()) return;
-    int (*&code)[Camera_imageheight] = pattern_type == 0 ? code_vertical : code_horizontal;
-    float (*&uw)[Camera_imageheight] = pattern_type == 0 ? unwrapped_phi_vertical : unwrapped_phi_horizontal;
-    float (*&wp)[Camera_imageheight] = pattern_type == 0 ? wrapped_phi_vertical : wrapped_phi_horizontal;
+    const Axis &axis = kAxis[pattern_type];
     if (!g.ctx_deferred) {
-        if (!code) code = (int (*)[Camera_imageheight])alloc_global<int>((size_t)W * H);     // 4/phase_unwrap.cpp:373-376
-        if (!uw) uw = (float (*)[Camera_imageheight])alloc_global<float>((size_t)W * H);     // :282 / :300
+        ensure_global(axis.code, (size_t)W * H);
+        ensure_global(axis.unwrapped, (size_t)W * H);
     }
 
     // read_captured_images :51-131: N Gray + N inverse-Gray frames (frame index N is loaded there but never used); the fringe
     // frames of the axis are resident since stage 3
-    const int F = number_of_patterns_fringe;
-    const int N = pattern_type == 0 ? number_of_patterns_binary_vertical : number_of_patterns_binary_horizontal;
+    const int F = number_of_patterns_fringe, N = axis.n_gray;
     std::vector<Frame> img;
     std::vector<std::vector<std::string>> names((size_t)(2 * N));
-    char name[256], alt[256];
     for (int i = 0; i < N; i++) {
-        snprintf(name, sizeof name, "Captured_patterns/Coded_patterns/Gray_coded/%s/Undistorted/Captured_image_%d.bmp", axis_dir(pattern_type), i);
-        snprintf(alt, sizeof alt, "Captured_patterns/Coded_patterns/Gray_coded/%s/Undistorted/Gray_captured_image_%d.bmp", axis_dir(pattern_type), i);
-        names[(size_t)i] = {name, alt};
-        snprintf(name, sizeof name, "Captured_patterns/Coded_patterns/Gray_coded/%s/Undistorted/inverse_Captured_image_%d.bmp", axis_dir(pattern_type), i);
-        snprintf(alt, sizeof alt, "Captured_patterns/Coded_patterns/Gray_coded/%s/Undistorted/inverse_Gray_captured_image_%d.bmp", axis_dir(pattern_type), i);
-        names[(size_t)(N + i)] = {name, alt};
+        names[(size_t)i] = capture_names("Coded_patterns/Gray_coded", axis, "", i);
+        names[(size_t)(N + i)] = capture_names("Coded_patterns/Gray_coded", axis, "inverse_", i);
     }
     if (g.ctx_deferred) {  // deferred: the Gray / inverse frames of this axis go to the GPU, nothing else happens here
         if (!load_frames(names, img, axis_slot0(pattern_type) + (size_t)F, scan_slots())) return;
@@ -956,22 +768,13 @@ try {
     }
     if (!load_frames(names, img)) return;
     if (N > 0 && !upload_planes(img, pattern_type, F)) return;
-    if (!each_part("sl3d_unwrap_phase", [&](const Part &q) { return sl3d_unwrap_phase(q.ctx, 0, pattern_type); })) return;
+    if (!each_part("sl3d_unwrap_phase", [&](sl3d_ctx *c, const Part &) { return sl3d_unwrap_phase(c, 0, pattern_type); })) return;
 
-    if (!fetch_global<int32_t>("code", pattern_type == 0 ? SL3D_G_CODE_V : SL3D_G_CODE_H, code,
-                               [&](const Part &q, int32_t *d) { return sl3d_get_code(q.ctx, 0, pattern_type, d, W); })) return;
-    if (!fetch_global<float>("unwrapped phase", pattern_type == 0 ? SL3D_G_UNWRAPPED_V : SL3D_G_UNWRAPPED_H, uw,
-                             [&](const Part &q, float *d) { return sl3d_get_unwrapped_phase(q.ctx, 0, pattern_type, d, W); })) return;
+    if (!fetch_global<int32_t>("code", axis.id_code, flat(axis.code), [&](sl3d_ctx *c, int32_t *d) { return sl3d_get_code(c, 0, pattern_type, d, W); })) return;
+    if (!fetch_global<float>("unwrapped phase", axis.id_unwrapped, flat(axis.unwrapped), [&](sl3d_ctx *c, float *d) { return sl3d_get_unwrapped_phase(c, 0, pattern_type, d, W); })) return;
     // stage 4 shifts wrapped_phi in place by +Pi (:290, :308)
-    if (wp && !fetch_global<float>("wrapped phase", pattern_type == 0 ? SL3D_G_WRAPPED_V : SL3D_G_WRAPPED_H, wp,
-                                   [&](const Part &q, float *d) { return sl3d_get_wrapped_phase(q.ctx, 0, pattern_type, d, W); })) return;
-    if (g.write_debug) {       // save_unwrap_phase_image :321-364
-        std::vector<uint8_t> d((size_t)W * H);
-        if (each_part("sl3d_get_debug_image", [&](const Part &q) { return sl3d_get_debug_image(q.ctx, 0, 4, pattern_type, d.data() + (size_t)q.row0 * W, W); }))
-            write_bmp_gray(data_root() + (pattern_type == 0 ? "/Unwrapped_phase_images/Gray_coded/Vertical/Unwrapped_phase_vertical.bmp"
-                                                            : "/Unwrapped_phase_images/Gray_coded/Horizontal/Unwrapped_phase_horizontal.bmp"),
-                           d.data());
-    }
+    if (axis.wrapped && !fetch_global<float>("wrapped phase", axis.id_wrapped, flat(axis.wrapped), [&](sl3d_ctx *c, float *d) { return sl3d_get_wrapped_phase(c, 0, pattern_type, d, W); })) return;
+    if (g.write_debug) write_debug_image(4, pattern_type);
 }
 SHIM_CATCH("unwrap_phase")
 
@@ -981,14 +784,11 @@ try {
     g.status = SL3D_OK;
     if (!g.ctx) { fail(SL3D_E_STATE, "compute_c_p_map before the phase stages"); return; }
     if (g.ctx_deferred) return;  // deferred: stage 5 is part of triangulate()'s one launch
-    if (!valid_map) valid_map = (int (*)[Camera_imageheight])alloc_global<int>((size_t)W * H);  // 5/compute_correspondance.cpp:635
-    if (!c_p_map) c_p_map = (long int (*)[2])alloc_global<long int>((size_t)total_camera_pixels * 2);  // :640
-    if (!each_part("sl3d_compute_c_p_map", [&](const Part &q) { return sl3d_compute_c_p_map(q.ctx, 0); })) return;
-    if (!fetch_global<uint8_t>("valid map", SL3D_G_VALID, valid_map,
-                               [&](const Part &q, uint8_t *d) { return sl3d_get_valid_map(q.ctx, 0, SL3D_VALID_MERGED, d, W); })) return;
-    static_assert(sizeof(long int) == sizeof(int64_t), "c_p_map is long[ ][2] on LP64");
-    // c_p_map is indexed [row*W + col] in the reference too (common_variables.h:15): the row-major plane is the global
-    each_part("sl3d_get_c_p_map", [&](const Part &q) { return sl3d_get_c_p_map(q.ctx, 0, (int64_t *)c_p_map + 2 * (size_t)q.row0 * W); });
+    ensure_global(valid_map, (size_t)W * H);
+    ensure_global(c_p_map, (size_t)total_camera_pixels * 2);
+    if (!each_part("sl3d_compute_c_p_map", [&](sl3d_ctx *c, const Part &) { return sl3d_compute_c_p_map(c, 0); })) return;
+    if (!fetch_global<uint8_t>("valid map", SL3D_G_VALID, flat(valid_map), [&](sl3d_ctx *c, uint8_t *d) { return sl3d_get_valid_map(c, 0, SL3D_VALID_MERGED, d, W); })) return;
+    fetch_c_p_map(TIMED);
 }
 SHIM_CATCH("compute_c_p_map")
 
@@ -1002,31 +802,25 @@ try {
     // (T0 and the per-calibration tables are rebuilt only when a number changed: the reference re-reads the same 8 files every scan)
     if (!g.cal_valid || memcmp(cal, g.cal, sizeof cal) != 0) {
         g.cal_valid = false;
-        if (!each_part("sl3d_set_calibration", [&](const Part &q) { return set_cal(q.ctx, cal); })) return;
+        if (!each_part("sl3d_set_calibration", [&](sl3d_ctx *c, const Part &) { return set_cal(c, cal); })) return;
         memcpy(g.cal, cal, sizeof cal);
         g.cal_valid = true;
     }
     if (g.ctx_deferred) {
         // deferred: stages 3(v) 3(h) 4(v) 4(h) 5 7 as ONE launch of the timed fused kernel on the frames the stage calls brought up
         // (the launch the C ABI's sl3d_run makes: the same kernel bench.py times), then only the globals the mask names
-        const bool launched = each_part("sl3d_run", [&](const Part &q) { return sl3d_run(q.ctx, 0, 1); });
-        g.scan_open = g.mask_fresh = false;  // (this scan is over whatever happened: EVERY exit of triangulate() -- fail() does the same)
+        const bool launched = each_part("sl3d_run", [&](sl3d_ctx *c, const Part &) { return sl3d_run(c, 0, 1); });
+        abandon_scan();  // (this scan is over whatever happened: EVERY exit of triangulate() leaves no scan open)
         if (!launched) return;
         g.scan_done = true;
         if (g.globals_mask && !fill_globals(g.globals_mask)) return;
         if (g.write_debug) write_deferred_debug_images();
         return;
     }
-    if (!intersection_points) intersection_points = (double (*)[Camera_imageheight][3])alloc_global<double>((size_t)W * H * 3);  // :1513
-    if (!each_part("sl3d_triangulate", [&](const Part &q) { return sl3d_triangulate(q.ctx, 0); })) return;
-    if (!g.host_transpose) {
-        each_part("sl3d_get_global_colrow", [&](const Part &q) { return sl3d_get_global_colrow(q.ctx, 0, SL3D_G_INTERSECTION_POINTS, intersection_points, H, q.row0); });
-        return;
-    }
-    std::vector<double> pts((size_t)W * H * 3);
-    if (!each_part("sl3d_get_intersection_points", [&](const Part &q) { return sl3d_get_intersection_points(q.ctx, 0, pts.data() + 3 * (size_t)q.row0 * W); })) return;
-    for (int r = 0; r < H; r++)
-        for (int c = 0; c < W; c++) memcpy(intersection_points[c][r], &pts[3 * ((size_t)r * W + c)], 3 * sizeof(double));
+    ensure_global(intersection_points, (size_t)W * H * 3);
+    if (!each_part("sl3d_triangulate", [&](sl3d_ctx *c, const Part &) { return sl3d_triangulate(c, 0); })) return;
+    fetch_global<double, 3>("sl3d_get_global_colrow", SL3D_G_INTERSECTION_POINTS, flat(intersection_points),
+                            [&](sl3d_ctx *c, double *d) { return sl3d_get_intersection_points(c, 0, d); }, "sl3d_get_intersection_points");
 }
 SHIM_CATCH("triangulate")
 
@@ -1052,7 +846,7 @@ try {
         if (it != g.images.end() && it->second.width == W && it->second.height == H && it->second.channels == 3) {
             tex = it->second.data;
             tex_stride = it->second.stride;
-        } else if (read_bmp_bgr(data_root() + "/Point_cloud/texture.bmp", tex_store)) {
+        } else if (sl3d_io::read_bmp_bgr(data_root() + "/Point_cloud/texture.bmp", W, H, tex_store)) {
             tex = tex_store.data();
         } else {
             fail(SL3D_E_INVALID_ARG, "cannot read " + data_root() + "/Point_cloud/texture.bmp (8/24-bit BMP of the camera size)");
@@ -1060,72 +854,32 @@ try {
         }
     }
     pt.lap("texture read");
-    if (!each_part("sl3d_set_texture", [&](const Part &q) { return sl3d_set_texture(q.ctx, 0, tex + (size_t)q.row0 * tex_stride, tex_stride); })) return;
+    if (!each_part("sl3d_set_texture", [&](sl3d_ctx *c, const Part &q) { return sl3d_set_texture(c, 0, tex + (size_t)q.row0 * tex_stride, tex_stride); })) return;
     pt.lap("texture upload");
     // the parts' clouds one after the other: stripe order = row order = the scan order of :85-104
     int64_t n = 0;
     std::vector<int64_t> cnt(g.parts.size(), 0);
     size_t k = 0;
-    if (!each_part("sl3d_get_cloud_rgb", [&](const Part &q) { const int rc = sl3d_get_cloud_rgb(q.ctx, 0, nullptr, nullptr, 0, &cnt[k]); n += cnt[k++]; return rc; })) return;
+    if (!each_part("sl3d_get_cloud_rgb", [&](sl3d_ctx *c, const Part &) { const int rc = sl3d_get_cloud_rgb(c, 0, nullptr, nullptr, 0, &cnt[k]); n += cnt[k++]; return rc; })) return;
     std::vector<float> &xyz = g.cloud_xyz;
     std::vector<uint8_t> &rgb = g.cloud_rgb;
     xyz.resize((size_t)n * 3);
     rgb.resize((size_t)n * 3);
     int64_t off = 0;
     k = 0;
-    if (!each_part("sl3d_get_cloud_rgb", [&](const Part &q) {
+    if (!each_part("sl3d_get_cloud_rgb", [&](sl3d_ctx *c, const Part &) {
             int64_t m = 0;
-            const int rc = sl3d_get_cloud_rgb(q.ctx, 0, xyz.data() + 3 * off, rgb.data() + 3 * off, cnt[k], &m);
+            const int rc = sl3d_get_cloud_rgb(c, 0, xyz.data() + 3 * off, rgb.data() + 3 * off, cnt[k], &m);
             off += cnt[k++];
             return rc;
         }))
         return;
     pt.lap("compaction + download");
     mkdir((data_root() + "/Point_cloud").c_str(), 0777);
-    const std::string base = data_root() + "/Point_cloud/point_cloud_" + std::to_string(cloud_index);
-    char hdr[512];
-    snprintf(hdr, sizeof hdr, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F U\nCOUNT 1 1 1 1\n"
-                              "WIDTH %lld\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %lld\nDATA %s\n", (long long)n, (long long)n, g.binary_clouds ? "binary" : "ascii");
-    const std::string pcd_header = hdr;
-    snprintf(hdr, sizeof hdr, "ply\nformat %s 1.0\ncomment generated by sl3d (3dscan_amd)\nelement vertex %lld\nproperty float x\nproperty float y\n"
-                              "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
-             g.binary_clouds ? "binary_little_endian" : "ascii", (long long)n);
-    const std::string ply_header = hdr;
-    // The pieces of both files are produced on all host threads; then the two files go out side by side, a write() loop each.
-    // (Writers that start on the finished pieces while the rest is still being formatted were measured too: they compete with the
-    // formatting threads for the container's CPU quota -- 97 against 83 ms per save.)
-    std::vector<std::string> &pcd_rows = g.pcd_rows, &ply_rows = g.ply_rows;
-    const int parts = g.binary_clouds ? (int)std::max<int64_t>(1, std::min<int64_t>((n + 65535) / 65536, 4 * usable_threads())) : cloud_parts(n);
-    pcd_rows.resize((size_t)parts);
-    ply_rows.resize((size_t)parts);
-    if (g.binary_clouds) {
-        // fixed-size records: PCD x y z + packed rgb (16 bytes), PLY x y z + r g b (15 bytes), little endian
-        parallel_for(parts, [&](int k) {
-            const int64_t a = n * k / parts, b = n * (k + 1) / parts;
-            std::string &pc = pcd_rows[(size_t)k], &pl = ply_rows[(size_t)k];
-            pc.resize((size_t)(b - a) * 16);
-            pl.resize((size_t)(b - a) * 15);
-            for (int64_t i = a; i < b; i++) {
-                const uint32_t packed = ((uint32_t)rgb[3 * i] << 16) | ((uint32_t)rgb[3 * i + 1] << 8) | (uint32_t)rgb[3 * i + 2];
-                memcpy(&pc[(size_t)(i - a) * 16], &xyz[3 * i], 12);
-                memcpy(&pc[(size_t)(i - a) * 16 + 12], &packed, 4);
-                memcpy(&pl[(size_t)(i - a) * 15], &xyz[3 * i], 12);
-                memcpy(&pl[(size_t)(i - a) * 15 + 12], &rgb[3 * i], 3);
-            }
-        });
-    } else {
-        format_cloud(xyz.data(), rgb.data(), n, &pcd_rows, &ply_rows);
-    }
-    pt.lap("format");
-    bool pcd_ok = false;
-    std::thread pcd_writer([&] { pcd_ok = write_pieces(base + ".pcd", pcd_header, pcd_rows); });
-    const bool ply_ok = write_pieces(base + ".ply", ply_header, ply_rows);
-    pcd_writer.join();
-    pt.lap("write pcd + ply");
+    const std::string base = data_root() + "/Point_cloud/point_cloud_" + std::to_string(cloud_index), pcd_path = base + ".pcd", ply_path = base + ".ply";
+    const bool written = write_cloud_files(xyz.data(), rgb.data(), n, &pcd_path, ply_path, &pt);
     pt.print("save_point_cloud");
-    if (!pcd_ok) { fail(SL3D_E_INVALID_ARG, "cannot write " + base + ".pcd"); return; }
-    if (!ply_ok) { fail(SL3D_E_INVALID_ARG, "cannot write " + base + ".ply"); return; }
-    fprintf(stderr, "Saved %lld data points to %s.pcd / .ply\n", (long long)n, base.c_str());
+    if (written) fprintf(stderr, "Saved %lld data points to %s.pcd / .ply\n", (long long)n, base.c_str());
 }
 SHIM_CATCH("save_point_cloud")
 
@@ -1133,11 +887,8 @@ SHIM_CATCH("save_point_cloud")
 // ---- stage 9: register_point_clouds() -------------------------------------------------------------------
 // 9/register_point_clouds.cpp:23-155: Point_cloud/point_cloud_<i>.ply, i = 0..n-1, each rotated about the Y axis through
 // (tx,ty,tz) by theta_i (theta_0 = 0, theta_{i+1} = theta_i + rot_step in float, degrees with Pi = 22/7), colours kept,
-// concatenated into Point_cloud/registered_point_cloud.ply.  Reads the ASCII PLY files save_point_cloud() writes (vertex
+// concatenated into Point_cloud/registered_point_cloud.ply.  Reads the PLY files save_point_cloud() writes, ASCII or binary (vertex
 // properties x y z [red green blue] in any order, other properties ignored); the rotation runs on the device.
-using sl3d_io::PlyCloud;
-using sl3d_io::read_ply;
-
 void register_point_clouds(unsigned num_point_clouds, float tx, float ty, float tz, float rot_step)
 try {
     g.status = SL3D_OK;
@@ -1146,33 +897,16 @@ try {
     std::vector<uint8_t> all_rgb;
     float theta = 0.0;  // :79
     for (unsigned i = 0; i < num_point_clouds; i++) {
-        PlyCloud c;
+        sl3d_io::PlyCloud c;
         const std::string path = data_root() + "/Point_cloud/point_cloud_" + std::to_string(i) + ".ply";
-        if (!read_ply(path, c)) { fail(SL3D_E_INVALID_ARG, "cannot read " + path + " (ASCII or binary_little_endian PLY with x y z vertex properties)"); return; }
+        if (!sl3d_io::read_ply(path, c)) { fail(SL3D_E_INVALID_ARG, "cannot read " + path + " (ASCII or binary_little_endian PLY with x y z vertex properties)"); return; }
         const int64_t n = (int64_t)c.xyz.size() / 3;
         std::vector<float> out((size_t)n * 3);
-        if (!ok(sl3d_transform_cloud(g.ctx, c.xyz.data(), n, theta, tx, ty, tz, out.data()), "sl3d_transform_cloud")) return;
+        if (!ok(sl3d_transform_cloud(g.ctx, c.xyz.data(), n, theta, tx, ty, tz, out.data()), "sl3d_transform_cloud", g.ctx)) return;
         all_xyz.insert(all_xyz.end(), out.begin(), out.end());
         all_rgb.insert(all_rgb.end(), c.rgb.begin(), c.rgb.end());
         theta += rot_step;  // :145
     }
-    const std::string outp = data_root() + "/Point_cloud/registered_point_cloud.ply";
-    const long long n = (long long)all_xyz.size() / 3;
-    char hdr[512];
-    snprintf(hdr, sizeof hdr, "ply\nformat %s 1.0\ncomment generated by sl3d (3dscan_amd)\nelement vertex %lld\nproperty float x\nproperty float y\n"
-                              "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
-             g.binary_clouds ? "binary_little_endian" : "ascii", n);
-    std::vector<std::string> rows;
-    if (g.binary_clouds) {
-        rows.assign(1, std::string());
-        rows[0].resize((size_t)n * 15);
-        for (long long i = 0; i < n; i++) {
-            memcpy(&rows[0][15 * (size_t)i], &all_xyz[3 * i], 12);
-            memcpy(&rows[0][15 * (size_t)i + 12], &all_rgb[3 * i], 3);
-        }
-    } else {
-        format_cloud(all_xyz.data(), all_rgb.data(), (int64_t)n, nullptr, &rows);
-    }
-    if (!write_pieces(outp, hdr, rows)) { fail(SL3D_E_INVALID_ARG, "cannot write " + outp); return; }
+    write_cloud_files(all_xyz.data(), all_rgb.data(), (int64_t)all_xyz.size() / 3, nullptr, data_root() + "/Point_cloud/registered_point_cloud.ply");
 }
 SHIM_CATCH("register_point_clouds")

@@ -1,20 +1,29 @@
-// sl3d_shim_io.h -- the file readers of the drop-in shim (sl3d_shim.cpp), on their own: plain C++17, no HIP, no shim state, so that
-// the test suite can compile them with -fsanitize=address,undefined and feed them truncated / oversized / garbage files
-// (tests/native/shim_io_check.cpp, tests/test_shim_io.py).
+// sl3d_shim_io.h -- the file readers and writers of the drop-in shim (sl3d_shim.cpp), on their own: plain C++17, no HIP, no shim state,
+// so that the test suite can compile them with -fsanitize=address,undefined, feed the readers truncated / oversized / garbage files
+// and hold the writers to their formats byte for byte (tests/native/shim_io_check.cpp, tests/test_shim_io.py).
 //   read_bmp_gray / read_bmp_bgr : what cvLoadImage yields for the reference's BMP files (3/wrapped_phase.cpp:44,
 //                                  4/phase_unwrap.cpp:78,84, 8/save_point_cloud.cpp:46)
 //   parse_xml_matrix             : the numbers of an OpenCV XML matrix (cvReadByName, 7/triangulation.cpp:152-168,1069-1083)
 //   read_ply                     : the vertex list of Point_cloud/point_cloud_<i>.ply (9/register_point_clouds.cpp:83-128)
+//   write_bmp_gray               : what cvSaveImage writes for a 1-channel image (1/pattern_generator.cpp:414-470, the debug images)
+//   pcd_header / ply_header, append_cloud_rows / pack_cloud_records, cloud_pieces, format_cloud, write_pieces :
+//                                  the cloud files of 8/save_point_cloud.cpp:211-217 and 9/register_point_clouds.cpp, ASCII or binary
 // Every size a file CLAIMS is checked against the bytes the file HAS before anything is allocated or read with it: a malformed file
 // is a `false`, never an allocation of its header's vertex count or a read through its header's offsets.
 #pragma once
+#include <algorithm>
+#include <charconv>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fcntl.h>
 #include <string>
+#include <unistd.h>
 #include <vector>
+
+#include "sl3d_shim_pool.h"
 
 namespace sl3d_io {
 
@@ -238,12 +247,160 @@ inline bool read_ply(const std::string &path, PlyCloud &c)
             for (size_t i = 0; i < props.size(); i++)
                 if (fscanf(in.f, "%lf", &v[i]) != 1) return false;
         }
-        // (a double beyond the float range becomes +-inf by saturation, not by an out-of-range conversion)
-        auto f32 = [](double x) { return std::fabs(x) > 3.4028234663852886e38 ? (x > 0 ? HUGE_VALF : -HUGE_VALF) : (float)x; };
+        // (a double beyond the float range becomes +-inf by saturation, not by an out-of-range conversion; the range ends half an ulp
+        // above FLT_MAX, so that the nine digits of FLT_MAX itself, 3.40282347e+38, read back as FLT_MAX)
+        auto f32 = [](double x) { return std::fabs(x) >= 0x1.ffffffp127 ? (x > 0 ? HUGE_VALF : -HUGE_VALF) : (float)x; };
         c.xyz[3 * p] = f32(v[ix]); c.xyz[3 * p + 1] = f32(v[iy]); c.xyz[3 * p + 2] = f32(v[iz]);
         if (ir >= 0 && ig >= 0 && ib >= 0) { c.rgb[3 * p] = u8(v[ir]); c.rgb[3 * p + 1] = u8(v[ig]); c.rgb[3 * p + 2] = u8(v[ib]); }
     }
     return true;
+}
+
+// 8-bit palettised BMP exactly as the reference's cvSaveImage (OpenCV 2.4 BMP encoder) writes a 1-channel image:
+// 14 + 40 byte headers with biSizeImage = biClrUsed = 0, 256 grey palette entries, bottom-up rows padded to 4 bytes.
+// (tests/test_gpu_shim.py compares whole files with the SHA-256 of the reference's own pattern images.)
+inline bool write_bmp_gray(const std::string &path, const uint8_t *img, int w, int h)
+{
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const uint32_t rowbytes = ((uint32_t)w + 3) & ~3u, off = 54 + 1024, size = off + rowbytes * h;
+    uint8_t hdr[54] = {0};
+    auto put32 = [&](int o, uint32_t v) { hdr[o] = v & 255; hdr[o + 1] = (v >> 8) & 255; hdr[o + 2] = (v >> 16) & 255; hdr[o + 3] = v >> 24; };
+    hdr[0] = 'B'; hdr[1] = 'M';
+    put32(2, size); put32(10, off); put32(14, 40); put32(18, w); put32(22, h);
+    hdr[26] = 1; hdr[28] = 8;
+    fwrite(hdr, 1, 54, f);
+    for (int i = 0; i < 256; i++) { uint8_t q[4] = {(uint8_t)i, (uint8_t)i, (uint8_t)i, 0}; fwrite(q, 1, 4, f); }
+    std::vector<uint8_t> row(rowbytes, 0);
+    for (int y = h - 1; y >= 0; y--) { memcpy(row.data(), img + (size_t)y * w, w); fwrite(row.data(), 1, rowbytes, f); }
+    fclose(f);
+    return true;
+}
+
+// The cloud files are standard PCD v0.7 (fields x y z rgb, rgb as the packed 0x00RRGGBB integer) and PLY (x y z red green blue),
+// in their ASCII or their binary flavour ("DATA binary", "binary_little_endian").
+inline std::string pcd_header(int64_t n, bool binary)
+{
+    char hdr[512];
+    snprintf(hdr, sizeof hdr, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F U\nCOUNT 1 1 1 1\n"
+                              "WIDTH %lld\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %lld\nDATA %s\n", (long long)n, (long long)n, binary ? "binary" : "ascii");
+    return hdr;
+}
+inline std::string ply_header(int64_t n, bool binary)
+{
+    char hdr[512];
+    snprintf(hdr, sizeof hdr, "ply\nformat %s 1.0\ncomment generated by sl3d (3dscan_amd)\nelement vertex %lld\nproperty float x\nproperty float y\n"
+                              "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
+             binary ? "binary_little_endian" : "ascii", (long long)n);
+    return hdr;
+}
+
+inline uint32_t packed_rgb(const uint8_t *c) { return ((uint32_t)c[0] << 16) | ((uint32_t)c[1] << 8) | (uint32_t)c[2]; }
+
+// The ASCII cloud rows of the reference's PCL writers (8/save_point_cloud.cpp:211-217), built in memory: std::to_chars with
+// chars_format::general and precision 9 yields the digits of printf("%.9g") (the C++17 contract), several times faster than a
+// fprintf per point.  The float -> text conversion is what costs, and the PCD and the PLY row of a point share their "x y z "
+// text: it is formatted ONCE and appended to both (pcd / ply may be NULL); the PCD row ends with the packed colour, the PLY row
+// with "red green blue".
+inline void append_cloud_rows(std::string *pcd, std::string *ply, const float *xyz, const uint8_t *rgb, int64_t first, int64_t n)
+{
+    // rows are written straight into the strings' storage through raw pointers (a row is at most 3 * 16 + 12 bytes), and the
+    // strings are cut to their real length at the end: no per-value append
+    constexpr size_t kRowMax = 64;
+    const size_t pcd0 = pcd ? pcd->size() : 0, ply0 = ply ? ply->size() : 0;
+    if (pcd) pcd->resize(pcd0 + (size_t)n * kRowMax);
+    if (ply) ply->resize(ply0 + (size_t)n * kRowMax);
+    char *pc = pcd ? &(*pcd)[pcd0] : nullptr, *pl = ply ? &(*ply)[ply0] : nullptr;
+    char buf[64];
+    for (int64_t i = first; i < first + n; i++) {
+        char *p = buf;
+        for (int k = 0; k < 3; k++) {
+            p = std::to_chars(p, buf + sizeof buf, xyz[3 * i + k], std::chars_format::general, 9).ptr;
+            *p++ = ' ';
+        }
+        const size_t len = (size_t)(p - buf);
+        if (pc) {
+            memcpy(pc, buf, len);
+            pc = std::to_chars(pc + len, pc + len + 12, packed_rgb(rgb + 3 * i)).ptr;
+            *pc++ = '\n';
+        }
+        if (pl) {
+            memcpy(pl, buf, len);
+            pl += len;
+            for (int k = 0; k < 3; k++) {
+                pl = std::to_chars(pl, pl + 4, (unsigned)rgb[3 * i + k]).ptr;
+                *pl++ = k < 2 ? ' ' : '\n';
+            }
+        }
+    }
+    if (pcd) pcd->resize((size_t)(pc - pcd->data()));
+    if (ply) ply->resize((size_t)(pl - ply->data()));
+}
+
+// The binary records of points [first, first + n), little endian: PCD x y z + packed colour (16 bytes), PLY x y z + r g b (15 bytes).
+// The strings are SET to the records (pcd / ply may be NULL): one that already has their size is not touched before it is filled.
+inline void pack_cloud_records(std::string *pcd, std::string *ply, const float *xyz, const uint8_t *rgb, int64_t first, int64_t n)
+{
+    if (pcd) pcd->resize((size_t)n * 16);
+    if (ply) ply->resize((size_t)n * 15);
+    for (int64_t i = first; i < first + n; i++) {
+        const size_t k = (size_t)(i - first);
+        if (pcd) {
+            const uint32_t packed = packed_rgb(rgb + 3 * i);
+            memcpy(&(*pcd)[k * 16], xyz + 3 * i, 12);
+            memcpy(&(*pcd)[k * 16 + 12], &packed, 4);
+        }
+        if (ply) {
+            memcpy(&(*ply)[k * 15], xyz + 3 * i, 12);
+            memcpy(&(*ply)[k * 15 + 12], rgb + 3 * i, 3);
+        }
+    }
+}
+
+// into how many pieces a cloud of n points is cut: `piece` points each, at most four per thread, at least one
+inline int cloud_pieces(int64_t n, int64_t piece, int threads = sl3d_pool::usable_threads())
+{
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + piece - 1) / piece, 4 * (int64_t)threads));
+}
+
+// The contents of both files of a whole cloud (either may be NULL), rows or records: disjoint point ranges are formatted on all host
+// threads into their own buffers; concatenated in order they are byte for byte what one loop over all points writes.  A text piece
+// takes 16,384 points, a piece of records 65,536.
+inline void format_cloud(const float *xyz, const uint8_t *rgb, int64_t n, bool binary, std::vector<std::string> *pcd, std::vector<std::string> *ply,
+                         int threads = sl3d_pool::usable_threads())
+{
+    const int pieces = cloud_pieces(n, binary ? 65536 : 16384, threads);
+    // (resize + clear: a buffer that is being reused keeps its capacity, i.e. its already-touched pages)
+    if (pcd) pcd->resize((size_t)pieces);
+    if (ply) ply->resize((size_t)pieces);
+    sl3d_pool::parallel_for(pieces, [&](int k) {
+        const int64_t a = n * k / pieces, b = n * (k + 1) / pieces;
+        std::string *pc = pcd ? &(*pcd)[(size_t)k] : nullptr, *pl = ply ? &(*ply)[(size_t)k] : nullptr;
+        if (binary) return pack_cloud_records(pc, pl, xyz, rgb, a, b - a);
+        if (pc) pc->clear();
+        if (pl) pl->clear();
+        append_cloud_rows(pc, pl, xyz, rgb, a, b - a);
+    }, threads);
+}
+
+// header + pieces -> one file, in order.  (Giving the file its final size, mapping it and letting every thread copy its pieces in
+// was measured too: on the GPU boxes' overlay file system the page faults of a shared mapping cost more than write() -- 233 against
+// 155 ms for the two ASCII files of a 1.87-Mpoint cloud -- so the pieces are written one after the other.)
+inline bool write_pieces(const std::string &path, const std::string &header, const std::vector<std::string> &pieces)
+{
+    const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return false;
+    bool good = true;
+    auto put = [&](const char *p, size_t n) {
+        while (good && n) {
+            const ssize_t w = write(fd, p, n);
+            if (w <= 0) good = false;
+            else { p += w; n -= (size_t)w; }
+        }
+    };
+    put(header.data(), header.size());
+    for (const auto &q : pieces) put(q.data(), q.size());
+    return close(fd) == 0 && good;
 }
 
 }  // namespace sl3d_io

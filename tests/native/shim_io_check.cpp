@@ -1,9 +1,14 @@
-// Malformed-input check of the shim's file readers (3dscan_amd/csrc/sl3d_shim_io.h), built with -fsanitize=address,undefined by
-// tests/test_shim_io.py: well-formed files must parse to the right values; truncated, oversized, garbage and lying files must be
-// refused (or parsed) WITHOUT touching memory they do not own, allocating what their headers claim, or running into undefined
-// behaviour.  Test infrastructure only.   usage: shim_io_check <scratch directory>   -> exit code 0, "ok <cases>" on stdout
+// Check of the shim's file readers and writers (3dscan_amd/csrc/sl3d_shim_io.h) and of its host thread pool (sl3d_shim_pool.h), built
+// with -fsanitize=address,undefined by tests/test_shim_io.py.  Readers: well-formed files must parse to the right values; truncated,
+// oversized, garbage and lying files must be refused (or parsed) WITHOUT touching memory they do not own, allocating what their headers
+// claim, or running into undefined behaviour.  Writers: the BMP header byte for byte, the text rows equal to printf's, the pieces of a
+// cloud equal to one pass, files that read back bit for bit.  Pool: an exception in one item reaches the caller and stops nothing else.
+// Test infrastructure only.   usage: shim_io_check <scratch directory>   -> exit code 0, "ok <cases>" on stdout
+#include <atomic>
+#include <cfloat>
 #include <cstdio>
 #include <random>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -25,6 +30,21 @@ static void put(const std::string &path, const std::vector<uint8_t> &b)
 }
 static void put_text(const std::string &path, const std::string &s) { put(path, std::vector<uint8_t>(s.begin(), s.end())); }
 static void le32(std::vector<uint8_t> &b, size_t o, uint32_t v) { for (int k = 0; k < 4; k++) b[o + k] = (uint8_t)(v >> (8 * k)); }
+static std::vector<uint8_t> get(const std::string &path)
+{
+    std::vector<uint8_t> b;
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return b;
+    for (int ch; (ch = fgetc(f)) != EOF;) b.push_back((uint8_t)ch);
+    fclose(f);
+    return b;
+}
+static std::string joined(const std::vector<std::string> &pieces)
+{
+    std::string all;
+    for (const auto &q : pieces) all += q;
+    return all;
+}
 
 // a well-formed BMP of w x h: 8 bits with a grey ramp palette (value = (x + 2 y) & 255) or 24 bits (B, G, R = x, y, x ^ y)
 static std::vector<uint8_t> bmp(int w, int h, int bpp, bool top_down = false, uint32_t ncolors = 0)
@@ -172,6 +192,117 @@ int main(int argc, char **argv)
         cases++;
     }
     CHECK(!read_ply(dir + "/none.ply", c));
+
+    // ---- write_bmp_gray: 37 x 11 (a row of 37 bytes is padded to 40) and 8 x 1
+    for (const auto &wh : {std::pair<int, int>{37, 11}, std::pair<int, int>{8, 1}}) {
+        const int w = wh.first, h = wh.second;
+        std::vector<uint8_t> img((size_t)w * h), back((size_t)w * h, 0);
+        for (auto &x : img) x = (uint8_t)rng();
+        CHECK(write_bmp_gray(p, img.data(), w, h));
+        const std::vector<uint8_t> file = get(p);
+        // what cvSaveImage writes for a 1-channel image: "BM", the file size, the pixel array at 14 + 40 + 1024, a 40-byte info header with
+        // the width, the height (positive: bottom-up), 1 plane, 8 bits, and zero in every other field (biCompression, biSizeImage, the
+        // resolutions, biClrUsed, biClrImportant); then 256 palette entries B = G = R = index, reserved byte 0
+        const uint32_t rowbytes = (uint32_t)(w + 3) / 4 * 4;
+        std::vector<uint8_t> head(1078, 0);
+        head[0] = 'B'; head[1] = 'M';
+        le32(head, 2, 1078 + rowbytes * (uint32_t)h); le32(head, 10, 1078); le32(head, 14, 40); le32(head, 18, (uint32_t)w); le32(head, 22, (uint32_t)h);
+        head[26] = 1; head[28] = 8;
+        for (int i = 0; i < 256; i++) head[54 + 4 * i] = head[54 + 4 * i + 1] = head[54 + 4 * i + 2] = (uint8_t)i;
+        CHECK(file.size() == 1078 + (size_t)rowbytes * h && std::equal(head.begin(), head.end(), file.begin()));
+        CHECK(read_bmp_gray(p, w, h, back.data()) && back == img);
+    }
+    CHECK(!write_bmp_gray(dir + "/no_such_directory/x.bmp", gray.data(), W, H));
+
+    // ---- the text rows: random bit patterns (the non-finite ones left out: the project defines no text for them) and the edge values
+    // against printf("%.9g"), byte for byte
+    std::vector<float> xyz = {0.f, -0.f, 1.401298464e-45f, FLT_MIN, FLT_MAX, 1e-5f, 1e-4f, 999999999.f, 1e9f,
+                              -1.401298464e-45f, -FLT_MIN, -FLT_MAX, -1e-5f, -1e-4f, -999999999.f, -1e9f, 1.f, 0.1f};
+    while (xyz.size() < 3 * 40000) {
+        const uint32_t bits = (uint32_t)rng();
+        float v;
+        memcpy(&v, &bits, 4);
+        if (std::isfinite(v)) xyz.push_back(v);
+    }
+    const int64_t npts = (int64_t)xyz.size() / 3;
+    std::vector<uint8_t> rgb((size_t)npts * 3);
+    for (auto &x : rgb) x = (uint8_t)rng();
+    rgb[0] = rgb[1] = rgb[2] = 0; rgb[3] = rgb[4] = rgb[5] = 255;
+    std::string pcd_all, ply_all, pcd_want, ply_want;
+    append_cloud_rows(&pcd_all, &ply_all, xyz.data(), rgb.data(), 0, npts);
+    for (int64_t i = 0; i < npts; i++) {
+        char row[128];
+        const unsigned r = rgb[3 * i], g = rgb[3 * i + 1], b = rgb[3 * i + 2];
+        snprintf(row, sizeof row, "%.9g %.9g %.9g %u\n", xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], r << 16 | g << 8 | b);
+        pcd_want += row;
+        snprintf(row, sizeof row, "%.9g %.9g %.9g %u %u %u\n", xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], r, g, b);
+        ply_want += row;
+    }
+    CHECK(pcd_all == pcd_want);
+    CHECK(ply_all == ply_want);
+    {   // either file alone, a range that does not start at 0, appended behind what the string holds
+        std::string only_pcd = "x", only_ply = "y", first_pcd, first_ply;
+        append_cloud_rows(&first_pcd, &first_ply, xyz.data(), rgb.data(), 0, 7);
+        append_cloud_rows(&only_pcd, nullptr, xyz.data(), rgb.data(), 7, npts - 7);
+        append_cloud_rows(nullptr, &only_ply, xyz.data(), rgb.data(), 7, npts - 7);
+        CHECK("x" + pcd_want == "x" + first_pcd + only_pcd.substr(1) && only_pcd[0] == 'x');
+        CHECK("y" + ply_want == "y" + first_ply + only_ply.substr(1) && only_ply[0] == 'y');
+    }
+
+    // ---- the pieces of a cloud: 40,000 points are three uneven pieces; joined they are the one pass above, on all threads and on one
+    CHECK(cloud_pieces(0, 16384) == 1 && cloud_pieces(16384, 16384, 8) == 1 && cloud_pieces(16385, 16384, 8) == 2 && cloud_pieces(1 << 30, 65536, 2) == 8);
+    for (int threads : {sl3d_pool::usable_threads(), 1}) {
+        std::vector<std::string> pcd_pieces(5, "stale"), ply_pieces;
+        format_cloud(xyz.data(), rgb.data(), npts, false, &pcd_pieces, &ply_pieces, threads);
+        CHECK(pcd_pieces.size() == 3 && ply_pieces.size() == 3 && pcd_pieces[0].size() != pcd_pieces[1].size());
+        CHECK(joined(pcd_pieces) == pcd_want && joined(ply_pieces) == ply_want);
+        format_cloud(xyz.data(), rgb.data(), npts, false, nullptr, &ply_pieces, threads);   // the buffers again, one file only
+        CHECK(joined(ply_pieces) == ply_want);
+        // the binary records: 16 bytes (x y z, 0x00RRGGBB) and 15 bytes (x y z, r g b) per point, little endian
+        format_cloud(xyz.data(), rgb.data(), npts, true, &pcd_pieces, &ply_pieces, threads);
+        const std::string pcd_bin = joined(pcd_pieces), ply_bin = joined(ply_pieces);
+        bool same = pcd_pieces.size() == 1 && pcd_bin.size() == (size_t)npts * 16 && ply_bin.size() == (size_t)npts * 15;
+        for (int64_t i = 0; i < npts && same; i++) {
+            const uint8_t want[4] = {rgb[3 * i + 2], rgb[3 * i + 1], rgb[3 * i], 0};
+            same = !memcmp(&pcd_bin[16 * i], &xyz[3 * i], 12) && !memcmp(&pcd_bin[16 * i + 12], want, 4) &&
+                   !memcmp(&ply_bin[15 * i], &xyz[3 * i], 12) && !memcmp(&ply_bin[15 * i + 12], &rgb[3 * i], 3);
+        }
+        CHECK(same);
+    }
+
+    // ---- header + pieces through write_pieces, read back by read_ply: the same floats bit for bit, the same colours
+    for (bool binary : {false, true}) {
+        std::vector<std::string> ply_pieces;
+        format_cloud(xyz.data(), rgb.data(), npts, binary, nullptr, &ply_pieces);
+        CHECK(write_pieces(p, ply_header(npts, binary), ply_pieces));
+        PlyCloud back;
+        CHECK(read_ply(p, back) && back.xyz.size() == xyz.size() && !memcmp(back.xyz.data(), xyz.data(), 4 * xyz.size()) && back.rgb == rgb);
+        CHECK(get(p).size() == ply_header(npts, binary).size() + joined(ply_pieces).size());
+    }
+    CHECK(ply_header(12, false) == "ply\nformat ascii 1.0\ncomment generated by sl3d (3dscan_amd)\nelement vertex 12\nproperty float x\nproperty float y\n"
+                                   "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n");
+    CHECK(pcd_header(12, true) == "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F U\nCOUNT 1 1 1 1\n"
+                                  "WIDTH 12\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS 12\nDATA binary\n");
+    CHECK(!write_pieces(dir + "/no_such_directory/x.ply", "h", {}));
+
+    // ---- the pool: one item of a burst throws -- the caller gets the exception, every other item has run, the next burst is whole
+    {
+        std::vector<std::atomic<int>> ran(64);
+        bool caught = false;
+        try {
+            sl3d_pool::parallel_for(64, [&](int i) { ran[(size_t)i]++; if (i == 13) throw std::runtime_error("item 13"); }, 4);
+        } catch (const std::runtime_error &e) {
+            caught = std::string(e.what()) == "item 13";
+        }
+        CHECK(caught);
+        bool all = true;
+        for (auto &r : ran) all &= r == 1;
+        CHECK(all);
+        sl3d_pool::parallel_for(64, [&](int i) { ran[(size_t)i]++; }, 4);
+        all = true;
+        for (auto &r : ran) all &= r == 2;
+        CHECK(all);
+    }
     remove(p.c_str());
     if (failures) { fprintf(stderr, "%d of %d checks failed\n", failures, cases); return 1; }
     printf("ok %d\n", cases);

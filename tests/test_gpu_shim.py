@@ -29,6 +29,15 @@ def _xml(path, name, rows, cols, vals):
                 % (name, rows, cols, " ".join("%.17e" % v for v in vals), name))
 
 
+def build_driver(exe, defs):
+    """the shim + its headless driver for a test's compile-time dimensions (the reference fixes them with macros too)"""
+    csrc = os.path.join(ROOT, "3dscan_amd", "csrc")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", *defs, "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "native", "shim_driver.cpp"), os.path.join(csrc, "sl3d_shim.cpp"),
+                           os.path.join(csrc, "sl3d_shim_globals.cpp"), "-L" + os.path.join(ROOT, "3dscan_amd"), "-lsl3d",
+                           "-Wl,-rpath," + os.path.join(ROOT, "3dscan_amd"), "-o", exe])
+
+
 # the deferred mode (sl3d_shim_globals): <inputs>+deferred_<mask>[x<scans>]
 DEFERRED = {"every": 0xfff, "final": 0x804, "none": 0x0, "phases": 0x804 | 0x78}
 
@@ -110,11 +119,7 @@ def test_shim_matches_oracle(tmp_path, devices, mode):
     # build the shim + driver for this test's compile-time dimensions (the reference fixes them with macros too)
     exe = f"{root}/shim_driver"
     defs = [f"-DCamera_imagewidth={W}", f"-DCamera_imageheight={H}", f"-DProjector_imagewidth={PW}", f"-DProjector_imageheight={PH}"]
-    csrc = os.path.join(ROOT, "3dscan_amd", "csrc")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", *defs, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "native", "shim_driver.cpp"), os.path.join(csrc, "sl3d_shim.cpp"),
-                           os.path.join(csrc, "sl3d_shim_globals.cpp"), "-L" + os.path.join(ROOT, "3dscan_amd"), "-lsl3d",
-                           "-Wl,-rpath," + os.path.join(ROOT, "3dscan_amd"), "-o", exe])
+    build_driver(exe, defs)
     out = f"{root}/out.bin"
     ncv, nch = -(-PW // FWV), -(-PH // FWH)
     env = {k: v for k, v in os.environ.items() if k != "SL3D_DEVICES"}
@@ -250,12 +255,8 @@ def test_shim_generate_pattern_reproduces_reference_files(tmp_path):
     PWr, PHr, F, fwv, fwh = (int(v) for v in fx["config"])
     root = str(tmp_path)
     exe = f"{root}/shim_driver"
-    csrc = os.path.join(ROOT, "3dscan_amd", "csrc")
     defs = [f"-DProjector_imagewidth={PWr}", f"-DProjector_imageheight={PHr}", "-DCamera_imagewidth=64", "-DCamera_imageheight=48"]
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", *defs, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "native", "shim_driver.cpp"), os.path.join(csrc, "sl3d_shim.cpp"),
-                           os.path.join(csrc, "sl3d_shim_globals.cpp"), "-L" + os.path.join(ROOT, "3dscan_amd"), "-lsl3d",
-                           "-Wl,-rpath," + os.path.join(ROOT, "3dscan_amd"), "-o", exe])
+    build_driver(exe, defs)
     r = subprocess.run([exe, "patterns", root, str(F), str(fwv), str(fwh)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.split()[-4:] == ["40", "6", "23", "5"]  # the counts allocate_memory() derives (common_variables.h:6-9,23-24)
@@ -294,12 +295,8 @@ def test_shim_register_point_clouds_files(tmp_path, binary):
         clouds.append(xyz)
         cols.append(rgb)
     exe = f"{root}/shim_driver"
-    csrc = os.path.join(ROOT, "3dscan_amd", "csrc")
     defs = ["-DCamera_imagewidth=64", "-DCamera_imageheight=48", "-DProjector_imagewidth=64", "-DProjector_imageheight=48"]
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", *defs, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "native", "shim_driver.cpp"), os.path.join(csrc, "sl3d_shim.cpp"),
-                           os.path.join(csrc, "sl3d_shim_globals.cpp"), "-L" + os.path.join(ROOT, "3dscan_amd"), "-lsl3d",
-                           "-Wl,-rpath," + os.path.join(ROOT, "3dscan_amd"), "-o", exe])
+    build_driver(exe, defs)
     tx, ty, tz, step = 60.0, 35.0, -2.0, 12.5
     env = dict(os.environ, SL3D_SHIM_BINARY="1" if binary else "0")
     r = subprocess.run([exe, "register", root, "3", str(tx), str(ty), str(tz), str(step)], capture_output=True, text=True, timeout=300, env=env)
