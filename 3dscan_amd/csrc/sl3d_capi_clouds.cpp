@@ -1,6 +1,6 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
-// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals).  Every consumer of a dense result
+// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals, sl3d_mesh_components.hip for the components).  Every consumer of a dense result
 // keeps its counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, read_totals
 // brings its totals to the host.
 #include "sl3d_capi_internal.h"
@@ -116,16 +116,17 @@ static float *mapped_destination(float *xyz)
     return nullptr;
 }
 
-// Host copy of per-view device arrays of 12-byte elements (points, faces), `stride` elements apart, back to back: view v's first counts[v]
-// elements, at most `capacity` in all (negative or used up: nothing more is copied; the counts stay the caller's to report in full).
-// host == NULL: nothing.  Enqueued only -- the caller synchronises
-static int download_clamped(sl3d_ctx *x, void *host, const void *dev, size_t stride, int n_views, const int64_t *counts, int64_t capacity)
+// Host copy of per-view device arrays of `elem`-byte elements (12: points, faces, normals; 4: labels, ids), `stride` elements apart, back
+// to back: view v's first counts[v] elements, at most `capacity` in all (negative or used up: nothing more is copied; the counts stay the
+// caller's to report in full).  host == NULL: nothing.  Enqueued only -- the caller synchronises
+static int download_clamped(sl3d_ctx *x, void *host, const void *dev, size_t stride, int n_views, const int64_t *counts, int64_t capacity,
+                            size_t elem = 12)
 {
     int64_t off = 0;
     for (int v = 0; v < n_views && host; v++) {
         const int64_t n = std::min<int64_t>(counts[v], capacity - off);
         if (n <= 0) continue;
-        HIPCHK_DRAIN(x, hipMemcpyAsync((char *)host + 12 * off, (const char *)dev + 12 * (size_t)v * stride, (size_t)n * 12, hipMemcpyDeviceToHost, x->stream));
+        HIPCHK_DRAIN(x, hipMemcpyAsync((char *)host + elem * off, (const char *)dev + elem * (size_t)v * stride, (size_t)n * elem, hipMemcpyDeviceToHost, x->stream));
         off += n;
     }
     return SL3D_OK;
@@ -578,6 +579,170 @@ try {
     size_t stride = 0;
     rc = sl3d_mesh_normals(x, first_view, n_views, max_edge, &dev, &stride, n_vertices);
     if (rc || (rc = download_clamped(x, normals, dev, stride, n_views, n_vertices, vertex_capacity))) return rc;
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// ---- connected components of those meshes, and the meshes without the small ones (sl3d_mesh_components.h: the definition and the
+// union-find; sl3d_mesh_components.hip: the kernels) -----------------------------------------------------------------------------------
+static int ensure_cc_buffers(sl3d_ctx *x)
+{
+    if (x->cc_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride, chunks = mv * (size_t)mesh_chunks(P);
+    CcBuffers &b = x->cc;
+    int rc = SL3D_OK;
+    if (!b.cells) rc = dev_alloc(x, &b.cells, px);
+    if (!rc && !b.labels) rc = dev_alloc(x, &b.labels, px);
+    if (!rc && !b.vid) rc = dev_alloc(x, &b.vid, px);
+    if (!rc && !b.sizes) rc = dev_alloc(x, &b.sizes, px);
+    if (!rc && !x->d_cc_labels) rc = dev_alloc(x, &x->d_cc_labels, px);
+    if (!rc && !b.cnt) rc = dev_alloc(x, &b.cnt, chunks);
+    if (!rc && !b.off) rc = dev_alloc(x, &b.off, chunks);
+    if (!rc && !b.tot) rc = dev_alloc(x, &b.tot, 5 * mv);
+    if (rc) return rc;
+    x->ccf.tot = b.tot + mv;
+    b.stat = b.tot + 3 * mv;
+    x->cc_ready = true;
+    return SL3D_OK;
+}
+
+static int ensure_ccf_buffers(sl3d_ctx *x)
+{
+    if (x->ccf_ready) return SL3D_OK;
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride, chunks = mv * 2 * (size_t)mesh_chunks(P);
+    CcFiltered &f = x->ccf;
+    f.face_stride = std::max<size_t>(1, 2 * (size_t)(P.W - 1) * (size_t)(P.H - 1));
+    int rc = SL3D_OK;
+    if (!f.keep) rc = dev_alloc(x, &f.keep, px);
+    if (!rc && !f.cnt) rc = dev_alloc(x, &f.cnt, chunks);
+    if (!rc && !f.off) rc = dev_alloc(x, &f.off, chunks);
+    if (!rc && !f.xyz) rc = dev_alloc(x, &f.xyz, 3 * px);
+    if (!rc && !f.ids) rc = dev_alloc(x, &f.ids, px);
+    if (!rc && !f.faces) rc = dev_alloc(x, &f.faces, mv * f.face_stride * 3);
+    if (rc) return rc;
+    x->ccf_ready = true;
+    return SL3D_OK;
+}
+
+// The one read-back of a components or filter call: x->cc.tot whole (5 words per view of the context).  A failure word set by a kernel
+// -- an iteration bound ran out: a logic error -- ends the call as SL3D_E_INTERNAL.  Synchronises for the caller
+static int read_cc_totals(sl3d_ctx *x, int first_view, int n_views, std::vector<unsigned long long> &t)
+{
+    const size_t mv = (size_t)x->cfg.max_views;
+    t.resize(5 * mv);
+    HIPCHK(x, hipMemcpyAsync(t.data(), x->cc.tot, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    for (int v = first_view; v < first_view + n_views; v++)
+        if (t[3 * mv + 2 * (size_t)v + 1])
+            return fail(x, SL3D_E_INTERNAL, "mesh components: a label walk of view " + std::to_string(v) + " ran out of its iteration bound");
+    return SL3D_OK;
+}
+
+// Five launches (cells, scan, union, flatten, labels), one read-back.  Reads the dense result only and writes buffers of its own.
+extern "C" int sl3d_mesh_components(sl3d_ctx *x, int first_view, int n_views, float max_edge, const int32_t **device_labels,
+                                    size_t *view_stride_points, int64_t *n_vertices, int64_t *n_components)
+try {
+    int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_components);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    rc = ensure_cc_buffers(x);
+    if (rc) return rc;
+    CcBuffers b = x->cc;
+    b.labels_out = x->d_cc_labels;
+    rc = launched(x, launch_mesh_components(P, first_view, n_views, max_edge, b, x->stream));
+    std::vector<unsigned long long> t;
+    if (!rc) rc = read_cc_totals(x, first_view, n_views, t);
+    if (rc) return rc;
+    const size_t mv = (size_t)x->cfg.max_views;
+    for (int k = 0; k < n_views; k++) {
+        n_vertices[k] = (int64_t)t[(size_t)first_view + k];
+        n_components[k] = (int64_t)t[3 * mv + 2 * ((size_t)first_view + k)];
+    }
+    if (device_labels) *device_labels = x->d_cc_labels + (size_t)first_view * P.px_view_stride;
+    if (view_stride_points) *view_stride_points = P.px_view_stride;
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: the labels of the views back to back
+extern "C" int sl3d_get_mesh_components(sl3d_ctx *x, int first_view, int n_views, float max_edge, int32_t *labels, int64_t vertex_capacity,
+                                        int64_t *n_vertices, int64_t *n_components)
+try {
+    int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_components);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const int32_t *dev = nullptr;
+    size_t stride = 0;
+    rc = sl3d_mesh_components(x, first_view, n_views, max_edge, &dev, &stride, n_vertices, n_components);
+    if (rc || (rc = download_clamped(x, labels, dev, stride, n_views, n_vertices, vertex_capacity, 4))) return rc;
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+static int check_filter_args(sl3d_ctx *x, int first_view, int n_views, float max_edge, int64_t min_vertices, const int64_t *n_vertices,
+                             const int64_t *n_faces)
+{
+    const int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_faces);
+    if (rc) return rc;
+    if (min_vertices < 1) return fail(x, SL3D_E_INVALID_ARG, "min_vertices must be >= 1 (1: the mesh itself)");
+    return SL3D_OK;
+}
+
+// Seven launches (cells, scan, union, flatten, keep, scan, emit), one read-back
+extern "C" int sl3d_mesh_views_filtered(sl3d_ctx *x, int first_view, int n_views, float max_edge, int64_t min_vertices,
+                                        sl3d_mesh_filtered *device_mesh, int64_t *n_vertices, int64_t *n_faces)
+try {
+    int rc = check_filter_args(x, first_view, n_views, max_edge, min_vertices, n_vertices, n_faces);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    rc = ensure_cc_buffers(x);
+    if (!rc) rc = ensure_ccf_buffers(x);
+    if (rc) return rc;
+    CcBuffers b = x->cc;
+    b.labels_out = nullptr;
+    rc = launched(x, launch_mesh_components(P, first_view, n_views, max_edge, b, x->stream));
+    // (a component has fewer vertices than INT_MAX: every larger bar keeps nothing, as INT_MAX does)
+    if (!rc) rc = launched(x, launch_mesh_filter(P, first_view, n_views, (int)std::min<int64_t>(min_vertices, INT32_MAX), b, x->ccf, x->stream));
+    std::vector<unsigned long long> t;
+    if (!rc) rc = read_cc_totals(x, first_view, n_views, t);
+    if (rc) return rc;
+    const size_t mv = (size_t)x->cfg.max_views;
+    for (int k = 0; k < n_views; k++) {
+        n_vertices[k] = (int64_t)t[mv + 2 * ((size_t)first_view + k)];
+        n_faces[k] = (int64_t)t[mv + 2 * ((size_t)first_view + k) + 1];
+    }
+    if (device_mesh) {
+        device_mesh->xyz = x->ccf.xyz + 3 * (size_t)first_view * P.px_view_stride;
+        device_mesh->faces = x->ccf.faces + 3 * (size_t)first_view * x->ccf.face_stride;
+        device_mesh->vertex_ids = x->ccf.ids + (size_t)first_view * P.px_view_stride;
+        device_mesh->view_stride_points = P.px_view_stride;
+        device_mesh->view_stride_faces = x->ccf.face_stride;
+    }
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: the kept points of the views back to back in xyz, their original ids in vertex_ids, the kept faces in faces
+extern "C" int sl3d_get_meshes_filtered(sl3d_ctx *x, int first_view, int n_views, float max_edge, int64_t min_vertices, float *xyz,
+                                        int32_t *vertex_ids, int64_t vertex_capacity, int32_t *faces, int64_t face_capacity, int64_t *n_vertices,
+                                        int64_t *n_faces)
+try {
+    int rc = check_filter_args(x, first_view, n_views, max_edge, min_vertices, n_vertices, n_faces);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    sl3d_mesh_filtered m;
+    rc = sl3d_mesh_views_filtered(x, first_view, n_views, max_edge, min_vertices, &m, n_vertices, n_faces);
+    if (rc) return rc;
+    rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc) rc = download_clamped(x, vertex_ids, m.vertex_ids, m.view_stride_points, n_views, n_vertices, vertex_capacity, 4);
+    if (!rc) rc = download_clamped(x, faces, m.faces, m.view_stride_faces, n_views, n_faces, face_capacity);
+    if (rc) return rc;
     SYNC_FOR_CALLER(x);
     return SL3D_OK;
 }

@@ -106,6 +106,15 @@ struct sl3d_ctx {
     CompactScratch chk_nrm{};
     float *d_normals = nullptr;
     bool normals_ready = false;               // ensure_normal_buffers ran to its end
+    // sl3d_mesh_components / sl3d_mesh_views_filtered (all allocated on first use, nothing shared with the mesh or the normals call):
+    // the planes and scratch of the union-find (CcBuffers, sl3d_internal.h; cc.labels_out is set per call) and the labels handed out;
+    // the filtered meshes (CcFiltered).  cc.tot is ONE array a call reads back whole: [max_views] vertices, [max_views][2] kept vertices and
+    // faces (ccf.tot), [max_views][2] components and the failure word (cc.stat)
+    CcBuffers cc{};
+    int32_t *d_cc_labels = nullptr;
+    bool cc_ready = false;                    // ensure_cc_buffers ran to its end
+    CcFiltered ccf{};
+    bool ccf_ready = false;                   // ensure_ccf_buffers ran to its end
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

@@ -240,6 +240,31 @@ int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_e
 // view v's in the order of its compacted cloud
 int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, float *normals,
                         size_t normal_stride, void *stream);
+// connected components of those meshes and the meshes without their small components (sl3d_mesh_components.hip, sl3d_mesh_components.h).
+// Every plane is [max_views][px_view_stride]: cells = a byte per cell (cc_cell_code), labels = the union-find over pixel indices (after the
+// launch: every valid pixel's root), vid = vertex id of a pixel, sizes = vertices of the component at its root's pixel.  cnt / off:
+// [max_views][mesh_chunks] valid pixels per chunk and their scan, tot [max_views]; stat: [max_views][2] {components, failure word};
+// labels_out: [max_views][px_view_stride] labels in vertex-id order, or NULL: the caller only wants the state the filter starts from
+struct CcBuffers {
+    uint8_t *cells;
+    int *labels, *vid, *sizes;
+    unsigned *cnt;
+    unsigned long long *off, *tot, *stat;
+    int *labels_out;
+};
+// the filtered mesh: keep = 0/1 byte per pixel; cnt / off [max_views][2][mesh_chunks] (kept vertices, kept faces per chunk), tot
+// [max_views][2]; xyz [max_views][px_view_stride][3], ids [max_views][px_view_stride], faces [max_views][face_stride][3]
+struct CcFiltered {
+    uint8_t *keep;
+    unsigned *cnt;
+    unsigned long long *off, *tot;
+    float *xyz;
+    int *ids, *faces;
+    size_t face_stride;
+};
+int launch_mesh_components(const KParams &P, int first_view, int n_views, float max_edge, const CcBuffers &b, void *stream);
+// behind launch_mesh_components over the same views: vertices of components of >= min_vertices vertices, and the faces among them
+int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

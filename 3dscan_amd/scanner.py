@@ -27,7 +27,7 @@ ABI_SYMBOLS = (
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
-    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
+    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_mesh_components", "sl3d_get_mesh_components", "sl3d_mesh_views_filtered", "sl3d_get_meshes_filtered", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
     "sl3d_get_device_buffers", "sl3d_download", "sl3d_download_2d",
     "sl3d_group_create", "sl3d_group_destroy", "sl3d_group_last_error", "sl3d_group_size", "sl3d_group_stripe", "sl3d_group_transport",
     "sl3d_group_set_calibration", "sl3d_group_set_mask", "sl3d_group_set_frames", "sl3d_group_run", "sl3d_group_gather",
@@ -65,6 +65,12 @@ class CloudSegments(C.Structure):
 class Mesh(C.Structure):
     """sl3d_mesh: device addresses of the clouds and faces sl3d_mesh_views left in HBM"""
     _fields_ = [("xyz", C.c_void_p), ("faces", C.c_void_p), ("view_stride_points", C.c_size_t), ("view_stride_faces", C.c_size_t)]
+
+
+class MeshFiltered(C.Structure):
+    """sl3d_mesh_filtered: device addresses of the clouds, faces and original vertex ids sl3d_mesh_views_filtered left in HBM"""
+    _fields_ = [("xyz", C.c_void_p), ("faces", C.c_void_p), ("vertex_ids", C.c_void_p), ("view_stride_points", C.c_size_t),
+                ("view_stride_faces", C.c_size_t)]
 
 
 _lib = None
@@ -116,6 +122,15 @@ def load_library(path=None):
         L.sl3d_mesh_normals.argtypes = [vp, i, i, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
         L.sl3d_get_mesh_normals.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, C.POINTER(C.c_int64)]
     except AttributeError:   # a build before 0.9.0 under SL3D_LIB: everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        p64 = C.POINTER(C.c_int64)
+        L.sl3d_mesh_components.argtypes = [vp, i, i, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), p64, p64]
+        L.sl3d_get_mesh_components.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, p64, p64]
+        L.sl3d_mesh_views_filtered.argtypes = [vp, i, i, C.c_float, C.c_int64, C.POINTER(MeshFiltered), p64, p64]
+        L.sl3d_get_meshes_filtered.argtypes = [vp, i, i, C.c_float, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, p64, p64]
+    except AttributeError:   # a build before 0.10.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -634,6 +649,56 @@ class Scanner:
     def mesh_normals(self, max_edge, view=0):
         """(n, 3) float32 normals of the vertices of mesh(max_edge, view) (meshes_normals)."""
         return self.meshes_normals(max_edge, view, 1)[0]
+
+    def mesh_components_device(self, max_edge, first_view=0, n_views=1):
+        """sl3d_mesh_components: the component labels of the meshes of a batch of views left in HBM; returns (device address, stride
+        between the views in labels, vertex counts, component counts)."""
+        dev, stride, nv, nc = C.c_void_p(), C.c_size_t(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_mesh_components(self._h, first_view, n_views, float(max_edge), C.byref(dev), C.byref(stride), nv, nc),
+                  "sl3d_mesh_components")
+        return dev.value, stride.value, [int(c) for c in nv], [int(c) for c in nc]
+
+    def meshes_components(self, max_edge, first_view=0, n_views=1):
+        """The connected components of meshes(max_edge, first_view, n_views): a list of (n_k,) int32 arrays, entry i the smallest vertex
+        id of the component of vertex i (two vertices are connected iff they share a face; a vertex in no face is a component of its
+        own).  The roots are the i with labels[i] == i (include/sl3d.h: the exact definition)."""
+        nv, nc = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_get_mesh_components(self._h, first_view, n_views, float(max_edge), None, 0, nv, nc), "sl3d_get_mesh_components")
+        tv = sum(nv)
+        flat = np.empty(tv, dtype=np.int32)
+        self._chk(self.L.sl3d_get_mesh_components(self._h, first_view, n_views, float(max_edge), flat.ctypes.data, tv, nv, nc),
+                  "sl3d_get_mesh_components")
+        return _cut(flat, nv)
+
+    def mesh_components(self, max_edge, view=0):
+        """(n,) int32 component labels of the vertices of mesh(max_edge, view) (meshes_components)."""
+        return self.meshes_components(max_edge, view, 1)[0]
+
+    def mesh_filtered_device(self, max_edge, min_vertices, first_view=0, n_views=1):
+        """sl3d_mesh_views_filtered: the filtered meshes of a batch of views left in HBM; returns (MeshFiltered, vertex counts, face
+        counts)."""
+        m, nv, nf = MeshFiltered(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        self._chk(self.L.sl3d_mesh_views_filtered(self._h, first_view, n_views, float(max_edge), int(min_vertices), C.byref(m), nv, nf),
+                  "sl3d_mesh_views_filtered")
+        return m, [int(c) for c in nv], [int(c) for c in nf]
+
+    def meshes_filtered(self, max_edge, min_vertices, first_view=0, n_views=1):
+        """meshes(max_edge, first_view, n_views) without the components of fewer than min_vertices vertices: a list of (xyz float32
+        (n, 3), faces int32 (m, 3), vertex_ids int32 (n,)); the kept vertices in order, the original faces among them with the new ids,
+        vertex_ids[i] the id new vertex i has in mesh() -- mesh_normals(...)[vertex_ids] and cloud_rgb()[1][vertex_ids] are the normals
+        and colours of the filtered mesh (include/sl3d.h: the exact definition)."""
+        nv, nf = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        args = (self._h, first_view, n_views, float(max_edge), int(min_vertices))
+        self._chk(self.L.sl3d_get_meshes_filtered(*args, None, None, 0, None, 0, nv, nf), "sl3d_get_meshes_filtered")
+        tv, tf = sum(nv), sum(nf)
+        xyz, ids, faces = np.empty((tv, 3), dtype=np.float32), np.empty(tv, dtype=np.int32), np.empty((tf, 3), dtype=np.int32)
+        self._chk(self.L.sl3d_get_meshes_filtered(*args, xyz.ctypes.data, ids.ctypes.data, tv, faces.ctypes.data, tf, nv, nf),
+                  "sl3d_get_meshes_filtered")
+        return list(zip(_cut(xyz, nv), _cut(faces, nf), _cut(ids, nv)))
+
+    def mesh_filtered(self, max_edge, min_vertices, view=0):
+        """(xyz, faces, vertex_ids) of one view (meshes_filtered)."""
+        return self.meshes_filtered(max_edge, min_vertices, view, 1)[0]
 
     def set_texture(self, bgr, view=0):
         """The colour image save_point_cloud() takes r,g,b from: (H, W, 3) uint8, B,G,R order (cvLoadImage)."""

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.9.0"
+#define SL3D_VERSION_STRING "0.10.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -431,6 +431,56 @@ int sl3d_mesh_normals(sl3d_ctx *ctx, int first_view, int n_views, float max_edge
 /* the same with a host copy, back to back, at most vertex_capacity triples in all; normals may be NULL (counts only) */
 int sl3d_get_mesh_normals(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, float *normals, int64_t vertex_capacity,
                           int64_t *n_vertices);
+
+/* ---- connected components of a view's mesh, and the mesh without its small components (0.10.0) --------------------------------
+ * The mesh of a real scan is one object plus hundreds of fragments; this labels them on the device and drops the small ones.  The
+ * mesh is the one sl3d_mesh_views(first_view, n_views, max_edge) defines: vertices = the valid pixels in scan order, faces as there.
+ *   component     two vertices are connected iff they share a face; components are the transitive closure.  A vertex that is in no
+ *                 face is a component of its own, of size 1.
+ *   label         the smallest vertex id of the vertex's component: one int32 per vertex in vertex-id order.  A component's root is
+ *                 the vertex whose label is its own id.
+ *   n_components  the number of roots, singletons included.
+ *   size          the number of vertices of the component.
+ *   filtered mesh for min_vertices >= 1, a sub-mesh of the original: the vertices whose component has size >= min_vertices, in scan
+ *                 order, renumbered 0..n'; the original faces whose vertices are kept (a face's three vertices share a component: any
+ *                 and all coincide), in the original order, with the new ids; vertex_ids[i] = the original id of new vertex i,
+ *                 ascending.  min_vertices = 1 gives the mesh itself.
+ * The filtered mesh is NOT the mesh of the filtered valid map: take a cell with four valid corners in which len2(a,e) <= len2(b,d) <=
+ * max_edge^2 and d-e and b-e are long -- it has no face; with e dropped from the valid map the three-corner rule would invent the face
+ * (a,d,b).  The face list is filtered, never derived again.
+ * Gathers through vertex_ids are exact: every face of a kept vertex is kept, so the normals of the filtered mesh are
+ * normals[vertex_ids] of sl3d_mesh_normals and its colours rgb[vertex_ids] of sl3d_get_cloud_rgb -- no filtered form of either exists
+ * or is needed.
+ * Labels are integers fixed by the definition: the result is the same bit for bit whatever the batch, the launch shape or the run.
+ * Works wherever sl3d_mesh_views works (timed and parity contexts, windows: cells end at the window).  Everything lives in buffers of
+ * its own (allocated on first use): points, valid, the clouds of sl3d_compact* / sl3d_run_clouds, the device mesh of the last
+ * sl3d_mesh_views and the normals of the last sl3d_mesh_normals are not modified and stay valid.  A NaN or non-positive max_edge,
+ * min_vertices < 1, a bad view range or NULL count pointers: SL3D_E_INVALID_ARG, and nothing on the device changes.  A fixed sequence
+ * of launches, no launch depends on the data; should a label walk ever exceed its iteration bound (a logic error) the call returns
+ * SL3D_E_INTERNAL with a text.  Not covered: as for the mesh (groups, segments, the shim). */
+/* labels of the meshes of views [first_view, first_view+n_views): view first_view+k has n_vertices[k] int32 labels at *device_labels +
+ * k*(*view_stride_points) and n_components[k] components; valid until the next sl3d_mesh_components / sl3d_get_mesh_components on this
+ * context (five launches, one read-back of the counts; device_labels / view_stride_points may be NULL) */
+int sl3d_mesh_components(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, const int32_t **device_labels,
+                         size_t *view_stride_points, int64_t *n_vertices, int64_t *n_components);
+/* the same with a host copy, back to back, at most vertex_capacity labels in all; labels may be NULL (counts only) */
+int sl3d_get_mesh_components(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int32_t *labels, int64_t vertex_capacity,
+                             int64_t *n_vertices, int64_t *n_components);
+typedef struct sl3d_mesh_filtered {   /* device-resident, valid until the next sl3d_mesh_views_filtered / sl3d_get_meshes_filtered */
+    const float *xyz;                 /* view first_view+k: n_vertices[k] points       at xyz        + 3*k*view_stride_points */
+    const int32_t *faces;             /* view first_view+k: n_faces[k] new-id triples  at faces      + 3*k*view_stride_faces  */
+    const int32_t *vertex_ids;        /* view first_view+k: n_vertices[k] original ids at vertex_ids + k*view_stride_points   */
+    size_t view_stride_points, view_stride_faces;
+} sl3d_mesh_filtered;
+/* the filtered meshes of views [first_view, first_view+n_views) on the device (seven launches, one read-back of the counts);
+ * device_mesh may be NULL */
+int sl3d_mesh_views_filtered(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int64_t min_vertices,
+                             sl3d_mesh_filtered *device_mesh, int64_t *n_vertices, int64_t *n_faces);
+/* the same with a host copy under the capacity contract of sl3d_get_meshes: points in xyz and original ids in vertex_ids (at most
+ * vertex_capacity of each in all), faces in faces (at most face_capacity triples in all); any of the three may be NULL */
+int sl3d_get_meshes_filtered(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int64_t min_vertices, float *xyz,
+                             int32_t *vertex_ids, int64_t vertex_capacity, int32_t *faces, int64_t face_capacity, int64_t *n_vertices,
+                             int64_t *n_faces);
 
 /* register_point_clouds(unsigned, float tx, float ty, float tz, float rot_step)  9/register_point_clouds.cpp:23:
  * the compacted clouds of views [first_view, first_view+n_views) are rotated about the Y axis through (tx,ty,tz)

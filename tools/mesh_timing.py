@@ -5,7 +5,10 @@ over time against the 6.3 TB/s achievable and the 8 TB/s peak, and -- for scale 
 vertices only).  One JSON line.  Under `rocprofv3 --kernel-trace --stats` (a run of its own) the kernel table gives the per-kernel split.
 --normals: the normals leg instead -- sl3d_mesh_normals over the same cases, sl3d_mesh_views timed in the same process in alternating
 blocks of calls so that both see the same clocks, the ratio per case (profiles/mesh_normals_timing.json).
-usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals]"""
+--components: the components leg -- sl3d_mesh_components and sl3d_mesh_views_filtered (min_vertices = MIN_VERTICES) over the same cases,
+each against sl3d_mesh_views in alternating blocks in the same process, the ratios and the component counts per case; written to --out
+(default profiles/mesh_components_timing.json) as well as printed.
+usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components [--out PATH]]"""
 import argparse
 import importlib
 import json
@@ -27,6 +30,7 @@ from mesh_reference import np_mesh  # the NumPy restatement of the definition: t
 ACHIEVABLE_TBS, PEAK_TBS = 6.3, 8.0
 CONFIGS = {"1080p_1": (1920, 1080, 1920, 1080, 1), "1080p_16": (1920, 1080, 1920, 1080, 16), "12mp_3": (4096, 3000, 2048, 2048, 3)}
 N, FW = 10, 2
+MIN_VERTICES = 100
 
 
 def lasso(W, H, share=358580.0 / 1920000.0):
@@ -68,10 +72,18 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--only", default="")
     ap.add_argument("--normals", action="store_true")
+    ap.add_argument("--components", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_components_timing.json"))
     a = ap.parse_args()
     syn = importlib.import_module("3dscan_amd.synth")
     scm = importlib.import_module("3dscan_amd.scanner")
-    if a.normals:
+    if a.components:
+        out = {"tool": "mesh_timing --components", "reps": a.reps, "min_vertices": MIN_VERTICES,
+               "bytes_note": "design, atomics not counted: components = 17 B/px (valid 3x, cell plane written + read, labels, sizes and ids "
+                             "initialised) + 32 B per vertex (points once, label read + written by the flatten, label + root id read, label "
+                             "written); filtered = 21 B/px (valid 3x, cell plane written + read 3x, labels, sizes, ids, keep bytes written + read) "
+                             "+ 28 B per vertex (points, flatten, label + size by the keep pass) + 32 B per kept vertex + 12 B per kept face", "runs": []}
+    elif a.normals:
         out = {"tool": "mesh_timing --normals", "reps": a.reps, "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
                "bytes_note": "design = valid 2x (count; the gather's rows r-1 and r+1 counted as L2 hits) + points 12 B per vertex read once "
                              "(rows r-1 / r+1 likewise) + 12 B per vertex written", "runs": []}
@@ -96,8 +108,28 @@ def main():
                 st = {}
                 np_mesh(np.ascontiguousarray(xyz[r0:r0 + 200]), np.ascontiguousarray(valid[r0:r0 + 200]), float("inf"), st)
                 med = float(np.float32(np.sqrt(np.median(st["len2"]))))
-                t_compact = 0.0 if a.normals else clock(lambda: sc.compact_views(0, V), a.reps)
+                t_compact = 0.0 if a.normals or a.components else clock(lambda: sc.compact_views(0, V), a.reps)
                 for label, max_edge in (("inf", float("inf")), ("median", med)):
+                    if a.components:
+                        _, nv, nf = sc.mesh_device(max_edge, 0, V)
+                        _, _, cv, nc = sc.mesh_components_device(max_edge, 0, V)
+                        _, kv, kf = sc.mesh_filtered_device(max_edge, MIN_VERTICES, 0, V)
+                        assert cv == nv
+                        tc, tm = clock_alternating(lambda: sc.mesh_components_device(max_edge, 0, V), lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                        tf, tm2 = clock_alternating(lambda: sc.mesh_filtered_device(max_edge, MIN_VERTICES, 0, V), lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                        d_comp = 17 * W * H * V + 32 * sum(nv)
+                        d_filt = 21 * W * H * V + 28 * sum(nv) + 32 * sum(kv) + 12 * sum(kf)
+                        out["runs"].append({
+                            "config": name, "size": [W, H], "views": V, "selection": sel, "max_edge": label, "max_edge_mm": None if label == "inf" else round(med, 6),
+                            "vertices_per_view": round(sum(nv) / V), "faces_per_view": round(sum(nf) / V), "components_per_view": round(sum(nc) / V),
+                            "kept_vertices_per_view": round(sum(kv) / V), "kept_faces_per_view": round(sum(kf) / V),
+                            "components_us_per_call": round(tc * 1e6, 1), "components_us_per_view": round(tc * 1e6 / V, 2),
+                            "filtered_us_per_call": round(tf * 1e6, 1), "filtered_us_per_view": round(tf * 1e6 / V, 2),
+                            "mesh_us_per_call": round(tm * 1e6, 1), "mesh_us_per_call_beside_filtered": round(tm2 * 1e6, 1),
+                            "components_over_mesh": round(tc / tm, 2), "filtered_over_mesh": round(tf / tm2, 2),
+                            "components_design_bytes_per_view": d_comp // V, "components_design_tbs": round(d_comp / tc / 1e12, 3),
+                            "filtered_design_bytes_per_view": d_filt // V, "filtered_design_tbs": round(d_filt / tf / 1e12, 3)})
+                        continue
                     if a.normals:
                         _, nv, nf = sc.mesh_device(max_edge, 0, V)
                         assert sc.mesh_normals_device(max_edge, 0, V)[2] == nv
@@ -123,6 +155,9 @@ def main():
                         "design_bytes_per_view": design // V, "algorithmic_bytes_per_view": algorithmic // V,
                         "design_tbs": round(design / t / 1e12, 3), "design_over_achievable": round(design / t / 1e12 / ACHIEVABLE_TBS, 3),
                         "design_over_peak": round(design / t / 1e12 / PEAK_TBS, 3)})
+    if a.components:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out) + "\n")
     print(json.dumps(out))
 
 
