@@ -1,6 +1,6 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
-// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals, sl3d_mesh_components.hip for the components).  Every consumer of a dense result
+// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals, sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing).  Every consumer of a dense result
 // keeps its counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, read_totals
 // brings its totals to the host.
 #include "sl3d_capi_internal.h"
@@ -742,6 +742,84 @@ try {
     rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
     if (!rc) rc = download_clamped(x, vertex_ids, m.vertex_ids, m.view_stride_points, n_views, n_vertices, vertex_capacity, 4);
     if (!rc) rc = download_clamped(x, faces, m.faces, m.view_stride_faces, n_views, n_faces, face_capacity);
+    if (rc) return rc;
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// ---- smoothed vertices of those meshes, and their normals (sl3d_mesh_smooth.h: the definition, the ring and the step;
+// sl3d_mesh_smooth.hip: the kernels) ---------------------------------------------------------------------------------------------------
+static int ensure_smooth_buffers(sl3d_ctx *x, bool normals)
+{
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride;
+    int rc = SL3D_OK;
+    if (normals && !x->d_smooth_normals) rc = dev_alloc(x, &x->d_smooth_normals, 3 * px);
+    if (rc || x->smooth_ready) return rc;  // (one flag, set at the very end: ensure_cloud_buffers)
+    SmoothBuffers &b = x->smooth;
+    if (!b.cells) rc = dev_alloc(x, &b.cells, px);
+    if (!rc && !b.rings) rc = dev_alloc(x, &b.rings, px);
+    if (!rc && !b.plane[0]) rc = dev_alloc(x, &b.plane[0], 3 * px);
+    if (!rc && !b.plane[1]) rc = dev_alloc(x, &b.plane[1], 3 * px);
+    if (!rc && !b.cnt) rc = dev_alloc(x, &b.cnt, mv * (size_t)mesh_chunks(P));
+    if (!rc && !b.off) rc = dev_alloc(x, &b.off, mv * (size_t)mesh_chunks(P));
+    if (!rc && !b.tot) rc = dev_alloc(x, &b.tot, mv);
+    if (rc) return rc;
+    x->smooth_ready = true;
+    return SL3D_OK;
+}
+
+static int check_smooth_args(sl3d_ctx *x, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu, unsigned flags,
+                             const int64_t *n_vertices)
+{
+    const int rc = check_mesh_args(x, first_view, n_views, max_edge, n_vertices, n_vertices);
+    if (rc) return rc;
+    if (iterations < 1 || iterations > 1024) return fail(x, SL3D_E_INVALID_ARG, "iterations must lie in [1, 1024]");
+    if (!(lambda > 0.0f && lambda <= 1.0f)) return fail(x, SL3D_E_INVALID_ARG, "lambda must lie in (0, 1]");        // (false for NaN)
+    if (!(mu >= -1.0f && mu <= 0.0f)) return fail(x, SL3D_E_INVALID_ARG, "mu must lie in [-1, 0] (0: no second step)");
+    if (flags & ~(SL3D_SMOOTH_FIX_BOUNDARY | SL3D_SMOOTH_NORMALS)) return fail(x, SL3D_E_INVALID_ARG, "unknown smoothing flag");
+    return SL3D_OK;
+}
+
+// Cells, scan, rings, one launch per step, vertices out (and normals): 4 + steps (+ 1) launches, one read-back of the total per view.
+// Reads the dense result only and writes buffers of its own.
+extern "C" int sl3d_mesh_smooth(sl3d_ctx *x, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu, unsigned flags,
+                                sl3d_mesh_smoothed *device_mesh, int64_t *n_vertices)
+try {
+    int rc = check_smooth_args(x, first_view, n_views, max_edge, iterations, lambda, mu, flags, n_vertices);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    const bool normals = flags & SL3D_SMOOTH_NORMALS;
+    rc = ensure_smooth_buffers(x, normals);
+    if (rc) return rc;
+    SmoothBuffers b = x->smooth;
+    b.normals = normals ? x->d_smooth_normals : nullptr;
+    rc = launched(x, launch_mesh_smooth(P, first_view, n_views, max_edge, iterations, lambda, mu, flags & SL3D_SMOOTH_FIX_BOUNDARY, b, x->stream));
+    if (!rc) rc = read_totals(x, b.tot, 1, first_view, n_views, n_vertices);
+    if (rc) return rc;
+    if (device_mesh) {
+        device_mesh->xyz = b.plane[smooth_steps(iterations, mu) & 1] + 3 * (size_t)first_view * P.px_view_stride;
+        device_mesh->normals = normals ? b.normals + 3 * (size_t)first_view * P.px_view_stride : nullptr;
+        device_mesh->view_stride_points = P.px_view_stride;
+    }
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: the smoothed vertices of the views back to back, and their normals
+extern "C" int sl3d_get_mesh_smoothed(sl3d_ctx *x, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu,
+                                      unsigned flags, float *xyz, float *normals, int64_t vertex_capacity, int64_t *n_vertices)
+try {
+    int rc = check_smooth_args(x, first_view, n_views, max_edge, iterations, lambda, mu, flags, n_vertices);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    sl3d_mesh_smoothed m;
+    rc = sl3d_mesh_smooth(x, first_view, n_views, max_edge, iterations, lambda, mu, flags, &m, n_vertices);
+    if (rc) return rc;
+    rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc && m.normals) rc = download_clamped(x, normals, m.normals, m.view_stride_points, n_views, n_vertices, vertex_capacity);
     if (rc) return rc;
     SYNC_FOR_CALLER(x);
     return SL3D_OK;

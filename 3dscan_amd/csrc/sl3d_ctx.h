@@ -115,6 +115,12 @@ struct sl3d_ctx {
     bool cc_ready = false;                    // ensure_cc_buffers ran to its end
     CcFiltered ccf{};
     bool ccf_ready = false;                   // ensure_ccf_buffers ran to its end
+    // sl3d_mesh_smooth (all allocated on first use, nothing shared with the calls above): cell and ring bytes, the two planes of the
+    // steps, the chunk scratch (SmoothBuffers, sl3d_internal.h; smooth.normals is set per call) and, from the first call that asks for
+    // them, the normals of the smoothed mesh
+    SmoothBuffers smooth{};
+    float *d_smooth_normals = nullptr;
+    bool smooth_ready = false;                // ensure_smooth_buffers ran to its end
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

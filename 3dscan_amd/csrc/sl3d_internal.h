@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP
-// kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip).  Not part of the public ABI.
+// kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip).  Not part of the public ABI.
 // What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes, mesh_row_chunks);
 // the block idioms of their kernels are in sl3d_block.h.
 #pragma once
@@ -265,6 +265,21 @@ struct CcFiltered {
 int launch_mesh_components(const KParams &P, int first_view, int n_views, float max_edge, const CcBuffers &b, void *stream);
 // behind launch_mesh_components over the same views: vertices of components of >= min_vertices vertices, and the faces among them
 int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream);
+// smoothing of those meshes (sl3d_mesh_smooth.hip, sl3d_mesh_smooth.h).  cells / rings: [max_views][px_view_stride] a byte per cell
+// (cc_cell_code) / per pixel (smooth_ring); plane[2]: [max_views][px_view_stride][3] the ping-pong planes of the steps -- step s writes
+// plane[s & 1], and plane[smooth_steps & 1], the one the last step did not write, takes the compacted vertices (view v's at 3 * v *
+// px_view_stride); cnt / off: [max_views][mesh_chunks] valid pixels per chunk and their scan, tot [max_views]; normals:
+// [max_views][px_view_stride][3] in vertex-id order, or NULL: no normals asked for
+struct SmoothBuffers {
+    uint8_t *cells, *rings;
+    float *plane[2];
+    unsigned *cnt;
+    unsigned long long *off, *tot;
+    float *normals;
+};
+inline int smooth_steps(int iterations, float mu) { return iterations * (mu != 0.0f ? 2 : 1); }  // a step with mu == 0 is left out
+int launch_mesh_smooth(const KParams &P, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu, bool fix_boundary,
+                       const SmoothBuffers &b, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

@@ -18,6 +18,7 @@ SL3D_FLAG_SERIAL_LAUNCHES = 64
 AXIS_VERTICAL, AXIS_HORIZONTAL = 0, 1
 PATTERN_FRINGE, PATTERN_GRAY, PATTERN_INVERSE_GRAY, PATTERN_BINARY = 0, 1, 2, 3
 VALID_VERTICAL, VALID_HORIZONTAL, VALID_MERGED = 0, 1, 2
+SL3D_SMOOTH_FIX_BOUNDARY, SL3D_SMOOTH_NORMALS = 1, 2
 
 # every symbol include/sl3d.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -27,7 +28,7 @@ ABI_SYMBOLS = (
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
-    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_mesh_components", "sl3d_get_mesh_components", "sl3d_mesh_views_filtered", "sl3d_get_meshes_filtered", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
+    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_mesh_components", "sl3d_get_mesh_components", "sl3d_mesh_views_filtered", "sl3d_get_meshes_filtered", "sl3d_mesh_smooth", "sl3d_get_mesh_smoothed", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
     "sl3d_get_device_buffers", "sl3d_download", "sl3d_download_2d",
     "sl3d_group_create", "sl3d_group_destroy", "sl3d_group_last_error", "sl3d_group_size", "sl3d_group_stripe", "sl3d_group_transport",
     "sl3d_group_set_calibration", "sl3d_group_set_mask", "sl3d_group_set_frames", "sl3d_group_run", "sl3d_group_gather",
@@ -71,6 +72,11 @@ class MeshFiltered(C.Structure):
     """sl3d_mesh_filtered: device addresses of the clouds, faces and original vertex ids sl3d_mesh_views_filtered left in HBM"""
     _fields_ = [("xyz", C.c_void_p), ("faces", C.c_void_p), ("vertex_ids", C.c_void_p), ("view_stride_points", C.c_size_t),
                 ("view_stride_faces", C.c_size_t)]
+
+
+class MeshSmoothed(C.Structure):
+    """sl3d_mesh_smoothed: device addresses of the smoothed vertices and (with SL3D_SMOOTH_NORMALS, else None) their normals"""
+    _fields_ = [("xyz", C.c_void_p), ("normals", C.c_void_p), ("view_stride_points", C.c_size_t)]
 
 
 _lib = None
@@ -131,6 +137,13 @@ def load_library(path=None):
         L.sl3d_mesh_views_filtered.argtypes = [vp, i, i, C.c_float, C.c_int64, C.POINTER(MeshFiltered), p64, p64]
         L.sl3d_get_meshes_filtered.argtypes = [vp, i, i, C.c_float, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, p64, p64]
     except AttributeError:   # a build before 0.10.0 under SL3D_LIB: everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        f, u = C.c_float, C.c_uint
+        L.sl3d_mesh_smooth.argtypes = [vp, i, i, f, i, f, f, u, C.POINTER(MeshSmoothed), C.POINTER(C.c_int64)]
+        L.sl3d_get_mesh_smoothed.argtypes = [vp, i, i, f, i, f, f, u, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    except AttributeError:   # a build before 0.11.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -699,6 +712,37 @@ class Scanner:
     def mesh_filtered(self, max_edge, min_vertices, view=0):
         """(xyz, faces, vertex_ids) of one view (meshes_filtered)."""
         return self.meshes_filtered(max_edge, min_vertices, view, 1)[0]
+
+    @staticmethod
+    def _smooth_args(max_edge, iterations, lam, mu, fix_boundary, normals):
+        flags = (SL3D_SMOOTH_FIX_BOUNDARY if fix_boundary else 0) | (SL3D_SMOOTH_NORMALS if normals else 0)
+        return float(max_edge), int(iterations), float(lam), float(mu), flags
+
+    def mesh_smoothed_device(self, max_edge, first_view=0, n_views=1, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, normals=False):
+        """sl3d_mesh_smooth: the smoothed vertices (and normals) of the meshes of a batch of views left in HBM; returns (MeshSmoothed,
+        vertex counts)."""
+        m, nv = MeshSmoothed(), (C.c_int64 * n_views)()
+        args = self._smooth_args(max_edge, iterations, lam, mu, fix_boundary, normals)
+        self._chk(self.L.sl3d_mesh_smooth(self._h, first_view, n_views, *args, C.byref(m), nv), "sl3d_mesh_smooth")
+        return m, [int(c) for c in nv]
+
+    def meshes_smoothed(self, max_edge, first_view=0, n_views=1, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, normals=False):
+        """The vertices of meshes(max_edge, first_view, n_views) after `iterations` Taubin iterations over the 1-ring (one step with lam,
+        one with mu; mu = 0: plain Laplacian smoothing): a list of (n_k, 3) float32 arrays, or of (vertices, normals) pairs with
+        normals=True -- the normals of the smoothed mesh.  Faces and vertex ids are those of meshes(); fix_boundary keeps the vertices of
+        edges with one face where they are (include/sl3d.h: the exact definition)."""
+        nv = (C.c_int64 * n_views)()
+        args = (self._h, first_view, n_views) + self._smooth_args(max_edge, iterations, lam, mu, fix_boundary, normals)
+        self._chk(self.L.sl3d_get_mesh_smoothed(*args, None, None, 0, nv), "sl3d_get_mesh_smoothed")
+        tv = sum(nv)
+        xyz = np.empty((tv, 3), dtype=np.float32)
+        nrm = np.empty((tv, 3), dtype=np.float32) if normals else None
+        self._chk(self.L.sl3d_get_mesh_smoothed(*args, xyz.ctypes.data, nrm.ctypes.data if normals else None, tv, nv), "sl3d_get_mesh_smoothed")
+        return list(zip(_cut(xyz, nv), _cut(nrm, nv))) if normals else _cut(xyz, nv)
+
+    def mesh_smoothed(self, max_edge, view=0, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, normals=False):
+        """(n, 3) float32 smoothed vertices of mesh(max_edge, view), or (vertices, normals) with normals=True (meshes_smoothed)."""
+        return self.meshes_smoothed(max_edge, view, 1, iterations, lam, mu, fix_boundary, normals)[0]
 
     def set_texture(self, bgr, view=0):
         """The colour image save_point_cloud() takes r,g,b from: (H, W, 3) uint8, B,G,R order (cvLoadImage)."""

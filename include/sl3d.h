@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.10.0"
+#define SL3D_VERSION_STRING "0.11.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -481,6 +481,52 @@ int sl3d_mesh_views_filtered(sl3d_ctx *ctx, int first_view, int n_views, float m
 int sl3d_get_meshes_filtered(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int64_t min_vertices, float *xyz,
                              int32_t *vertex_ids, int64_t vertex_capacity, int32_t *faces, int64_t face_capacity, int64_t *n_vertices,
                              int64_t *n_faces);
+
+/* ---- smoothed vertex positions of a view's mesh, and the normals of the smoothed mesh (0.11.0) -----------------------------------
+ * The phase noise of a scan is of the order of its sample spacing, and the normals of sl3d_mesh_normals are the normals of that noise;
+ * this smooths the vertices on the device by Taubin's lambda|mu steps over the 1-ring.  Let M = (vertices, faces) be the mesh
+ * sl3d_mesh_views(first_view, n_views, max_edge) defines.  The faces and the vertex ids do not change; the connectivity is taken once,
+ * from the original positions.  Exact:
+ *   neighbours  two vertices are neighbours iff some face contains both: 0..8 of them, among the 8 pixels around the vertex's own.
+ *   boundary    an edge is a boundary edge iff exactly one face contains it (no edge lies in more than two faces); a boundary vertex is
+ *               an endpoint of a boundary edge.
+ *   one step    with factor f (a double: the float argument widened) reads positions p as float32 and writes p' as float32.  A vertex
+ *               with k >= 1 neighbours that is not fixed, per component: s = the neighbours' coordinates widened to double, added one
+ *               after the other in ascending vertex id, starting from +0; m = s / (double)k; p' = (float)((double)p + f * (m - (double)p)).
+ *               Every +, -, *, / is one IEEE double operation, nothing contracted; the cast rounds to nearest even.  Ascending vertex id
+ *               is the pixels' scan order: (r-1,c-1), (r-1,c), (r-1,c+1), (r,c-1), (r,c+1), (r+1,c-1), (r+1,c), (r+1,c+1).  A vertex with
+ *               k = 0, or a fixed one, keeps p' = p bitwise.  All vertices of a step read the positions of the step before (Jacobi).  No
+ *               special case for a NaN or infinity under a valid pixel: the arithmetic above is all there is.
+ *   iterations  >= 1; each is one step with lambda, then one step with mu if mu != 0 (Taubin's lambda|mu; mu == 0: plain Laplacian
+ *               smoothing).
+ *   flags       SL3D_SMOOTH_FIX_BOUNDARY: boundary vertices are fixed (scans are open surfaces, and the umbrella operator shrinks their
+ *               rims).  SL3D_SMOOTH_NORMALS: also the normals -- the definition of sl3d_mesh_normals applied to the faces of M with the
+ *               smoothed positions (the connectivity is NOT derived again from positions that have moved).
+ *   output      one float triple per vertex in vertex-id order; the same bit for bit whatever the launch shape, the batch or the run.
+ * No filtered form exists or is needed: gathers through vertex_ids of sl3d_mesh_views_filtered are exact for the smoothed positions and
+ * their normals alike -- a kept vertex keeps all its faces, hence all its neighbours and its boundary edges.
+ * Works wherever sl3d_mesh_views works (timed and parity contexts, windows: cells end at the window).  Everything lives in buffers of
+ * its own (allocated on first use): points, valid, the clouds of sl3d_compact* / sl3d_run_clouds, the device mesh of the last
+ * sl3d_mesh_views, the normals of the last sl3d_mesh_normals and the labels and filtered mesh of sl3d_mesh_components /
+ * sl3d_mesh_views_filtered are not modified and stay valid.  SL3D_E_INVALID_ARG, and nothing on the device changes, for: a NaN or
+ * non-positive max_edge, iterations outside [1, 1024], lambda not finite or outside (0, 1], mu not finite or outside [-1, 0], an unknown
+ * flag bit, a bad view range, a NULL n_vertices.  The launch sequence is fixed by the arguments alone (cells, scan, rings, one launch per
+ * step, vertices out, normals on request); nothing is read back but the counts.  Not covered: as for the mesh (groups, segments, the
+ * shim). */
+#define SL3D_SMOOTH_FIX_BOUNDARY 1u
+#define SL3D_SMOOTH_NORMALS 2u
+typedef struct sl3d_mesh_smoothed {   /* device-resident, valid until the next sl3d_mesh_smooth / sl3d_get_mesh_smoothed */
+    const float *xyz;                 /* view first_view+k: n_vertices[k] triples at xyz + 3*k*view_stride_points */
+    const float *normals;             /* same layout; NULL without SL3D_SMOOTH_NORMALS */
+    size_t view_stride_points;
+} sl3d_mesh_smoothed;
+/* the smoothed vertices (and normals) of the meshes of views [first_view, first_view+n_views) on the device; device_mesh may be NULL */
+int sl3d_mesh_smooth(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu, unsigned flags,
+                     sl3d_mesh_smoothed *device_mesh, int64_t *n_vertices);
+/* the same with a host copy under the capacity contract of sl3d_get_meshes: back to back, at most vertex_capacity triples in all in
+ * xyz and in normals; xyz may be NULL; normals is looked at only with SL3D_SMOOTH_NORMALS (and may be NULL then) */
+int sl3d_get_mesh_smoothed(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu,
+                           unsigned flags, float *xyz, float *normals, int64_t vertex_capacity, int64_t *n_vertices);
 
 /* register_point_clouds(unsigned, float tx, float ty, float tz, float rot_step)  9/register_point_clouds.cpp:23:
  * the compacted clouds of views [first_view, first_view+n_views) are rotated about the Y axis through (tx,ty,tz)

@@ -8,7 +8,11 @@ blocks of calls so that both see the same clocks, the ratio per case (profiles/m
 --components: the components leg -- sl3d_mesh_components and sl3d_mesh_views_filtered (min_vertices = MIN_VERTICES) over the same cases,
 each against sl3d_mesh_views in alternating blocks in the same process, the ratios and the component counts per case; written to --out
 (default profiles/mesh_components_timing.json) as well as printed.
-usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components [--out PATH]]"""
+--smooth: the smoothing leg -- sl3d_mesh_smooth (10 iterations, lambda 0.5, mu -0.53: 20 steps) with both flags off and with both on,
+each against sl3d_mesh_views in alternating blocks in the same process; the time per step is the difference to a run of 1 iteration
+(2 steps) over the 18 steps between them, so the cell, ring, scan and output launches and the read-back cancel; written to --out (default
+profiles/mesh_smooth_timing.json) as well as printed.
+usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components | --smooth [--out PATH]]"""
 import argparse
 import importlib
 import json
@@ -31,6 +35,7 @@ ACHIEVABLE_TBS, PEAK_TBS = 6.3, 8.0
 CONFIGS = {"1080p_1": (1920, 1080, 1920, 1080, 1), "1080p_16": (1920, 1080, 1920, 1080, 16), "12mp_3": (4096, 3000, 2048, 2048, 3)}
 N, FW = 10, 2
 MIN_VERTICES = 100
+SMOOTH = (10, 0.5, -0.53)  # iterations, lambda, mu of the smoothing leg
 
 
 def lasso(W, H, share=358580.0 / 1920000.0):
@@ -73,11 +78,18 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--normals", action="store_true")
     ap.add_argument("--components", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_components_timing.json"))
+    ap.add_argument("--smooth", action="store_true")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "mesh_smooth_timing.json" if a.smooth else "mesh_components_timing.json")
     syn = importlib.import_module("3dscan_amd.synth")
     scm = importlib.import_module("3dscan_amd.scanner")
-    if a.components:
+    if a.smooth:
+        out = {"tool": "mesh_timing --smooth", "reps": a.reps, "iterations": SMOOTH[0], "lambda": SMOOTH[1], "mu": SMOOTH[2],
+               "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
+               "bytes_note": "design, one step = 2 B/px (valid, ring) + 24 B per vertex (points read once, rows r-1 / r+1 counted as L2 hits, "
+                             "points written)", "runs": []}
+    elif a.components:
         out = {"tool": "mesh_timing --components", "reps": a.reps, "min_vertices": MIN_VERTICES,
                "bytes_note": "design, atomics not counted: components = 17 B/px (valid 3x, cell plane written + read, labels, sizes and ids "
                              "initialised) + 32 B per vertex (points once, label read + written by the flatten, label + root id read, label "
@@ -108,8 +120,29 @@ def main():
                 st = {}
                 np_mesh(np.ascontiguousarray(xyz[r0:r0 + 200]), np.ascontiguousarray(valid[r0:r0 + 200]), float("inf"), st)
                 med = float(np.float32(np.sqrt(np.median(st["len2"]))))
-                t_compact = 0.0 if a.normals or a.components else clock(lambda: sc.compact_views(0, V), a.reps)
+                t_compact = 0.0 if a.normals or a.components or a.smooth else clock(lambda: sc.compact_views(0, V), a.reps)
                 for label, max_edge in (("inf", float("inf")), ("median", med)):
+                    if a.smooth:
+                        it, lam, mu = SMOOTH
+                        _, nv, nf = sc.mesh_device(max_edge, 0, V)
+                        assert sc.mesh_smoothed_device(max_edge, 0, V, it, lam, mu)[1] == nv
+                        run = {"config": name, "size": [W, H], "views": V, "selection": sel, "max_edge": label,
+                               "max_edge_mm": None if label == "inf" else round(med, 6), "vertices_per_view": round(sum(nv) / V),
+                               "faces_per_view": round(sum(nf) / V)}
+                        step_bytes = 2 * W * H * V + 24 * sum(nv)
+                        for tag, flag in (("plain", False), ("fixed_normals", True)):
+                            ts, tm = clock_alternating(lambda: sc.mesh_smoothed_device(max_edge, 0, V, it, lam, mu, flag, flag),
+                                                       lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                            t1, _ = clock_alternating(lambda: sc.mesh_smoothed_device(max_edge, 0, V, 1, lam, mu, flag, flag),
+                                                      lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                            step = (ts - t1) / (2 * (it - 1))
+                            run.update({f"{tag}_us_per_call": round(ts * 1e6, 1), f"{tag}_us_per_view": round(ts * 1e6 / V, 2),
+                                        f"{tag}_one_iteration_us_per_call": round(t1 * 1e6, 1), f"{tag}_mesh_us_per_call": round(tm * 1e6, 1),
+                                        f"{tag}_over_mesh": round(ts / tm, 2), f"{tag}_step_us_per_view": round(step * 1e6 / V, 2),
+                                        f"{tag}_step_design_tbs": round(step_bytes / step / 1e12, 3)})
+                        run["step_design_bytes_per_view"] = step_bytes // V
+                        out["runs"].append(run)
+                        continue
                     if a.components:
                         _, nv, nf = sc.mesh_device(max_edge, 0, V)
                         _, _, cv, nc = sc.mesh_components_device(max_edge, 0, V)
@@ -155,7 +188,7 @@ def main():
                         "design_bytes_per_view": design // V, "algorithmic_bytes_per_view": algorithmic // V,
                         "design_tbs": round(design / t / 1e12, 3), "design_over_achievable": round(design / t / 1e12 / ACHIEVABLE_TBS, 3),
                         "design_over_peak": round(design / t / 1e12 / PEAK_TBS, 3)})
-    if a.components:
+    if a.components or a.smooth:
         with open(a.out, "w") as f:
             f.write(json.dumps(out) + "\n")
     print(json.dumps(out))
