@@ -20,18 +20,30 @@ namespace sl3d {
 // O1 / N2: compaction of the dense cloud in the reference's row-major scan order
 // (8/save_point_cloud.cpp:33-37 counts the valid pixels, :85-104 appends them).  Three launches on the
 // context's stream: per-block counts (wave ballots), an exclusive scan of the block counts by one block,
-// and the scatter.  A block covers 1024 consecutive pixels of the pitch-padded plane; padding pixels are
-// never valid, so the scan order of the valid pixels is exactly the reference's.
+// and the scatter.  A block covers 1024 consecutive pixels of the pitch-padded plane; the padding columns
+// [W, pitch) of a row are clipped away like the mesh kernels clip them (QUAD_IN_WINDOW), whatever their valid
+// bytes hold, so the scan order of the valid pixels is exactly the reference's.
 // ------------------------------------------------------------------------------------------------
+// The lane's 4 valid bytes (0/1, bit 0 of every byte) with those beyond the window cleared.  base: the lane's first pixel in the plane, a
+// multiple of 4 -- the pitch is a multiple of 16, so the quad lies in one row; a plane stays below 2^32 pixels (sl3d_create)
+__device__ __forceinline__ unsigned quad_valid_bytes(const uint8_t *valid, size_t base, size_t n_px, int W, int pitch)
+{
+    if (base >= n_px) return 0u;
+    const int col = (int)((unsigned)base % (unsigned)pitch);
+    if (col >= W) return 0u;
+    const unsigned in_w = QUAD_IN_WINDOW(W, col);
+    return *(const unsigned *)(valid + base) & ((in_w & 1u) | (in_w & 2u) << 7 | (in_w & 4u) << 14 | (in_w & 8u) << 21);
+}
+
 // blockIdx.y = view of a batch (strides in elements)
-__global__ __launch_bounds__(256) void k_compact_count(const uint8_t *valid, size_t n_px, unsigned *block_counts, size_t valid_stride, int nb)
+__global__ __launch_bounds__(256) void k_compact_count(const uint8_t *valid, size_t n_px, unsigned *block_counts, size_t valid_stride, int nb, int W,
+                                                       int pitch)
 {
     valid += (size_t)blockIdx.y * valid_stride;
     block_counts += (size_t)blockIdx.y * nb;
     __shared__ unsigned s_cnt[4];
     const size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    unsigned w = base < n_px ? *(const unsigned *)(valid + base) : 0u;  // 4 valid bytes (0/1)
-    unsigned c = __popc(w & 0x01010101u);
+    unsigned c = __popc(quad_valid_bytes(valid, base, n_px, W, pitch));
     BLOCK_SUM(c, s_cnt);
     if (threadIdx.x == 0) block_counts[blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
 }
@@ -63,7 +75,7 @@ __global__ __launch_bounds__(1024) void k_compact_scan(const unsigned *counts, u
 // 70-72), [row][pitch][3] bytes; rgb_out receives r,g,b per compacted point
 __global__ __launch_bounds__(256) void k_compact_scatter(const uint8_t *valid, const float *points, size_t n_px,
                                                          const unsigned long long *block_offsets, float *cloud, const uint8_t *texture,
-                                                         uint8_t *rgb_out, size_t view_stride, int nb)
+                                                         uint8_t *rgb_out, size_t view_stride, int nb, int W, int pitch)
 {
     valid += (size_t)blockIdx.y * view_stride;
     points += 3 * (size_t)blockIdx.y * view_stride;
@@ -72,7 +84,7 @@ __global__ __launch_bounds__(256) void k_compact_scatter(const uint8_t *valid, c
     __shared__ unsigned s_wave[4];
     __shared__ __attribute__((aligned(16))) float s_pts[1024 * 3];  // the block's valid points, compacted
     const size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x * 4;
-    const unsigned w = base < n_px ? (*(const unsigned *)(valid + base) & 0x01010101u) : 0u;
+    const unsigned w = quad_valid_bytes(valid, base, n_px, W, pitch);
     const unsigned c = __popc(w);
     // exclusive prefix of c over the block: wave scan by shuffles, then the 4 wave totals
     const unsigned incl = wave_prefix(c, s_wave);
@@ -113,9 +125,10 @@ int launch_compact_views(const KParams &P, int first_view, int n_views, const Co
     const int nb = (int)compact_blocks(P);
     const ViewPlanes in = view_planes(P, first_view);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_compact_count, dim3(nb, n_views), dim3(256), 0, st, in.valid, n_px, s.cnt, n_px, nb);
+    hipLaunchKernelGGL(k_compact_count, dim3(nb, n_views), dim3(256), 0, st, in.valid, n_px, s.cnt, n_px, nb, P.W, P.pitch);
     hipLaunchKernelGGL(k_compact_scan, dim3(n_views), dim3(1024), 0, st, s.cnt, s.off, nb, s.tot + first_view);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb, n_views), dim3(256), 0, st, in.valid, in.points, n_px, s.off, clouds, texture, rgb_out, n_px, nb);
+    hipLaunchKernelGGL(k_compact_scatter, dim3(nb, n_views), dim3(256), 0, st, in.valid, in.points, n_px, s.off, clouds, texture, rgb_out, n_px, nb, P.W,
+                       P.pitch);
     return (int)hipGetLastError();
 }
 

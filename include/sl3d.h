@@ -381,7 +381,8 @@ int sl3d_get_clouds(sl3d_ctx *ctx, int first_view, int n_views, float *xyz, int6
  * meshed the PLY of stage 8 by hand); the definition is this library's own and exact:
  *   vertices  the compacted cloud of sl3d_get_cloud: the valid pixels in row-major scan order, id = position in that cloud
  *   len2(p,q) (dx*dx + dy*dy) + dz*dz of the float coordinates widened to double; an edge is short iff len2 <= max_edge^2
- *             (in double; NaN is not short)
+ *             (in double; NaN is not short).  A NaN the arithmetic produces only ever enters these comparisons: its sign and payload
+ *             are not part of the definition; the vertices are copies and keep the bits of whatever lies under a valid pixel.
  *   cells     r in [0, height-1), c in [0, width-1): corners a = (r,c), b = (r,c+1), d = (r+1,c), e = (r+1,c+1).
  *             4 valid corners: diagonal a-e iff len2(a,e) <= len2(b,d), candidates (a,d,e) then (a,e,b); else b-d, candidates
  *             (a,d,b) then (b,d,e).  3 valid corners: e missing (a,d,b); a missing (b,d,e); b missing (a,d,e); d missing (a,e,b).
@@ -415,7 +416,8 @@ int sl3d_get_meshes(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, 
  *                the vertex at pixel (r,c) the cells (r-1,c-1), (r-1,c), (r,c-1), (r,c), within a cell the cell's face order (<= 8 faces)
  *   normal       ss = (acc.x*acc.x + acc.y*acc.y) + acc.z*acc.z; if 0 < ss < +inf: n = (float)(acc / sqrt(ss)) per component (sqrt and
  *                division correctly rounded in double, the cast to nearest even); otherwise n = (+0,+0,+0): a vertex in no face,
- *                degenerate faces, an overflow, a NaN or infinity under a valid pixel
+ *                degenerate faces, an overflow, a NaN or infinity under a valid pixel.  Where the arithmetic PRODUCES a NaN (none
+ *                reaches a normal: NaN sums give +0), its sign and payload are not part of the definition.
  *   orientation  follows the faces: for points (x,y,z) = (col, row, f(col,row)) the normal is (f_x, f_y, -1)/|..|.  Nothing is flipped
  *                towards the camera: that choice is the caller's.
  *   output       one float triple per vertex in vertex-id order (the order of sl3d_get_cloud); deterministic as the faces are.
@@ -496,7 +498,9 @@ int sl3d_get_meshes_filtered(sl3d_ctx *ctx, int first_view, int n_views, float m
  *               Every +, -, *, / is one IEEE double operation, nothing contracted; the cast rounds to nearest even.  Ascending vertex id
  *               is the pixels' scan order: (r-1,c-1), (r-1,c), (r-1,c+1), (r,c-1), (r,c+1), (r+1,c-1), (r+1,c), (r+1,c+1).  A vertex with
  *               k = 0, or a fixed one, keeps p' = p bitwise.  All vertices of a step read the positions of the step before (Jacobi).  No
- *               special case for a NaN or infinity under a valid pixel: the arithmetic above is all there is.
+ *               special case for a NaN or infinity under a valid pixel: the arithmetic above is all there is.  The sign and payload of a
+ *               NaN the arithmetic PRODUCES (inf - inf after a step left the float range, ...) are not part of the definition; a NaN that
+ *               is copied (p' = p) keeps its bits.
  *   iterations  >= 1; each is one step with lambda, then one step with mu if mu != 0 (Taubin's lambda|mu; mu == 0: plain Laplacian
  *               smoothing).
  *   flags       SL3D_SMOOTH_FIX_BOUNDARY: boundary vertices are fixed (scans are open surfaces, and the umbrella operator shrinks their
