@@ -1,10 +1,11 @@
 // sl3d_block.h -- the block idioms of the kernels that turn a dense result into an ordered output (sl3d_clouds.hip: k_compact_count /
-// k_compact_scatter; sl3d_mesh.hip: k_mesh_count / k_mesh_emit; sl3d_mesh_normals.hip: k_mesh_normals_count / k_mesh_normals), each
+// k_compact_scatter; the mesh kernels of sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip and sl3d_mesh_smooth.hip), each
 // spelled once.  All of them run the same scheme over blocks of 256 threads (4 waves of 64), a lane owning 4 consecutive pixels: count per
 // 1024-pixel block, scan the counts (k_compact_scan), walk the block again, rank every output by wave prefixes, stage the block's
 // outputs in LDS in output order, flush them as one coalesced run.  (k_seg_scan / k_seg_close work on 16 waves and a 64-bit carry:
 // their own text, sl3d_clouds.hip.)  Every helper is inlined into its kernel: the kernels' instruction streams are those of the
-// written-out forms (profiles/r09_block_idioms_identity.txt).
+// written-out forms, identical or in another order with equal resource figures (profiles/r09_block_idioms_identity.txt,
+// profiles/mesh_idioms_identity.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,13 @@ __device__ __forceinline__ unsigned valid_nibble(unsigned w) { return (w & 1u) |
     if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;               \
     __syncthreads()
 #define BLOCK_SUM_TOTAL(s_cnt) (s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3])
+
+// the wave's sum of n over its lanes, in every lane
+__device__ __forceinline__ unsigned wave_sum(unsigned n)
+{
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    return n;
+}
 
 // inclusive prefix of c over the lane's wave; the wave's total goes to s_wave[wave] (__shared__ unsigned [4]), valid behind the barrier
 // this ends in

@@ -1,8 +1,9 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
-// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces, sl3d_mesh_normals.hip for the normals, sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing).  Every consumer of a dense result
-// keeps its counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, read_totals
-// brings its totals to the host.
+// Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces and the cell pass, sl3d_mesh_normals.hip for the normals,
+// sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing).  Every consumer of a dense result keeps its
+// counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, ensure_plane a plane
+// beside it, read_totals brings its totals to the host.
 #include "sl3d_capi_internal.h"
 
 typedef sl3d_ctx::Scan Scan;
@@ -470,11 +471,11 @@ static int ensure_mesh_buffers(sl3d_ctx *x)
     if (x->mesh_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
     const KParams &P = x->P;
     const size_t mv = (size_t)x->cfg.max_views;
-    x->mesh_face_stride = std::max<size_t>(1, 2 * (size_t)(P.W - 1) * (size_t)(P.H - 1));
+    x->mesh_face_stride = mesh_face_stride(P);
     int rc = ensure_scratch(x, x->chk_mesh, mv * 2 * (size_t)mesh_chunks(P), mv * 2);
     if (!rc) rc = ensure_scratch(x, x->blk_mesh, mv * compact_blocks(P), mv);
-    if (!rc && !x->d_mesh_xyz) rc = dev_alloc(x, &x->d_mesh_xyz, mv * P.px_view_stride * 3);
-    if (!rc && !x->d_mesh_faces) rc = dev_alloc(x, &x->d_mesh_faces, mv * x->mesh_face_stride * 3);
+    if (!rc) rc = ensure_plane(x, &x->d_mesh_xyz, mv * P.px_view_stride * 3);
+    if (!rc) rc = ensure_plane(x, &x->d_mesh_faces, mv * x->mesh_face_stride * 3);
     if (rc) return rc;
     x->mesh_ready = true;
     return SL3D_OK;
@@ -542,7 +543,7 @@ static int ensure_normal_buffers(sl3d_ctx *x)
     const KParams &P = x->P;
     const size_t mv = (size_t)x->cfg.max_views;
     int rc = ensure_scratch(x, x->chk_nrm, mv * (size_t)mesh_chunks(P), mv);
-    if (!rc && !x->d_normals) rc = dev_alloc(x, &x->d_normals, mv * P.px_view_stride * 3);
+    if (!rc) rc = ensure_plane(x, &x->d_normals, mv * P.px_view_stride * 3);
     if (rc) return rc;
     x->normals_ready = true;
     return SL3D_OK;
@@ -590,53 +591,51 @@ static int ensure_cc_buffers(sl3d_ctx *x)
 {
     if (x->cc_ready) return SL3D_OK;  // (one flag, set at the very end: ensure_cloud_buffers)
     const KParams &P = x->P;
-    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride, chunks = mv * (size_t)mesh_chunks(P);
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride;
     CcBuffers &b = x->cc;
-    int rc = SL3D_OK;
-    if (!b.cells) rc = dev_alloc(x, &b.cells, px);
-    if (!rc && !b.labels) rc = dev_alloc(x, &b.labels, px);
-    if (!rc && !b.vid) rc = dev_alloc(x, &b.vid, px);
-    if (!rc && !b.sizes) rc = dev_alloc(x, &b.sizes, px);
-    if (!rc && !x->d_cc_labels) rc = dev_alloc(x, &x->d_cc_labels, px);
-    if (!rc && !b.cnt) rc = dev_alloc(x, &b.cnt, chunks);
-    if (!rc && !b.off) rc = dev_alloc(x, &b.off, chunks);
-    if (!rc && !b.tot) rc = dev_alloc(x, &b.tot, 5 * mv);
+    int rc = ensure_plane(x, &b.cells, px);
+    if (!rc) rc = ensure_plane(x, &b.labels, px);
+    if (!rc) rc = ensure_plane(x, &b.vid, px);
+    if (!rc) rc = ensure_plane(x, &b.sizes, px);
+    if (!rc) rc = ensure_plane(x, &x->d_cc_labels, px);
+    // (the totals: the whole CcTotals array, whose first part is this scratch's)
+    if (!rc) rc = ensure_scratch(x, b.s, mv * (size_t)mesh_chunks(P), CcTotals{nullptr, mv}.words());
     if (rc) return rc;
-    x->ccf.tot = b.tot + mv;
-    b.stat = b.tot + 3 * mv;
+    b.stat = CcTotals{b.s.tot, mv}.stat(0);
     x->cc_ready = true;
     return SL3D_OK;
 }
 
+// (behind ensure_cc_buffers: the filter's totals are the `kept` part of the components' CcTotals array, so that a call reads both back at once)
 static int ensure_ccf_buffers(sl3d_ctx *x)
 {
     if (x->ccf_ready) return SL3D_OK;
     const KParams &P = x->P;
-    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride, chunks = mv * 2 * (size_t)mesh_chunks(P);
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride;
     CcFiltered &f = x->ccf;
-    f.face_stride = std::max<size_t>(1, 2 * (size_t)(P.W - 1) * (size_t)(P.H - 1));
-    int rc = SL3D_OK;
-    if (!f.keep) rc = dev_alloc(x, &f.keep, px);
-    if (!rc && !f.cnt) rc = dev_alloc(x, &f.cnt, chunks);
-    if (!rc && !f.off) rc = dev_alloc(x, &f.off, chunks);
-    if (!rc && !f.xyz) rc = dev_alloc(x, &f.xyz, 3 * px);
-    if (!rc && !f.ids) rc = dev_alloc(x, &f.ids, px);
-    if (!rc && !f.faces) rc = dev_alloc(x, &f.faces, mv * f.face_stride * 3);
+    if (!x->cc_ready) return fail(x, SL3D_E_INTERNAL, "the filter's buffers are set up behind the components'");
+    f.face_stride = mesh_face_stride(P);
+    f.s.tot = CcTotals{x->cc.s.tot, mv}.kept(0);  // (set: ensure_scratch allocates no totals of its own)
+    int rc = ensure_plane(x, &f.keep, px);
+    if (!rc) rc = ensure_scratch(x, f.s, mv * 2 * (size_t)mesh_chunks(P), 0);
+    if (!rc) rc = ensure_plane(x, &f.xyz, 3 * px);
+    if (!rc) rc = ensure_plane(x, &f.ids, px);
+    if (!rc) rc = ensure_plane(x, &f.faces, mv * f.face_stride * 3);
     if (rc) return rc;
     x->ccf_ready = true;
     return SL3D_OK;
 }
 
-// The one read-back of a components or filter call: x->cc.tot whole (5 words per view of the context).  A failure word set by a kernel
-// -- an iteration bound ran out: a logic error -- ends the call as SL3D_E_INTERNAL.  Synchronises for the caller
-static int read_cc_totals(sl3d_ctx *x, int first_view, int n_views, std::vector<unsigned long long> &t)
+// The one read-back of a components or filter call: the CcTotals array whole, t: its host copy.  A failure word set by a kernel -- an
+// iteration bound ran out: a logic error -- ends the call as SL3D_E_INTERNAL.  Synchronises for the caller
+static int read_cc_totals(sl3d_ctx *x, int first_view, int n_views, std::vector<unsigned long long> &words, CcTotals &t)
 {
-    const size_t mv = (size_t)x->cfg.max_views;
-    t.resize(5 * mv);
-    HIPCHK(x, hipMemcpyAsync(t.data(), x->cc.tot, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
+    words.resize(CcTotals{nullptr, (size_t)x->cfg.max_views}.words());
+    t = CcTotals{words.data(), (size_t)x->cfg.max_views};
+    HIPCHK(x, hipMemcpyAsync(words.data(), x->cc.s.tot, sizeof(unsigned long long) * words.size(), hipMemcpyDeviceToHost, x->stream));
     SYNC_FOR_CALLER(x);
     for (int v = first_view; v < first_view + n_views; v++)
-        if (t[3 * mv + 2 * (size_t)v + 1])
+        if (t.stat(v)[1])
             return fail(x, SL3D_E_INTERNAL, "mesh components: a label walk of view " + std::to_string(v) + " ran out of its iteration bound");
     return SL3D_OK;
 }
@@ -654,13 +653,13 @@ try {
     CcBuffers b = x->cc;
     b.labels_out = x->d_cc_labels;
     rc = launched(x, launch_mesh_components(P, first_view, n_views, max_edge, b, x->stream));
-    std::vector<unsigned long long> t;
-    if (!rc) rc = read_cc_totals(x, first_view, n_views, t);
+    std::vector<unsigned long long> words;
+    CcTotals t;
+    if (!rc) rc = read_cc_totals(x, first_view, n_views, words, t);
     if (rc) return rc;
-    const size_t mv = (size_t)x->cfg.max_views;
     for (int k = 0; k < n_views; k++) {
-        n_vertices[k] = (int64_t)t[(size_t)first_view + k];
-        n_components[k] = (int64_t)t[3 * mv + 2 * ((size_t)first_view + k)];
+        n_vertices[k] = (int64_t)t.vertices(first_view + k)[0];
+        n_components[k] = (int64_t)t.stat(first_view + k)[0];
     }
     if (device_labels) *device_labels = x->d_cc_labels + (size_t)first_view * P.px_view_stride;
     if (view_stride_points) *view_stride_points = P.px_view_stride;
@@ -709,13 +708,13 @@ try {
     rc = launched(x, launch_mesh_components(P, first_view, n_views, max_edge, b, x->stream));
     // (a component has fewer vertices than INT_MAX: every larger bar keeps nothing, as INT_MAX does)
     if (!rc) rc = launched(x, launch_mesh_filter(P, first_view, n_views, (int)std::min<int64_t>(min_vertices, INT32_MAX), b, x->ccf, x->stream));
-    std::vector<unsigned long long> t;
-    if (!rc) rc = read_cc_totals(x, first_view, n_views, t);
+    std::vector<unsigned long long> words;
+    CcTotals t;
+    if (!rc) rc = read_cc_totals(x, first_view, n_views, words, t);
     if (rc) return rc;
-    const size_t mv = (size_t)x->cfg.max_views;
     for (int k = 0; k < n_views; k++) {
-        n_vertices[k] = (int64_t)t[mv + 2 * ((size_t)first_view + k)];
-        n_faces[k] = (int64_t)t[mv + 2 * ((size_t)first_view + k) + 1];
+        n_vertices[k] = (int64_t)t.kept(first_view + k)[0];
+        n_faces[k] = (int64_t)t.kept(first_view + k)[1];
     }
     if (device_mesh) {
         device_mesh->xyz = x->ccf.xyz + 3 * (size_t)first_view * P.px_view_stride;
@@ -754,17 +753,14 @@ static int ensure_smooth_buffers(sl3d_ctx *x, bool normals)
 {
     const KParams &P = x->P;
     const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride;
-    int rc = SL3D_OK;
-    if (normals && !x->d_smooth_normals) rc = dev_alloc(x, &x->d_smooth_normals, 3 * px);
+    int rc = normals ? ensure_plane(x, &x->d_smooth_normals, 3 * px) : SL3D_OK;
     if (rc || x->smooth_ready) return rc;  // (one flag, set at the very end: ensure_cloud_buffers)
     SmoothBuffers &b = x->smooth;
-    if (!b.cells) rc = dev_alloc(x, &b.cells, px);
-    if (!rc && !b.rings) rc = dev_alloc(x, &b.rings, px);
-    if (!rc && !b.plane[0]) rc = dev_alloc(x, &b.plane[0], 3 * px);
-    if (!rc && !b.plane[1]) rc = dev_alloc(x, &b.plane[1], 3 * px);
-    if (!rc && !b.cnt) rc = dev_alloc(x, &b.cnt, mv * (size_t)mesh_chunks(P));
-    if (!rc && !b.off) rc = dev_alloc(x, &b.off, mv * (size_t)mesh_chunks(P));
-    if (!rc && !b.tot) rc = dev_alloc(x, &b.tot, mv);
+    if (!rc) rc = ensure_plane(x, &b.cells, px);
+    if (!rc) rc = ensure_plane(x, &b.rings, px);
+    if (!rc) rc = ensure_plane(x, &b.plane[0], 3 * px);
+    if (!rc) rc = ensure_plane(x, &b.plane[1], 3 * px);
+    if (!rc) rc = ensure_scratch(x, b.s, mv * (size_t)mesh_chunks(P), mv);
     if (rc) return rc;
     x->smooth_ready = true;
     return SL3D_OK;
@@ -797,7 +793,7 @@ try {
     SmoothBuffers b = x->smooth;
     b.normals = normals ? x->d_smooth_normals : nullptr;
     rc = launched(x, launch_mesh_smooth(P, first_view, n_views, max_edge, iterations, lambda, mu, flags & SL3D_SMOOTH_FIX_BOUNDARY, b, x->stream));
-    if (!rc) rc = read_totals(x, b.tot, 1, first_view, n_views, n_vertices);
+    if (!rc) rc = read_totals(x, b.s.tot, 1, first_view, n_views, n_vertices);
     if (rc) return rc;
     if (device_mesh) {
         device_mesh->xyz = b.plane[smooth_steps(iterations, mu) & 1] + 3 * (size_t)first_view * P.px_view_stride;

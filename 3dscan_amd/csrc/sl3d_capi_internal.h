@@ -45,6 +45,13 @@ inline int ensure_scratch(sl3d_ctx *c, CompactScratch &s, size_t counts, size_t 
     return rc;
 }
 
+// allocates a plane of `count` elements unless an earlier attempt already has
+template <typename T>
+inline int ensure_plane(sl3d_ctx *c, T **p, size_t count)
+{
+    return *p ? SL3D_OK : dev_alloc(c, p, count);
+}
+
 SL3D_INTERNAL int launched(sl3d_ctx *x, int hip_err);   // a launch's hipError_t -> status (+ the context's error text)
 SL3D_INTERNAL int need_keep(sl3d_ctx *x);               // SL3D_E_STATE unless the context keeps the stage planes
 SL3D_INTERNAL int check_view(sl3d_ctx *x, int view, int n = 1);

@@ -108,8 +108,8 @@ struct sl3d_ctx {
     bool normals_ready = false;               // ensure_normal_buffers ran to its end
     // sl3d_mesh_components / sl3d_mesh_views_filtered (all allocated on first use, nothing shared with the mesh or the normals call):
     // the planes and scratch of the union-find (CcBuffers, sl3d_internal.h; cc.labels_out is set per call) and the labels handed out;
-    // the filtered meshes (CcFiltered).  cc.tot is ONE array a call reads back whole: [max_views] vertices, [max_views][2] kept vertices and
-    // faces (ccf.tot), [max_views][2] components and the failure word (cc.stat)
+    // the filtered meshes (CcFiltered).  cc.s.tot is ONE array a call reads back whole, its layout CcTotals (sl3d_internal.h): cc.s.tot,
+    // ccf.s.tot and cc.stat point at its three parts
     CcBuffers cc{};
     int32_t *d_cc_labels = nullptr;
     bool cc_ready = false;                    // ensure_cc_buffers ran to its end

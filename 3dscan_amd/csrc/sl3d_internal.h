@@ -1,11 +1,12 @@
-// sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP
-// kernels (sl3d_fused_*.hip, sl3d_kernels.hip, sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip).  Not part of the public ABI.
-// What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes, mesh_row_chunks);
-// the block idioms of their kernels are in sl3d_block.h.
+// sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip).  Not part of
+// the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
+// mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include <hip/hip_runtime_api.h>   // dim3
 #include <hip/hip_vector_types.h>  // float2
 
 #include "sl3d_fused_choice.h"  // SL3D_MAX_GRAY, SL3D_SMALL_LAUNCH_VIEWS, SL3D_BLOCK, SL3D_SMALL_BLOCK, FusedKey
@@ -234,30 +235,67 @@ int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int
 // faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)
 int mesh_row_chunks(const KParams &P);
 int mesh_chunks(const KParams &P);
+inline size_t mesh_face_stride(const KParams &P)  // the faces a view can have (an allocation of at least 1)
+{
+    const size_t n = 2 * (size_t)(P.W - 1) * (size_t)(P.H - 1);
+    return n ? n : 1;
+}
+// what every launch_mesh_* starts from: chunks per row / per view, the grid of a kernel over every chunk of the launch's views, the input
+// planes and the pixel offset of its first view; sliced(s, k): a chunk scratch of k count arrays per view from that view on
+struct MeshLaunch {
+    int nck, n_chunks, first_view, n_views;
+    dim3 grid;
+    ViewPlanes in;
+    size_t v0;
+    CompactScratch sliced(const CompactScratch &s, int k) const
+    {
+        return {s.cnt + (size_t)first_view * k * n_chunks, s.off + (size_t)first_view * k * n_chunks, s.tot + (size_t)k * first_view};
+    }
+};
+inline MeshLaunch mesh_launch(const KParams &P, int first_view, int n_views)
+{
+    const int nck = mesh_row_chunks(P);
+    return {nck, P.H * nck, first_view, n_views, dim3(nck, P.H, n_views), view_planes(P, first_view), (size_t)first_view * P.px_view_stride};
+}
 int launch_mesh_views(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, int *faces, size_t face_stride,
                       void *stream);
 // vertex normals of those meshes (sl3d_mesh_normals.hip): s: the normals form of CompactScratch, normals: [max_views][normal_stride][3],
 // view v's in the order of its compacted cloud
 int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, float *normals,
                         size_t normal_stride, void *stream);
+// The cell pass of the components and the smoothing calls (k_mesh_cells, sl3d_mesh.hip) and the scan behind it: mesh_cell of every cell
+// once, left in cells ([max_views][px_view_stride], a byte per cell: cc_cell_code); c: the launch's slice of a [max_views][mesh_chunks]
+// scratch -- valid pixels per chunk, their scan, the views' totals.  labels != NULL: the union-find variant -- label of a pixel = its
+// own index, size = 0, stat (the launch's first view's) zeroed
+int launch_mesh_cells(const KParams &P, const MeshLaunch &L, float max_edge, uint8_t *cells, int *labels, int *sizes, unsigned long long *stat,
+                      const CompactScratch &c, void *stream);
+// The totals of a components / filter call: ONE device array of 5 words per view of the context, read back whole once per call.  `at`:
+// the array or its host copy, mv: the context's max_views
+struct CcTotals {
+    unsigned long long *at;
+    size_t mv;
+    unsigned long long *vertices(int v) const { return at + v; }                   // [mv] vertices (the cell pass's scan)
+    unsigned long long *kept(int v) const { return at + mv + 2 * (size_t)v; }      // [mv][2] kept vertices, kept faces (the filter's scan)
+    unsigned long long *stat(int v) const { return at + 3 * mv + 2 * (size_t)v; }  // [mv][2] components, failure word
+    size_t words() const { return 5 * mv; }
+};
 // connected components of those meshes and the meshes without their small components (sl3d_mesh_components.hip, sl3d_mesh_components.h).
 // Every plane is [max_views][px_view_stride]: cells = a byte per cell (cc_cell_code), labels = the union-find over pixel indices (after the
-// launch: every valid pixel's root), vid = vertex id of a pixel, sizes = vertices of the component at its root's pixel.  cnt / off:
-// [max_views][mesh_chunks] valid pixels per chunk and their scan, tot [max_views]; stat: [max_views][2] {components, failure word};
+// launch: every valid pixel's root), vid = vertex id of a pixel, sizes = vertices of the component at its root's pixel.  s: cnt / off
+// [max_views][mesh_chunks] valid pixels per chunk and their scan, tot = CcTotals::vertices; stat: CcTotals::stat;
 // labels_out: [max_views][px_view_stride] labels in vertex-id order, or NULL: the caller only wants the state the filter starts from
 struct CcBuffers {
     uint8_t *cells;
     int *labels, *vid, *sizes;
-    unsigned *cnt;
-    unsigned long long *off, *tot, *stat;
+    CompactScratch s;
+    unsigned long long *stat;
     int *labels_out;
 };
-// the filtered mesh: keep = 0/1 byte per pixel; cnt / off [max_views][2][mesh_chunks] (kept vertices, kept faces per chunk), tot
-// [max_views][2]; xyz [max_views][px_view_stride][3], ids [max_views][px_view_stride], faces [max_views][face_stride][3]
+// the filtered mesh: keep = 0/1 byte per pixel; s: cnt / off [max_views][2][mesh_chunks] (kept vertices, kept faces per chunk), tot =
+// CcTotals::kept; xyz [max_views][px_view_stride][3], ids [max_views][px_view_stride], faces [max_views][face_stride][3]
 struct CcFiltered {
     uint8_t *keep;
-    unsigned *cnt;
-    unsigned long long *off, *tot;
+    CompactScratch s;
     float *xyz;
     int *ids, *faces;
     size_t face_stride;
@@ -268,13 +306,12 @@ int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_ve
 // smoothing of those meshes (sl3d_mesh_smooth.hip, sl3d_mesh_smooth.h).  cells / rings: [max_views][px_view_stride] a byte per cell
 // (cc_cell_code) / per pixel (smooth_ring); plane[2]: [max_views][px_view_stride][3] the ping-pong planes of the steps -- step s writes
 // plane[s & 1], and plane[smooth_steps & 1], the one the last step did not write, takes the compacted vertices (view v's at 3 * v *
-// px_view_stride); cnt / off: [max_views][mesh_chunks] valid pixels per chunk and their scan, tot [max_views]; normals:
+// px_view_stride); s: cnt / off [max_views][mesh_chunks] valid pixels per chunk and their scan, tot [max_views]; normals:
 // [max_views][px_view_stride][3] in vertex-id order, or NULL: no normals asked for
 struct SmoothBuffers {
     uint8_t *cells, *rings;
     float *plane[2];
-    unsigned *cnt;
-    unsigned long long *off, *tot;
+    CompactScratch s;
     float *normals;
 };
 inline int smooth_steps(int iterations, float mu) { return iterations * (mu != 0.0f ? 2 : 1); }  // a step with mu == 0 is left out

@@ -1,8 +1,8 @@
 // sl3d_mesh.h -- the arithmetic of the mesh stage (sl3d_mesh_views): which triangles one cell of the organized point grid gives.
 //
-// Shared by k_mesh_count / k_mesh_emit (sl3d_mesh.hip), k_mesh_normals (sl3d_mesh_normals.hip) and by the CPU checks the test suite
-// runs over whole frames (tests/native/mesh_check.cpp, mesh_normals_check.cpp): plain C, no HIP types.  The reference has no mesh stage (its user meshed the PLY of stage 8 in
-// MeshLab); the definition is this library's own and every test checks it bit for bit:
+// Shared by every mesh kernel (sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip) and by the CPU
+// checks the test suite runs over whole frames (tests/native/mesh_*_check.cpp): plain C, no HIP types.  The reference has no mesh stage
+// (its user meshed the PLY of stage 8 in MeshLab); the definition is this library's own and every test checks it bit for bit:
 //
 //   cell (r, c), r in [0, H-1), c in [0, W-1): corners a = (r, c), b = (r, c+1), d = (r+1, c), e = (r+1, c+1)
 //   len2(p, q) = (dx*dx + dy*dy) + dz*dz with dx = (double)p.x - (double)q.x ..., IEEE double, no contraction
@@ -98,6 +98,41 @@ SL3D_MESH_FN unsigned mesh_cell(unsigned vbits, const float *a, const float *b, 
 // corner number j (0..2) of face k (0..1) of a mesh_cell result
 SL3D_MESH_FN unsigned mesh_corner(unsigned cell, int k, int j) { return (cell >> (2 + 6 * k + 2 * j)) & 3u; }
 
+// ---- the cell plane ------------------------------------------------------------------------------------------------------------
+// mesh_cell has seven outcomes -- no face, one of the four shapes, or one of the two pairs -- so a byte per cell (cc_cell_code) keeps
+// everything later passes need: what the cell connects, and its faces in output order (cc_code_cell gives the mesh_cell result back),
+// without evaluating the doubles again.  Written by k_mesh_cells (sl3d_mesh.hip) for the components and the smoothing calls.
+#define CC_ADE MESH_TRI(MESH_A, MESH_D, MESH_E)
+#define CC_AEB MESH_TRI(MESH_A, MESH_E, MESH_B)
+#define CC_ADB MESH_TRI(MESH_A, MESH_D, MESH_B)
+#define CC_BDE MESH_TRI(MESH_B, MESH_D, MESH_E)
+
+// a mesh_cell result as a code: 0 no face; 1 (a,d,e); 2 (a,e,b); 3 (a,d,b); 4 (b,d,e); 5 (a,d,e)(a,e,b); 6 (a,d,b)(b,d,e)
+SL3D_MESH_FN unsigned cc_cell_code(unsigned cell)
+{
+    const unsigned n = cell & 3u, t0 = cell >> 2 & 63u;
+    if (n == 0u) return 0u;
+    if (n == 2u) return t0 == CC_ADE ? 5u : 6u;
+    return t0 == CC_ADE ? 1u : t0 == CC_AEB ? 2u : t0 == CC_ADB ? 3u : 4u;
+}
+
+// ... and back
+SL3D_MESH_FN unsigned cc_code_cell(unsigned code)
+{
+    switch (code & 7u) {
+    case 1u: return 1u | CC_ADE << 2;
+    case 2u: return 1u | CC_AEB << 2;
+    case 3u: return 1u | CC_ADB << 2;
+    case 4u: return 1u | CC_BDE << 2;
+    case 5u: return 2u | CC_ADE << 2 | CC_AEB << 8;
+    case 6u: return 2u | CC_ADB << 2 | CC_BDE << 8;
+    default: return 0u;
+    }
+}
+
+// the corners the faces of a code touch, bit MESH_A.. as in mesh_cell's vbits: these are what the cell connects
+SL3D_MESH_FN unsigned cc_code_corners(unsigned code) { return 0x0ffe7bd0u >> (4u * (code & 7u)) & 15u; }
+
 // ---- vertex normals ------------------------------------------------------------------------------------------------------------------
 // the area-weighted normal of the face (p, q, s), in the order the face list gives its vertices
 SL3D_MESH_FN void mesh_face_vector(const float *p, const float *q, const float *s, double out[3])
@@ -126,6 +161,29 @@ SL3D_MESH_FN void mesh_pick(int first, const float *x, const float *y, float out
     out[0] = first ? x0 : y0, out[1] = first ? x1 : y1, out[2] = first ? x2 : y2;
 }
 
+// The faces of one cell -- `cell`: its mesh_cell result, a / b / d / e: its corners' points -- add their vectors to the sums of the cell's
+// corners `left` and `right`.  j (0..4): the column of corner a among a quad's 6 columns; `left` is pixel j - 1 of the quad (none for
+// j = 0), `right` pixel j (none for j = 4); acc[3 * k ..]: the sum of pixel k.  Face 0 before face 1, `left` before `right`.
+SL3D_MESH_FN void mesh_cell_sums(unsigned cell, const float *a, const float *b, const float *d, const float *e, int j, unsigned left, unsigned right,
+                                 double acc[12])
+{
+    SL3D_MESH_UNROLL
+    for (int f = 0; f < 2; f++)
+        if ((int)(cell & 3u) > f) {
+            const unsigned c0 = mesh_corner(cell, f, 0), c1 = mesh_corner(cell, f, 1), c2 = mesh_corner(cell, f, 2);
+            // the four shapes mesh_cell gives -- (a,d,e) (a,e,b) (a,d,b) (b,d,e) -- start at a or b, go on to d or e and end at e or b
+            float p[3], q[3], s[3];
+            double fn[3];
+            mesh_pick(c0 == MESH_A, a, b, p);
+            mesh_pick(c1 == MESH_D, d, e, q);
+            mesh_pick(c2 == MESH_E, e, b, s);
+            mesh_face_vector(p, q, s, fn);
+            const unsigned has = 1u << c0 | 1u << c1 | 1u << c2;
+            if (j >= 1 && (has >> left & 1u)) acc[3 * j - 3] += fn[0], acc[3 * j - 2] += fn[1], acc[3 * j - 1] += fn[2];
+            if (j <= 3 && (has >> right & 1u)) acc[3 * j] += fn[0], acc[3 * j + 1] += fn[1], acc[3 * j + 2] += fn[2];
+        }
+}
+
 // The cells of one cell row under a quad's 6 columns, left to right: the cell whose corner a is column j (0..4) adds its faces' vectors
 // to the sums of its corners `left` (pixel j - 1 of the quad) and `right` (pixel j).  vu / vl: valid bits of the cells' upper / lower
 // pixel row, bit j = column j; up / lo: the points of those rows (18 floats each; those of invalid pixels are not looked at).
@@ -135,22 +193,7 @@ SL3D_MESH_FN void mesh_cell_row_sums(unsigned vu, unsigned vl, const float *up, 
     SL3D_MESH_UNROLL
     for (int j = 0; j < 5; j++) {
         const float *a = up + 3 * j, *b = a + 3, *d = lo + 3 * j, *e = d + 3;
-        const unsigned cell = mesh_cell((vu >> j & 3u) | (vl >> j & 3u) << 2, a, b, d, e, thr2);
-        SL3D_MESH_UNROLL
-        for (int f = 0; f < 2; f++)
-            if ((int)(cell & 3u) > f) {
-                const unsigned c0 = mesh_corner(cell, f, 0), c1 = mesh_corner(cell, f, 1), c2 = mesh_corner(cell, f, 2);
-                // the four shapes mesh_cell gives -- (a,d,e) (a,e,b) (a,d,b) (b,d,e) -- start at a or b, go on to d or e and end at e or b
-                float p[3], q[3], s[3];
-                double fn[3];
-                mesh_pick(c0 == MESH_A, a, b, p);
-                mesh_pick(c1 == MESH_D, d, e, q);
-                mesh_pick(c2 == MESH_E, e, b, s);
-                mesh_face_vector(p, q, s, fn);
-                const unsigned has = 1u << c0 | 1u << c1 | 1u << c2;
-                if (j >= 1 && (has >> left & 1u)) acc[3 * j - 3] += fn[0], acc[3 * j - 2] += fn[1], acc[3 * j - 1] += fn[2];
-                if (j <= 3 && (has >> right & 1u)) acc[3 * j] += fn[0], acc[3 * j + 1] += fn[1], acc[3 * j + 2] += fn[2];
-            }
+        mesh_cell_sums(mesh_cell((vu >> j & 3u) | (vl >> j & 3u) << 2, a, b, d, e, thr2), a, b, d, e, j, left, right, acc);
     }
 }
 

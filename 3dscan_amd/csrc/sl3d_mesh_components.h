@@ -1,14 +1,12 @@
-// sl3d_mesh_components.h -- the connectivity of the mesh stage (sl3d_mesh_components / sl3d_mesh_views_filtered): what one cell connects
-// and the union-find that turns that into labels.  Shared by the kernels of sl3d_mesh_components.hip and by the CPU check the test
+// sl3d_mesh_components.h -- the connectivity of the mesh stage (sl3d_mesh_components / sl3d_mesh_views_filtered): the union-find
+// that turns what the cells connect into labels, and which faces a filter keeps.  Shared by the kernels of sl3d_mesh_components.hip and by the CPU check the test
 // suite runs over whole frames (tests/native/mesh_components_check.cpp): plain C, no HIP types.  The definition (include/sl3d.h):
 //
 //   two vertices are connected iff they share a face of the mesh sl3d_mesh_views defines; components: the transitive closure
 //   label of a vertex = the smallest vertex id of its component; vertex ids follow the pixels' scan order, so the smallest PIXEL index
 //   (r * pitch + c) of a component names the same vertex: the union-find runs on pixel indices, ids appear only on the way out
 //
-// The cell plane: mesh_cell (sl3d_mesh.h) has seven outcomes -- no face, one of the four shapes, or one of the two pairs -- so a byte
-// per cell (cc_cell_code) keeps everything later passes need: the unions, and the faces in output order (cc_code_cell gives the
-// mesh_cell result back), without evaluating the doubles again.
+// What a cell connects comes from the cell plane (cc_cell_code / cc_code_corners, sl3d_mesh.h).
 //
 // The union-find: L[x] is x (a root) or a smaller pixel index of the same component.  Labels only ever decrease, every write is an
 // atomic minimum, and nobody waits for anybody: a lost race shows as a value that is not the one expected, and the loser goes on with
@@ -43,38 +41,6 @@ static inline int cc_plain_fetch_min(int *p, int v)
 #define CC_FETCH_MIN(p, v) cc_plain_fetch_min((p), (v))
 #endif
 #endif
-
-// ---- the cell plane --------------------------------------------------------------------------------------------------------------
-#define CC_ADE MESH_TRI(MESH_A, MESH_D, MESH_E)
-#define CC_AEB MESH_TRI(MESH_A, MESH_E, MESH_B)
-#define CC_ADB MESH_TRI(MESH_A, MESH_D, MESH_B)
-#define CC_BDE MESH_TRI(MESH_B, MESH_D, MESH_E)
-
-// a mesh_cell result as a code: 0 no face; 1 (a,d,e); 2 (a,e,b); 3 (a,d,b); 4 (b,d,e); 5 (a,d,e)(a,e,b); 6 (a,d,b)(b,d,e)
-SL3D_CC_FN unsigned cc_cell_code(unsigned cell)
-{
-    const unsigned n = cell & 3u, t0 = cell >> 2 & 63u;
-    if (n == 0u) return 0u;
-    if (n == 2u) return t0 == CC_ADE ? 5u : 6u;
-    return t0 == CC_ADE ? 1u : t0 == CC_AEB ? 2u : t0 == CC_ADB ? 3u : 4u;
-}
-
-// ... and back
-SL3D_CC_FN unsigned cc_code_cell(unsigned code)
-{
-    switch (code & 7u) {
-    case 1u: return 1u | CC_ADE << 2;
-    case 2u: return 1u | CC_AEB << 2;
-    case 3u: return 1u | CC_ADB << 2;
-    case 4u: return 1u | CC_BDE << 2;
-    case 5u: return 2u | CC_ADE << 2 | CC_AEB << 8;
-    case 6u: return 2u | CC_ADB << 2 | CC_BDE << 8;
-    default: return 0u;
-    }
-}
-
-// the corners the faces of a code touch, bit MESH_A.. as in mesh_cell's vbits: these are what the cell connects
-SL3D_CC_FN unsigned cc_code_corners(unsigned code) { return 0x0ffe7bd0u >> (4u * (code & 7u)) & 15u; }
 
 // Does face f (0..1) of a cell survive the filter?  A face's vertices share a component, so one of them decides: its first, which is a
 // or b in all four shapes -- a pixel of the cell's upper row.  keep_a / keep_b: whether the components of those corners are kept.

@@ -1,10 +1,9 @@
 // sl3d_mesh_components.hip -- the connected components of the mesh sl3d_mesh_views defines, and that mesh without its small components
-// (sl3d_mesh_components / sl3d_mesh_views_filtered; the definition, the cell plane and the union-find: sl3d_mesh_components.h).
+// (sl3d_mesh_components / sl3d_mesh_views_filtered; the definition and the union-find: sl3d_mesh_components.h; the cell plane: sl3d_mesh.h).
 // A fixed sequence of launches over the mesh kernels' chunks (1024 pixels of ONE row, a lane owning one quad); nothing in it depends on
 // the data, no block waits for another, and every loop over labels is bounded (a failure ends as a word the call reads back):
-//   k_cc_cells   : mesh_cell of every cell ONCE, left as a byte per cell (cc_cell_code); label of a pixel = its own index, size = 0;
-//                  per chunk its valid pixels
-//   (k_compact_scan over the count array of every view: sl3d_clouds.hip)
+//   k_mesh_cells_uf and k_compact_scan over the count array of every view (launch_mesh_cells, sl3d_mesh.hip): the cell plane; label of a
+//                  pixel = its own index, size = 0; per chunk its valid pixels and their scan
 //   k_cc_union   : every cell with a face joins its corners -- a lock-free union-find on the label plane, atomic minima only
 //   k_cc_flatten : every valid pixel looks its root up and stores it; vertex id of the pixel (chunk offset + prefix) into the id plane;
 //                  the roots are counted and every root's size summed, both by integer atomic adds aggregated per wave first
@@ -18,7 +17,7 @@
 // Between kernels plain loads read what the kernel before wrote; inside k_cc_union and k_cc_flatten, where other blocks write labels,
 // every label access is an agent-scope relaxed atomic (CC_LOAD / CC_FETCH_MIN).  What a caller sees -- labels, counts, kept ids, faces --
 // is fixed by the definition: the atomics only decide who does which part of the work.
-// The block idioms live in sl3d_block.h, a lane's loads and cells in sl3d_mesh_lane.h.
+// The block idioms live in sl3d_block.h, a lane's loads, cells and staged faces in sl3d_mesh_lane.h.
 #include <hip/hip_runtime.h>
 
 #include "sl3d_block.h"
@@ -28,40 +27,9 @@
 
 namespace sl3d {
 
-// the 4 valid (or keep) bits of the lane's quad of a 0/1 byte plane row, clipped to the window; 0 for a quad beyond it
-__device__ __forceinline__ unsigned quad_bits(const uint8_t *__restrict__ row, int W, int c0)
-{
-    if (c0 >= W) return 0u;
-    const unsigned in_w = QUAD_IN_WINDOW(W, c0);
-    return valid_nibble(*(const unsigned *)(row + c0)) & in_w;
-}
-
 __device__ __forceinline__ void cc_record_failure(unsigned long long *stat)
 {
     __hip_atomic_store(stat + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// grid (chunks of a row, H, views).  cells / labels / sizes: [view][view_stride] planes; counts: [view][H * chunks]; stat: [view][2]
-// {roots, failure}, zeroed here for the kernels behind
-__global__ __launch_bounds__(256) void k_cc_cells(const uint8_t *__restrict__ valid, const float *__restrict__ points, int W, int H, int pitch,
-                                                  size_t view_stride, double thr2, uint8_t *__restrict__ cells, int *__restrict__ labels,
-                                                  int *__restrict__ sizes, unsigned *__restrict__ counts, unsigned long long *__restrict__ stat)
-{
-    const int r = blockIdx.y, nck = gridDim.x, c0 = blockIdx.x * MESH_CHUNK + threadIdx.x * 4;
-    const size_t row = (size_t)blockIdx.z * view_stride + (size_t)r * pitch;
-    __shared__ unsigned s_cnt[4];
-    unsigned v0, v1, cell[4];
-    mesh_lane(valid + row, points + 3 * row, W, pitch, c0, r + 1 < H, thr2, v0, v1, cell);
-    if (c0 < W) {  // (the quad lies inside the pitch: a multiple of 16)
-        const int p = r * pitch + c0;
-        *(unsigned *)(cells + row + c0) = cc_cell_code(cell[0]) | cc_cell_code(cell[1]) << 8 | cc_cell_code(cell[2]) << 16 | cc_cell_code(cell[3]) << 24;
-        *(int4 *)(labels + row + c0) = make_int4(p, p + 1, p + 2, p + 3);
-        *(int4 *)(sizes + row + c0) = make_int4(0, 0, 0, 0);
-    }
-    if (blockIdx.x == 0 && r == 0 && threadIdx.x == 0) stat[2 * blockIdx.z] = stat[2 * blockIdx.z + 1] = 0ull;
-    unsigned c = __popc(v0 & 15u);
-    BLOCK_SUM(c, s_cnt);
-    if (threadIdx.x == 0) counts[((size_t)blockIdx.z * H + r) * nck + blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
 }
 
 // grid (chunks of a row, H - 1, views); bound: the iteration bound of every label walk
@@ -82,14 +50,7 @@ __global__ __launch_bounds__(256) void k_cc_union(const uint8_t *__restrict__ ce
     if (failed) cc_record_failure(stat + 2 * blockIdx.z);
 }
 
-// the wave's sum of n over its lanes
-__device__ __forceinline__ unsigned wave_sum(unsigned n)
-{
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    return n;
-}
-
-// grid (chunks of a row, H, views); offsets: [view][H * chunks] exclusive scan of k_cc_cells' counts; vid: [view][view_stride] vertex ids
+// grid (chunks of a row, H, views); offsets: [view][H * chunks] exclusive scan of k_mesh_cells' counts; vid: [view][view_stride] vertex ids
 // (-1 under an invalid pixel)
 __global__ __launch_bounds__(256) void k_cc_flatten(const uint8_t *__restrict__ valid, int W, int H, int pitch, size_t view_stride, int bound,
                                                     const unsigned long long *__restrict__ offsets, int *labels, int *__restrict__ vid, int *sizes,
@@ -101,7 +62,7 @@ __global__ __launch_bounds__(256) void k_cc_flatten(const uint8_t *__restrict__ 
     sizes += (size_t)blockIdx.z * view_stride;
     stat += 2 * blockIdx.z;
     __shared__ unsigned s_wave[4];
-    const unsigned own = quad_bits(valid + row, W, c0);
+    const unsigned own = quad_bits(valid + row + c0, W, c0);
     const int p = r * pitch + c0;
     // the roots of the lane's pixels, stored (a minimum like every other write: the root is not above what stands there)
     int root[4] = {-1, -1, -1, -1}, failed = 0;
@@ -140,7 +101,7 @@ __global__ __launch_bounds__(256) void k_cc_flatten(const uint8_t *__restrict__ 
     if ((threadIdx.x & 63) == 0 && roots) atomicAdd(stat, (unsigned long long)roots);
 }
 
-// grid (chunks of a row, H, views); counts / offsets: k_cc_cells' and their scan; out: [view][out_stride] labels in vertex-id order
+// grid (chunks of a row, H, views); counts / offsets: k_mesh_cells' and their scan; out: [view][out_stride] labels in vertex-id order
 __global__ __launch_bounds__(256) void k_cc_labels(const uint8_t *__restrict__ valid, int W, int H, int pitch, size_t view_stride,
                                                    const unsigned *__restrict__ counts, const unsigned long long *__restrict__ offsets,
                                                    const int *__restrict__ labels, const int *__restrict__ vid, int *__restrict__ out, size_t out_stride)
@@ -153,7 +114,7 @@ __global__ __launch_bounds__(256) void k_cc_labels(const uint8_t *__restrict__ v
     vid += (size_t)blockIdx.z * view_stride;
     __shared__ unsigned s_wave[4];
     __shared__ int s_lab[MESH_CHUNK];  // the block's labels in output order
-    const unsigned own = quad_bits(valid + row, W, c0);
+    const unsigned own = quad_bits(valid + row + c0, W, c0);
     int lab[4] = {0, 0, 0, 0};
     if (own) {
         const int4 l = *(const int4 *)(labels + row + c0);
@@ -197,7 +158,7 @@ __global__ __launch_bounds__(256) void k_cc_keep(const uint8_t *__restrict__ val
     sizes += (size_t)blockIdx.z * view_stride;
     counts += (size_t)blockIdx.z * 2 * n_chunks;
     __shared__ unsigned s_cnt[4];
-    const unsigned own = quad_bits(valid + row, W, c0);
+    const unsigned own = quad_bits(valid + row + c0, W, c0);
     unsigned kb = 0u, nf = 0u;
     if (c0 < W) {
         const unsigned codes = *(const unsigned *)(cells + row + c0);
@@ -223,14 +184,6 @@ __global__ __launch_bounds__(256) void k_cc_keep(const uint8_t *__restrict__ val
         counts[chunk] = t & 0xffffu;
         counts[n_chunks + chunk] = t >> 16;
     }
-}
-
-// the 5 bits of pixels c0 .. c0 + 4 of a 0/1 byte plane row (bit 4: the pixel right of the quad; 0 beyond the window or without the row)
-__device__ __forceinline__ unsigned quad_bits5(const uint8_t *__restrict__ row, int W, int c0, bool have_row)
-{
-    if (c0 >= W || !have_row) return 0u;
-    const unsigned right = c0 + 4 < W ? row[c0 + 4] : 0u;
-    return quad_bits(row, W, c0) | (right & 1u) << 4;
 }
 
 // grid (chunks of a row, H, views); counts / offsets: k_cc_keep's and their scan; xyz: [view][point_stride][3], ids: [view][point_stride],
@@ -260,9 +213,8 @@ __global__ __launch_bounds__(256) void k_cc_emit(const uint8_t *__restrict__ kee
     const unsigned ev = waves_before(s_wave_v, wave_prefix(cv, s_wave_v) - cv);
     unsigned rank_f = waves_before(s_wave_f, wave_prefix(cf, s_wave_f) - cf);
     if (k0 & 15u) {
-        const float4 *p4 = (const float4 *)(points + 3 * (row + c0));
-        const float4 a = p4[0], b = p4[1], d = p4[2];
-        const float q[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, d.x, d.y, d.z, d.w};
+        float q[12];
+        load_quad(points + 3 * (row + c0), q);
         const int4 o = *(const int4 *)(vid + row + c0);
         const int orig[4] = {o.x, o.y, o.z, o.w};
         unsigned rank_v = ev & 0xffffu;
@@ -274,30 +226,9 @@ __global__ __launch_bounds__(256) void k_cc_emit(const uint8_t *__restrict__ kee
                 rank_v++;
             }
     }
-    if (cf) {
-        // new ids of pixels c0 .. c0 + 4 of both rows: the chunk's offset + the kept pixels of the chunk in front (the pixel right of the
-        // block's last quad is the next chunk's first: the same expression)
-        const int id0 = (int)offsets[chunk] + (int)(ev & 0xffffu), id1 = (int)offsets[chunk + nck] + (int)(ev >> 16);
-        int id[2][5];
-#pragma unroll
-        for (int j = 0; j < 5; j++) {
-            id[0][j] = id0 + __popc(k0 & ((1u << j) - 1u));
-            id[1][j] = id1 + __popc(k1 & ((1u << j) - 1u));
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-#pragma unroll
-            for (int f = 0; f < 2; f++)
-                if (fk[k] >> f & 1u) {
-#pragma unroll
-                    for (int j = 0; j < 3; j++) {
-                        const unsigned cn = mesh_corner(cell[k], f, j);
-                        const int lo = (cn & 2u) ? id[1][k] : id[0][k], hi = (cn & 2u) ? id[1][k + 1] : id[0][k + 1];
-                        s_faces[3 * rank_f + j] = (cn & 1u) ? hi : lo;
-                    }
-                    rank_f++;
-                }
-    }
+    // new ids of pixels c0 .. c0 + 4 of both rows: the chunk's offset + the kept pixels of the chunk in front (the pixel right of the
+    // block's last quad is the next chunk's first: the same expression)
+    if (cf) stage_faces<false>((int)offsets[chunk] + (int)(ev & 0xffffu), (int)offsets[chunk + nck] + (int)(ev >> 16), k0, k1, cell, fk, rank_f, s_faces);
     __syncthreads();
     // the block's points, ids and faces are contiguous in the output: coalesced dword stores
     const size_t at = (size_t)blockIdx.z * point_stride + offsets[chunk];
@@ -309,44 +240,38 @@ __global__ __launch_bounds__(256) void k_cc_emit(const uint8_t *__restrict__ kee
 // labels (buffers.labels_out != nullptr) or the state the filter starts from
 int launch_mesh_components(const KParams &P, int first_view, int n_views, float max_edge, const CcBuffers &b, void *stream)
 {
-    const int nck = mesh_row_chunks(P), n_chunks = P.H * nck, bound = (int)P.px_view_stride;
-    const ViewPlanes in = view_planes(P, first_view);
-    const size_t v0 = (size_t)first_view * P.px_view_stride;
-    unsigned *counts = b.cnt + (size_t)first_view * n_chunks;
-    unsigned long long *offsets = b.off + (size_t)first_view * n_chunks, *stat = b.stat + 2 * (size_t)first_view;
+    const MeshLaunch L = mesh_launch(P, first_view, n_views);
+    const CompactScratch c = L.sliced(b.s, 1);
+    const int bound = (int)P.px_view_stride;
+    const size_t v0 = L.v0;
+    unsigned long long *stat = b.stat + 2 * (size_t)first_view;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(nck, P.H, n_views);
-    hipLaunchKernelGGL(k_cc_cells, grid, dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, mesh_thr2(max_edge), b.cells + v0,
-                       b.labels + v0, b.sizes + v0, counts, stat);
-    int rc = launch_compact_scan(counts, offsets, n_chunks, n_views, b.tot + first_view, stream);
+    int rc = launch_mesh_cells(P, L, max_edge, b.cells, b.labels, b.sizes, stat, c, stream);
     if (rc) return rc;
     if (P.H > 1)
-        hipLaunchKernelGGL(k_cc_union, dim3(nck, P.H - 1, n_views), dim3(256), 0, st, (const uint8_t *)(b.cells + v0), P.W, P.pitch, P.px_view_stride, bound,
+        hipLaunchKernelGGL(k_cc_union, dim3(L.nck, P.H - 1, n_views), dim3(256), 0, st, (const uint8_t *)(b.cells + v0), P.W, P.pitch, P.px_view_stride, bound,
                            b.labels + v0, stat);
-    hipLaunchKernelGGL(k_cc_flatten, grid, dim3(256), 0, st, in.valid, P.W, P.H, P.pitch, P.px_view_stride, bound, (const unsigned long long *)offsets,
+    hipLaunchKernelGGL(k_cc_flatten, L.grid, dim3(256), 0, st, L.in.valid, P.W, P.H, P.pitch, P.px_view_stride, bound, (const unsigned long long *)c.off,
                        b.labels + v0, b.vid + v0, b.sizes + v0, stat);
     if (b.labels_out)
-        hipLaunchKernelGGL(k_cc_labels, grid, dim3(256), 0, st, in.valid, P.W, P.H, P.pitch, P.px_view_stride, (const unsigned *)counts,
-                           (const unsigned long long *)offsets, (const int *)(b.labels + v0), (const int *)(b.vid + v0), b.labels_out + v0, P.px_view_stride);
+        hipLaunchKernelGGL(k_cc_labels, L.grid, dim3(256), 0, st, L.in.valid, P.W, P.H, P.pitch, P.px_view_stride, (const unsigned *)c.cnt,
+                           (const unsigned long long *)c.off, (const int *)(b.labels + v0), (const int *)(b.vid + v0), b.labels_out + v0, P.px_view_stride);
     return (int)hipGetLastError();
 }
 
 // behind launch_mesh_components over the same views
 int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream)
 {
-    const int nck = mesh_row_chunks(P), n_chunks = P.H * nck;
-    const ViewPlanes in = view_planes(P, first_view);
-    const size_t v0 = (size_t)first_view * P.px_view_stride;
-    unsigned *counts = f.cnt + (size_t)first_view * 2 * n_chunks;
-    unsigned long long *offsets = f.off + (size_t)first_view * 2 * n_chunks;
+    const MeshLaunch L = mesh_launch(P, first_view, n_views);
+    const CompactScratch c = L.sliced(f.s, 2);
+    const size_t v0 = L.v0;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(nck, P.H, n_views);
-    hipLaunchKernelGGL(k_cc_keep, grid, dim3(256), 0, st, in.valid, (const uint8_t *)(b.cells + v0), P.W, P.H, P.pitch, P.px_view_stride,
-                       (const int *)(b.labels + v0), (const int *)(b.sizes + v0), min_vertices, f.keep + v0, counts);
-    int rc = launch_compact_scan(counts, offsets, n_chunks, 2 * n_views, f.tot + 2 * (size_t)first_view, stream);
+    hipLaunchKernelGGL(k_cc_keep, L.grid, dim3(256), 0, st, L.in.valid, (const uint8_t *)(b.cells + v0), P.W, P.H, P.pitch, P.px_view_stride,
+                       (const int *)(b.labels + v0), (const int *)(b.sizes + v0), min_vertices, f.keep + v0, c.cnt);
+    int rc = launch_compact_scan(c.cnt, c.off, L.n_chunks, 2 * n_views, c.tot, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_cc_emit, grid, dim3(256), 0, st, (const uint8_t *)(f.keep + v0), (const uint8_t *)(b.cells + v0), in.points, (const int *)(b.vid + v0),
-                       P.W, P.H, P.pitch, P.px_view_stride, (const unsigned *)counts, (const unsigned long long *)offsets, f.xyz + 3 * v0, f.ids + v0,
+    hipLaunchKernelGGL(k_cc_emit, L.grid, dim3(256), 0, st, (const uint8_t *)(f.keep + v0), (const uint8_t *)(b.cells + v0), L.in.points, (const int *)(b.vid + v0),
+                       P.W, P.H, P.pitch, P.px_view_stride, (const unsigned *)c.cnt, (const unsigned long long *)c.off, f.xyz + 3 * v0, f.ids + v0,
                        P.px_view_stride, f.faces + 3 * (size_t)first_view * f.face_stride, f.face_stride);
     return (int)hipGetLastError();
 }

@@ -8,12 +8,15 @@
 // No atomics, no adjacency lists, nothing read that sl3d_mesh_views wrote: the result follows from the planes and the scan alone, so it
 // does not depend on the launch shape, the batch or the run.
 // The scheme is the compaction's; its idioms -- valid-bit unpack, window clip, block sum, wave prefix, the waves in front, LDS flush --
-// live in sl3d_block.h.  Chunks per row: mesh_row_chunks (sl3d_mesh.hip); the planes of a launch's first view: view_planes (sl3d_internal.h).
+// live in sl3d_block.h, the count kernel's quad_bits in sl3d_mesh_lane.h.  k_mesh_normals keeps its valid bits, its rows and its ordered
+// output written out: load_row6, load_quad, a six-bit form of quad_bits and the output helper were each tried alone, each changes its
+// instruction histogram, and none was measured (profiles/mesh_idioms_identity.txt).  What a launch starts from: mesh_launch
+// (sl3d_internal.h).
 #include <hip/hip_runtime.h>
 
 #include "sl3d_block.h"
 #include "sl3d_internal.h"
-#include "sl3d_mesh.h"
+#include "sl3d_mesh_lane.h"
 
 namespace sl3d {
 
@@ -24,11 +27,7 @@ __global__ __launch_bounds__(256) void k_mesh_normals_count(const uint8_t *__res
     const int r = blockIdx.y, nck = gridDim.x, c0 = blockIdx.x * MESH_CHUNK + threadIdx.x * 4;
     valid += (size_t)blockIdx.z * view_stride + (size_t)r * pitch;
     __shared__ unsigned s_cnt[4];
-    unsigned c = 0u;
-    if (c0 < W) {
-        const unsigned in_w = QUAD_IN_WINDOW(W, c0);
-        c = __popc(valid_nibble(*(const unsigned *)(valid + c0)) & in_w);
-    }
+    unsigned c = __popc(quad_bits(valid + c0, W, c0));
     BLOCK_SUM(c, s_cnt);
     if (threadIdx.x == 0) counts[((size_t)blockIdx.z * gridDim.y + r) * nck + blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
 }
@@ -114,17 +113,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 int launch_mesh_normals(const KParams &P, int first_view, int n_views, float max_edge, const CompactScratch &s, float *normals,
                         size_t normal_stride, void *stream)
 {
-    const int nck = mesh_row_chunks(P), n_chunks = P.H * nck;
-    const ViewPlanes in = view_planes(P, first_view);
-    unsigned *counts = s.cnt + (size_t)first_view * n_chunks;
-    unsigned long long *offsets = s.off + (size_t)first_view * n_chunks;
+    const MeshLaunch L = mesh_launch(P, first_view, n_views);
+    const CompactScratch c = L.sliced(s, 1);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(nck, P.H, n_views);
-    hipLaunchKernelGGL(k_mesh_normals_count, grid, dim3(256), 0, st, in.valid, P.W, P.pitch, P.px_view_stride, counts);
-    int rc = launch_compact_scan(counts, offsets, n_chunks, n_views, s.tot + first_view, stream);
+    hipLaunchKernelGGL(k_mesh_normals_count, L.grid, dim3(256), 0, st, L.in.valid, P.W, P.pitch, P.px_view_stride, c.cnt);
+    int rc = launch_compact_scan(c.cnt, c.off, L.n_chunks, n_views, c.tot, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mesh_normals, grid, dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, mesh_thr2(max_edge),
-                       (const unsigned *)counts, (const unsigned long long *)offsets, normals + 3 * (size_t)first_view * normal_stride, normal_stride);
+    hipLaunchKernelGGL(k_mesh_normals, L.grid, dim3(256), 0, st, L.in.valid, L.in.points, P.W, P.H, P.pitch, P.px_view_stride, mesh_thr2(max_edge),
+                       (const unsigned *)c.cnt, (const unsigned long long *)c.off, normals + 3 * (size_t)first_view * normal_stride, normal_stride);
     return (int)hipGetLastError();
 }
 

@@ -12,9 +12,9 @@
 //                p' = (float)((double)p + f * (m - (double)p)); every operation one IEEE double operation, nothing contracted;
 //                ring 0: p' = p bitwise.  All vertices read the positions of the step before (Jacobi)
 //   normals      the definition of sl3d_mesh.h over the smoothed positions with the ORIGINAL connectivity: the cells come from the cell
-//                plane (cc_cell_code, sl3d_mesh_components.h), never from positions that have moved
+//                plane (cc_cell_code, sl3d_mesh.h), never from positions that have moved
 #pragma once
-#include "sl3d_mesh_components.h"
+#include "sl3d_mesh.h"
 
 #define SL3D_SMOOTH_FN SL3D_MESH_FN
 
@@ -98,28 +98,14 @@ SL3D_SMOOTH_FN void smooth_step(unsigned rings, const float *pt, const float *pm
     }
 }
 
-// ---- normals of the smoothed mesh: the coded twins of mesh_cell_row_sums / mesh_quad_sums (sl3d_mesh.h) ---------------------------------
+// ---- normals of the smoothed mesh: mesh_cell_row_sums / mesh_quad_sums (sl3d_mesh.h) with cell codes in place of mesh_cell -------------
 // codes: byte j = the code of the cell whose corner a is column j (0..4) of the 6 columns; everything else as in mesh_cell_row_sums
 SL3D_SMOOTH_FN void smooth_cell_row_sums(unsigned long long codes, const float *up, const float *lo, unsigned left, unsigned right, double acc[12])
 {
     SL3D_MESH_UNROLL
     for (int j = 0; j < 5; j++) {
         const float *a = up + 3 * j, *b = a + 3, *d = lo + 3 * j, *e = d + 3;
-        const unsigned cell = cc_code_cell((unsigned)(codes >> (8 * j)) & 255u);
-        SL3D_MESH_UNROLL
-        for (int f = 0; f < 2; f++)
-            if ((int)(cell & 3u) > f) {
-                const unsigned c0 = mesh_corner(cell, f, 0), c1 = mesh_corner(cell, f, 1), c2 = mesh_corner(cell, f, 2);
-                float p[3], q[3], s[3];
-                double fn[3];
-                mesh_pick(c0 == MESH_A, a, b, p);
-                mesh_pick(c1 == MESH_D, d, e, q);
-                mesh_pick(c2 == MESH_E, e, b, s);
-                mesh_face_vector(p, q, s, fn);
-                const unsigned has = 1u << c0 | 1u << c1 | 1u << c2;
-                if (j >= 1 && (has >> left & 1u)) acc[3 * j - 3] += fn[0], acc[3 * j - 2] += fn[1], acc[3 * j - 1] += fn[2];
-                if (j <= 3 && (has >> right & 1u)) acc[3 * j] += fn[0], acc[3 * j + 1] += fn[1], acc[3 * j + 2] += fn[2];
-            }
+        mesh_cell_sums(cc_code_cell((unsigned)(codes >> (8 * j)) & 255u), a, b, d, e, j, left, right, acc);
     }
 }
 

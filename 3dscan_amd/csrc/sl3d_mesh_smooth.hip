@@ -2,9 +2,8 @@
 // (sl3d_mesh_smooth; the definition, the ring and the step: sl3d_mesh_smooth.h).  The grid gives the adjacency: a vertex's neighbours are
 // among the 8 pixels around it, and which of them follows from the faces of the four cells around the pixel.  A fixed sequence of
 // launches over the mesh kernels' chunks (1024 pixels of ONE row, a lane owning one quad):
-//   k_smooth_cells   : mesh_cell of every cell ONCE, from the ORIGINAL positions, left as a byte per cell (cc_cell_code); per chunk its
-//                      valid pixels -- k_cc_cells without labels and sizes
-//   (k_compact_scan over the count array of every view: sl3d_clouds.hip)
+//   k_mesh_cells and k_compact_scan over the count array of every view (launch_mesh_cells, sl3d_mesh.hip): mesh_cell of every cell
+//                      ONCE, from the ORIGINAL positions, left as a byte per cell (cc_cell_code); per chunk its valid pixels and their scan
 //   k_smooth_ring    : ring byte of every pixel from the four cell bytes around it (smooth_quad_rings): integers only, no points
 //   k_smooth_step    : once per step.  A lane loads its ring dword and the points of rows r - 1, r, r + 1, columns c0 - 1 .. c0 + 4 that a
 //                      ring bit points at, evaluates smooth_step and stores its quad.  Ping-pong between two planes of the dense layout;
@@ -15,7 +14,9 @@
 //   k_smooth_out     : the final plane compacted into the other one: chunk offset from the scan, wave-prefix rank, LDS staging, one coalesced run per chunk
 //   k_smooth_normals : (on request) the gather of k_mesh_normals over the final plane with cell bytes in place of mesh_cell
 // No atomics, no block waits for another, nothing depends on the data: the result follows from the planes and the scan alone.
-// The block idioms live in sl3d_block.h, a lane's loads and cells in sl3d_mesh_lane.h.
+// The block idioms live in sl3d_block.h, a lane's loads (quad_bits, cell_codes5, load_quad, load_row6) in sl3d_mesh_lane.h.  k_smooth_out
+// and k_smooth_normals write their ordered output (rank, staging, barrier, flush) out: one helper for it changed their instruction
+// histograms and was not measured (profiles/mesh_idioms_identity.txt).
 #include <hip/hip_runtime.h>
 
 #include "sl3d_block.h"
@@ -24,31 +25,6 @@
 #include "sl3d_mesh_smooth.h"
 
 namespace sl3d {
-
-// grid (chunks of a row, H, views).  cells: [view][view_stride]; counts: [view][H * chunks]
-__global__ __launch_bounds__(256) void k_smooth_cells(const uint8_t *__restrict__ valid, const float *__restrict__ points, int W, int H, int pitch,
-                                                      size_t view_stride, double thr2, uint8_t *__restrict__ cells, unsigned *__restrict__ counts)
-{
-    const int r = blockIdx.y, nck = gridDim.x, c0 = blockIdx.x * MESH_CHUNK + threadIdx.x * 4;
-    const size_t row = (size_t)blockIdx.z * view_stride + (size_t)r * pitch;
-    __shared__ unsigned s_cnt[4];
-    unsigned v0, v1, cell[4];
-    mesh_lane(valid + row, points + 3 * row, W, pitch, c0, r + 1 < H, thr2, v0, v1, cell);
-    if (c0 < W)  // (the quad lies inside the pitch: a multiple of 16)
-        *(unsigned *)(cells + row + c0) = cc_cell_code(cell[0]) | cc_cell_code(cell[1]) << 8 | cc_cell_code(cell[2]) << 16 | cc_cell_code(cell[3]) << 24;
-    unsigned c = __popc(v0 & 15u);
-    BLOCK_SUM(c, s_cnt);
-    if (threadIdx.x == 0) counts[((size_t)blockIdx.z * H + r) * nck + blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
-}
-
-// the codes of the cells of columns c0 - 1 .. c0 + 3 of a cell-plane row, byte j = column c0 - 1 + j; 0 without the row (c0 < W: the dword
-// was written whole by k_smooth_cells, cells beyond the window as 0)
-__device__ __forceinline__ unsigned long long cell_codes5(const uint8_t *__restrict__ row, int c0, bool have_row)
-{
-    if (!have_row) return 0ull;
-    const unsigned left = c0 > 0 ? row[c0 - 1] : 0u;
-    return (unsigned long long)*(const unsigned *)(row + c0) << 8 | left;
-}
 
 // grid (chunks of a row, H, views); rings: [view][view_stride]
 __global__ __launch_bounds__(256) void k_smooth_ring(const uint8_t *__restrict__ cells, int W, int pitch, size_t view_stride, int fix_boundary,
@@ -61,24 +37,6 @@ __global__ __launch_bounds__(256) void k_smooth_ring(const uint8_t *__restrict__
     *(unsigned *)(rings + row + c0) = (up | mid) ? smooth_quad_rings(up, mid, fix_boundary) : 0u;
 }
 
-// The points of pixels c0 - 1 .. c0 + 4 of one row of a plane as 18 floats: columns c0 .. c0 + 3 as 16-byte loads if `quad`, the pixels left
-// and right of them if asked for (lines the neighbouring lanes request anyway); what is not loaded is 0.  p: the row's pixel c0
-__device__ __forceinline__ void load_row6(const float *__restrict__ p, bool quad, bool left, bool right, float q[18])
-{
-    float4 f0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), f1 = f0, f2 = f0;
-    if (quad) {
-        const float4 *p4 = (const float4 *)p;
-        f0 = p4[0], f1 = p4[1], f2 = p4[2];
-    }
-    const float m[12] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w, f2.x, f2.y, f2.z, f2.w};
-#pragma unroll
-    for (int i = 0; i < 3; i++) q[i] = left ? p[i - 3] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 12; i++) q[3 + i] = m[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) q[15 + i] = right ? p[12 + i] : 0.0f;
-}
-
 // grid (chunks of a row, H, views); src / dst: [view][view_stride][3]; f: the step's factor
 __global__ __launch_bounds__(256) void k_smooth_step(const uint8_t *__restrict__ valid, const uint8_t *__restrict__ rings, const float *__restrict__ src,
                                                      int W, int pitch, size_t view_stride, double f, float *__restrict__ dst)
@@ -86,8 +44,7 @@ __global__ __launch_bounds__(256) void k_smooth_step(const uint8_t *__restrict__
     const int r = blockIdx.y, c0 = blockIdx.x * MESH_CHUNK + threadIdx.x * 4;
     if (c0 >= W) return;
     const size_t px = (size_t)blockIdx.z * view_stride + (size_t)r * pitch + c0;
-    const unsigned in_w = QUAD_IN_WINDOW(W, c0);
-    const unsigned own = valid_nibble(*(const unsigned *)(valid + px)) & in_w;
+    const unsigned own = quad_bits(valid + px, W, c0);
     if (!own) return;
     const unsigned ring = *(const unsigned *)(rings + px);
     // bits 0..2 of a ring byte point into row r - 1, bits 5..7 into row r + 1; bits 0, 3, 5 of pixel 0 at column c0 - 1, bits 2, 4, 7 of
@@ -106,7 +63,7 @@ __global__ __launch_bounds__(256) void k_smooth_step(const uint8_t *__restrict__
     d4[2] = make_float4(o[8], o[9], o[10], o[11]);
 }
 
-// grid (chunks of a row, H, views); counts / offsets: k_smooth_cells' and their scan; out: [view][out_stride][3] in vertex-id order
+// grid (chunks of a row, H, views); counts / offsets: k_mesh_cells' and their scan; out: [view][out_stride][3] in vertex-id order
 __global__ __launch_bounds__(256) void k_smooth_out(const uint8_t *__restrict__ valid, const float *__restrict__ plane, int W, int H, int pitch,
                                                     size_t view_stride, const unsigned *__restrict__ counts,
                                                     const unsigned long long *__restrict__ offsets, float *__restrict__ out, size_t out_stride)
@@ -118,20 +75,12 @@ __global__ __launch_bounds__(256) void k_smooth_out(const uint8_t *__restrict__ 
     const size_t px = (size_t)blockIdx.z * view_stride + (size_t)r * pitch + c0;
     __shared__ unsigned s_wave[4];
     __shared__ float s_pts[3 * MESH_CHUNK];  // the block's points in output order
-    unsigned own = 0u;
-    if (c0 < W) {
-        const unsigned in_w = QUAD_IN_WINDOW(W, c0);
-        own = valid_nibble(*(const unsigned *)(valid + px)) & in_w;
-    }
-    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, d = a;
-    if (own) {
-        const float4 *p4 = (const float4 *)(plane + 3 * px);
-        a = p4[0], b = p4[1], d = p4[2];
-    }
+    const unsigned own = quad_bits(valid + px, W, c0);
+    float q[12] = {};
+    if (own) load_quad(plane + 3 * px, q);
     const unsigned cv = __popc(own);
     unsigned rank = waves_before(s_wave, wave_prefix(cv, s_wave) - cv);
     if (own) {
-        const float q[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int k = 0; k < 4; k++)
             if (own >> k & 1u) {
@@ -158,8 +107,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     unsigned own = 0u;
     unsigned long long up = 0ull, mid = 0ull;
     if (c0 < W) {
-        const unsigned in_w = QUAD_IN_WINDOW(W, c0);
-        own = valid_nibble(*(const unsigned *)(valid + px)) & in_w;
+        own = quad_bits(valid + px, W, c0);
         if (own) mid = cell_codes5(cells + px - c0, c0, true), up = cell_codes5(cells + px - c0 - pitch, c0, r > 0);
     }
     float n[4][3] = {};
@@ -193,34 +141,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 int launch_mesh_smooth(const KParams &P, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu, bool fix_boundary,
                        const SmoothBuffers &b, void *stream)
 {
-    const int nck = mesh_row_chunks(P), n_chunks = P.H * nck;
-    const ViewPlanes in = view_planes(P, first_view);
-    const size_t v0 = (size_t)first_view * P.px_view_stride;
-    unsigned *counts = b.cnt + (size_t)first_view * n_chunks;
-    unsigned long long *offsets = b.off + (size_t)first_view * n_chunks;
+    const MeshLaunch L = mesh_launch(P, first_view, n_views);
+    const CompactScratch c = L.sliced(b.s, 1);
+    const size_t v0 = L.v0;
+    const unsigned *counts = c.cnt;
+    const unsigned long long *offsets = c.off;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(nck, P.H, n_views);
-    hipLaunchKernelGGL(k_smooth_cells, grid, dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, mesh_thr2(max_edge),
-                       b.cells + v0, counts);
-    int rc = launch_compact_scan(counts, offsets, n_chunks, n_views, b.tot + first_view, stream);
+    int rc = launch_mesh_cells(P, L, max_edge, b.cells, nullptr, nullptr, nullptr, c, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_smooth_ring, grid, dim3(256), 0, st, (const uint8_t *)(b.cells + v0), P.W, P.pitch, P.px_view_stride, (int)fix_boundary,
+    hipLaunchKernelGGL(k_smooth_ring, L.grid, dim3(256), 0, st, (const uint8_t *)(b.cells + v0), P.W, P.pitch, P.px_view_stride, (int)fix_boundary,
                        b.rings + v0);
     // step s reads what step s - 1 wrote (the first: the context's points) and writes plane s & 1; the plane the last step did not write
     // takes the compacted vertices
-    const float *src = in.points;
+    const float *src = L.in.points;
     const int per = mu != 0.0f ? 2 : 1, steps = smooth_steps(iterations, mu);
     for (int s = 0; s < steps; s++) {
         float *dst = b.plane[s & 1] + 3 * v0;
-        hipLaunchKernelGGL(k_smooth_step, grid, dim3(256), 0, st, in.valid, (const uint8_t *)(b.rings + v0), src, P.W, P.pitch, P.px_view_stride,
+        hipLaunchKernelGGL(k_smooth_step, L.grid, dim3(256), 0, st, L.in.valid, (const uint8_t *)(b.rings + v0), src, P.W, P.pitch, P.px_view_stride,
                            (double)(s % per ? mu : lambda), dst);
         src = dst;
     }
-    hipLaunchKernelGGL(k_smooth_out, grid, dim3(256), 0, st, in.valid, src, P.W, P.H, P.pitch, P.px_view_stride, (const unsigned *)counts,
-                       (const unsigned long long *)offsets, b.plane[steps & 1] + 3 * v0, P.px_view_stride);
+    hipLaunchKernelGGL(k_smooth_out, L.grid, dim3(256), 0, st, L.in.valid, src, P.W, P.H, P.pitch, P.px_view_stride, counts, offsets,
+                       b.plane[steps & 1] + 3 * v0, P.px_view_stride);
     if (b.normals)
-        hipLaunchKernelGGL(k_smooth_normals, grid, dim3(256), 0, st, in.valid, (const uint8_t *)(b.cells + v0), src, P.W, P.H, P.pitch,
-                           P.px_view_stride, (const unsigned *)counts, (const unsigned long long *)offsets, b.normals + 3 * v0, P.px_view_stride);
+        hipLaunchKernelGGL(k_smooth_normals, L.grid, dim3(256), 0, st, L.in.valid, (const uint8_t *)(b.cells + v0), src, P.W, P.H, P.pitch,
+                           P.px_view_stride, counts, offsets, b.normals + 3 * v0, P.px_view_stride);
     return (int)hipGetLastError();
 }
 

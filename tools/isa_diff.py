@@ -6,7 +6,9 @@ files per side may be given separated by commas).  For every kernel symbol prese
 compared after normalising what a refactoring may legitimately change: comments, directives, local label numbers.
 Prints one line per kernel that differs (first differing instruction + the instruction-histogram delta) and a summary.
 With `--kernarg` the immediate offsets of scalar loads from the kernel-argument segment (s[0:1] / s[4:5] ...) are masked too
-(a change of the KParams layout moves them and nothing else)."""
+(a change of the KParams layout moves them and nothing else).  `--pair=OLD=NEW` (any number of them) also compares the kernel of A
+whose name (demangled where llvm-cxxfilt is there, mangled otherwise) contains OLD -- OLD holds no `=` -- with the kernel of B whose
+name contains NEW: a kernel that was renamed."""
 import collections
 import re
 import subprocess
@@ -63,24 +65,26 @@ def main():
     mask = "--kernarg" in sys.argv
     A, B = kernels(args[0], mask), kernels(args[1], mask)
     sub = args[2] if len(args) > 2 else ""
-    common = sorted(set(A) & set(B))
-    names = demangle(common)
+    names = demangle(sorted(set(A) | set(B)))
+    pairs = [(k, k, names[k]) for k in sorted(set(A) & set(B)) if not sub or sub in names[k]]
+    for old, new in (a[len("--pair="):].split("=", 1) for a in sys.argv[1:] if a.startswith("--pair=")):
+        ka, kb = [k for k in A if old in names[k]], [k for k in B if new in names[k]]
+        if len(ka) != 1 or len(kb) != 1:
+            sys.exit(f"--pair={old}={new}: {len(ka)} kernels of A and {len(kb)} of B match")
+        pairs.append((ka[0], kb[0], f"{names[ka[0]]} = {names[kb[0]]}"))
     same = diff = 0
-    for k in common:
-        if sub and sub not in names[k]:
-            continue
-        if A[k] == B[k]:
+    for ka, kb, name in pairs:
+        a, b = A[ka], B[kb]
+        if a == b:
             same += 1
             continue
         diff += 1
-        ha = collections.Counter(s.split()[0] for s in A[k] if not s.endswith(":"))
-        hb = collections.Counter(s.split()[0] for s in B[k] if not s.endswith(":"))
+        ha = collections.Counter(s.split()[0] for s in a if not s.endswith(":"))
+        hb = collections.Counter(s.split()[0] for s in b if not s.endswith(":"))
         delta = {op: hb[op] - ha[op] for op in set(ha) | set(hb) if hb[op] != ha[op]}
-        first = next((i for i, (x, y) in enumerate(zip(A[k], B[k])) if x != y), min(len(A[k]), len(B[k])))
-        print(f"DIFF {names[k]}: {len(A[k])} -> {len(B[k])} lines, first difference at {first}: "
-              f"{A[k][first] if first < len(A[k]) else '<end>'!r} vs {B[k][first] if first < len(B[k]) else '<end>'!r}; histogram delta {delta or 'none (order only)'}")
-    onlyA = [names.get(k, k) for k in sorted(set(A) - set(B)) if not sub or sub in k]
-    onlyB = [k for k in sorted(set(B) - set(A)) if not sub or sub in k]
+        first = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+        print(f"DIFF {name}: {len(a)} -> {len(b)} lines, first difference at {first}: "
+              f"{a[first] if first < len(a) else '<end>'!r} vs {b[first] if first < len(b) else '<end>'!r}; histogram delta {delta or 'none (order only)'}")
     print(f"{same} kernels identical, {diff} differ; {len(set(A) - set(B))} only in A, {len(set(B) - set(A))} only in B")
 
 
