@@ -1,10 +1,11 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
 // Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces and the cell pass, sl3d_mesh_normals.hip for the normals,
-// sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing).  Every consumer of a dense result keeps its
+// sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing, sl3d_mesh_lod.hip for the level-of-detail mesh).  Every consumer of a dense result keeps its
 // counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, ensure_plane a plane
 // beside it, read_totals brings its totals to the host.
 #include "sl3d_capi_internal.h"
+#include "sl3d_mesh_lod.h"  // LOD_MAX_STEP
 
 typedef sl3d_ctx::Scan Scan;
 
@@ -816,6 +817,130 @@ try {
     if (rc) return rc;
     rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
     if (!rc && m.normals) rc = download_clamped(x, normals, m.normals, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (rc) return rc;
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// ---- the level-of-detail mesh: one vertex per step x step pixel block (include/sl3d.h: the definition; sl3d_mesh_lod.h: its arithmetic;
+// sl3d_mesh_lod.hip: the block pass) ---------------------------------------------------------------------------------------------------
+// the buffers of a call at `step` over the coarse grid C = lod_params(P, step, ..): every array at C's sizes, or larger from an earlier call
+static int ensure_lod_buffers(sl3d_ctx *x, const KParams &C, bool normals, bool fine_scan)
+{
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * C.px_view_stride, chunks = mv * (size_t)mesh_chunks(C), blocks = mv * compact_blocks(C);
+    LodBuffers &b = x->lod;
+    size_t *cap = x->lod_cap;
+    const size_t face_stride = mesh_face_stride(C);
+    int rc = grow_plane(x, &x->d_lod_valid, cap + 0, px);
+    if (!rc) rc = grow_plane(x, &x->d_lod_points, cap + 1, 3 * px);
+    if (!rc) rc = grow_plane(x, &b.ids, cap + 2, px);
+    if (!rc) rc = grow_plane(x, &b.blk.cnt, cap + 3, blocks);
+    if (!rc) rc = grow_plane(x, &b.blk.off, cap + 4, blocks);
+    if (!rc) rc = grow_plane(x, &b.blk.tot, cap + 5, mv);
+    if (!rc) rc = grow_plane(x, &b.chk.cnt, cap + 6, 2 * chunks);
+    if (!rc) rc = grow_plane(x, &b.chk.off, cap + 7, 2 * chunks);
+    if (!rc) rc = grow_plane(x, &b.chk.tot, cap + 8, 2 * mv);
+    if (!rc) rc = grow_plane(x, &b.xyz, cap + 9, 3 * px);
+    if (!rc) rc = grow_plane(x, &b.vertex_ids, cap + 10, px);
+    if (!rc) rc = grow_plane(x, &b.faces, cap + 11, 3 * mv * face_stride);
+    if (!rc && normals) {
+        rc = grow_plane(x, &b.normals, cap + 12, 3 * px);
+        if (!rc) rc = grow_plane(x, &b.nrm.cnt, cap + 13, chunks);
+        if (!rc) rc = grow_plane(x, &b.nrm.off, cap + 14, chunks);
+        if (!rc) rc = grow_plane(x, &b.nrm.tot, cap + 15, mv);
+    }
+    if (!rc && fine_scan) {  // (the fine window's sizes: the same at every step)
+        const size_t fine_chunks = mv * (size_t)mesh_chunks(P);
+        rc = grow_plane(x, &x->d_lod_cells, cap + 16, mv * P.px_view_stride);
+        if (!rc) rc = grow_plane(x, &x->lod_fine.cnt, cap + 17, fine_chunks);
+        if (!rc) rc = grow_plane(x, &x->lod_fine.off, cap + 18, fine_chunks);
+        if (!rc) rc = grow_plane(x, &x->lod_fine.tot, cap + 19, mv);
+    }
+    if (rc) return rc;
+    b.face_stride = face_stride;
+    return SL3D_OK;
+}
+
+static int check_lod_args(sl3d_ctx *x, int first_view, int n_views, int step, float max_edge, int64_t min_vertices, float lod_edge, unsigned flags,
+                          const int64_t *n_vertices, const int64_t *n_faces)
+{
+    const int rc = check_filter_args(x, first_view, n_views, max_edge, min_vertices, n_vertices, n_faces);
+    if (rc) return rc;
+    if (step < 1 || step > LOD_MAX_STEP) return fail(x, SL3D_E_INVALID_ARG, "step must lie in [1, 16]");
+    if (!(lod_edge > 0.0f)) return fail(x, SL3D_E_INVALID_ARG, "lod_edge must be > 0 (+inf: no edge-length test)");  // (false for NaN)
+    if (flags & ~(SL3D_LOD_MEAN | SL3D_LOD_NORMALS)) return fail(x, SL3D_E_INVALID_ARG, "unknown level-of-detail flag");
+    return SL3D_OK;
+}
+
+// min_vertices == 1: cells and scan (for the ids), blocks, the compaction's three and the mesh's three launches over the coarse grid, ids
+// (+ the normals' three): 10 (13) launches.  min_vertices > 1: the components' four launches and the keep bytes in place of the first two.
+// One read-back of the 2 totals per view (and, behind the components, of their failure words)
+extern "C" int sl3d_mesh_views_lod(sl3d_ctx *x, int first_view, int n_views, int step, float max_edge, int64_t min_vertices, float lod_edge,
+                                   unsigned flags, sl3d_mesh_lod *device_mesh, int64_t *n_vertices, int64_t *n_faces)
+try {
+    int rc = check_lod_args(x, first_view, n_views, step, max_edge, min_vertices, lod_edge, flags, n_vertices, n_faces);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    const bool normals = flags & SL3D_LOD_NORMALS, filtered = min_vertices > 1;
+    KParams C = lod_params(P, step, nullptr, nullptr);
+    rc = ensure_lod_buffers(x, C, normals, !filtered);
+    if (!rc && filtered) rc = ensure_cc_buffers(x);
+    if (!rc && filtered) rc = ensure_ccf_buffers(x);
+    if (rc) return rc;
+    C.valid = x->d_lod_valid, C.points = x->d_lod_points;
+    LodSource src{};
+    if (filtered) {
+        CcBuffers b = x->cc;
+        b.labels_out = nullptr;
+        rc = launched(x, launch_mesh_components(P, first_view, n_views, max_edge, b, x->stream));
+        if (!rc) rc = launched(x, launch_mesh_keep(P, first_view, n_views, (int)std::min<int64_t>(min_vertices, INT32_MAX), b, x->ccf, x->stream));
+        src = LodSource{x->ccf.keep, nullptr, x->cc.vid};
+    } else {
+        const MeshLaunch L = mesh_launch(P, first_view, n_views);
+        const CompactScratch c = L.sliced(x->lod_fine, 1);
+        rc = launched(x, launch_mesh_cells(P, L, max_edge, x->d_lod_cells, nullptr, nullptr, nullptr, c, x->stream));
+        src = LodSource{P.valid, c.off, nullptr};
+    }
+    if (!rc) rc = launched(x, launch_mesh_lod(P, C, first_view, n_views, step, lod_edge, flags & SL3D_LOD_MEAN, src, x->lod, normals, x->stream));
+    if (!rc) rc = read_totals(x, x->lod.chk.tot, 2, first_view, n_views, n_vertices, n_faces);
+    if (!rc && filtered) {
+        std::vector<unsigned long long> words;
+        CcTotals t;
+        rc = read_cc_totals(x, first_view, n_views, words, t);
+    }
+    if (rc) return rc;
+    if (device_mesh) {
+        device_mesh->xyz = x->lod.xyz + 3 * (size_t)first_view * C.px_view_stride;
+        device_mesh->faces = x->lod.faces + 3 * (size_t)first_view * x->lod.face_stride;
+        device_mesh->vertex_ids = x->lod.vertex_ids + (size_t)first_view * C.px_view_stride;
+        device_mesh->normals = normals ? x->lod.normals + 3 * (size_t)first_view * C.px_view_stride : nullptr;
+        device_mesh->view_stride_points = C.px_view_stride;
+        device_mesh->view_stride_faces = x->lod.face_stride;
+        device_mesh->grid_width = C.W;
+        device_mesh->grid_height = C.H;
+    }
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: vertices, original ids and normals of the views back to back, their faces back to back
+extern "C" int sl3d_get_meshes_lod(sl3d_ctx *x, int first_view, int n_views, int step, float max_edge, int64_t min_vertices, float lod_edge,
+                                   unsigned flags, float *xyz, int32_t *vertex_ids, float *normals, int64_t vertex_capacity, int32_t *faces,
+                                   int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces)
+try {
+    int rc = check_lod_args(x, first_view, n_views, step, max_edge, min_vertices, lod_edge, flags, n_vertices, n_faces);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    sl3d_mesh_lod m;
+    rc = sl3d_mesh_views_lod(x, first_view, n_views, step, max_edge, min_vertices, lod_edge, flags, &m, n_vertices, n_faces);
+    if (rc) return rc;
+    rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc) rc = download_clamped(x, vertex_ids, m.vertex_ids, m.view_stride_points, n_views, n_vertices, vertex_capacity, 4);
+    if (!rc && m.normals) rc = download_clamped(x, normals, m.normals, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc) rc = download_clamped(x, faces, m.faces, m.view_stride_faces, n_views, n_faces, face_capacity);
     if (rc) return rc;
     SYNC_FOR_CALLER(x);
     return SL3D_OK;

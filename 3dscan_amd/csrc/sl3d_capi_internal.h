@@ -52,6 +52,23 @@ inline int ensure_plane(sl3d_ctx *c, T **p, size_t count)
     return *p ? SL3D_OK : dev_alloc(c, p, count);
 }
 
+// a plane of at least `count` elements: *cap of them are there; one that is too small is freed (the device is idle then: hipFree
+// waits) and allocated again
+template <typename T>
+inline int grow_plane(sl3d_ctx *c, T **p, size_t *cap, size_t count)
+{
+    if (*p && *cap >= count) return SL3D_OK;
+    if (*p) {
+        (void)hipFree(*p);
+        c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), (void *)*p), c->allocs.end());
+        *p = nullptr;
+        *cap = 0;
+    }
+    const int rc = dev_alloc(c, p, count);
+    if (!rc) *cap = count;
+    return rc;
+}
+
 SL3D_INTERNAL int launched(sl3d_ctx *x, int hip_err);   // a launch's hipError_t -> status (+ the context's error text)
 SL3D_INTERNAL int need_keep(sl3d_ctx *x);               // SL3D_E_STATE unless the context keeps the stage planes
 SL3D_INTERNAL int check_view(sl3d_ctx *x, int view, int n = 1);

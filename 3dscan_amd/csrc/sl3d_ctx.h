@@ -121,6 +121,16 @@ struct sl3d_ctx {
     SmoothBuffers smooth{};
     float *d_smooth_normals = nullptr;
     bool smooth_ready = false;                // ensure_smooth_buffers ran to its end
+    // sl3d_mesh_views_lod (all allocated on first use for the step asked, grown when a later call needs more; the outputs share nothing
+    // with the calls above): the coarse valid / point planes the block pass writes and everything launched over them (LodBuffers,
+    // sl3d_internal.h); for min_vertices == 1 the cell bytes and the chunk scratch of the cell pass that gives the ids.  lod_cap: the
+    // elements every one of those arrays holds, in the order ensure_lod_buffers names them
+    uint8_t *d_lod_valid = nullptr;
+    float *d_lod_points = nullptr;
+    LodBuffers lod{};
+    uint8_t *d_lod_cells = nullptr;
+    CompactScratch lod_fine{};
+    size_t lod_cap[20] = {0};
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

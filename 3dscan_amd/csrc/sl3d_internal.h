@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -303,6 +303,8 @@ struct CcFiltered {
 int launch_mesh_components(const KParams &P, int first_view, int n_views, float max_edge, const CcBuffers &b, void *stream);
 // behind launch_mesh_components over the same views: vertices of components of >= min_vertices vertices, and the faces among them
 int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream);
+// its first launch alone: f.keep (and the counts in f.s.cnt) of those views, nothing scanned, nothing emitted
+int launch_mesh_keep(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream);
 // smoothing of those meshes (sl3d_mesh_smooth.hip, sl3d_mesh_smooth.h).  cells / rings: [max_views][px_view_stride] a byte per cell
 // (cc_cell_code) / per pixel (smooth_ring); plane[2]: [max_views][px_view_stride][3] the ping-pong planes of the steps -- step s writes
 // plane[s & 1], and plane[smooth_steps & 1], the one the last step did not write, takes the compacted vertices (view v's at 3 * v *
@@ -317,6 +319,38 @@ struct SmoothBuffers {
 inline int smooth_steps(int iterations, float mu) { return iterations * (mu != 0.0f ? 2 : 1); }  // a step with mu == 0 is left out
 int launch_mesh_smooth(const KParams &P, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu, bool fix_boundary,
                        const SmoothBuffers &b, void *stream);
+// the level-of-detail mesh (sl3d_mesh_lod.hip, sl3d_mesh_lod.h): one vertex per step x step block of a view's pixels.  The coarse grid is
+// a dense result of its own -- valid / points planes of W' x H' pixels, rows a multiple of 16 apart -- so a KParams that carries it feeds
+// launch_compact_views, launch_mesh_views and launch_mesh_normals as they stand
+inline KParams lod_params(const KParams &P, int step, uint8_t *valid, float *points)
+{
+    KParams C = P;
+    C.W = (P.W + step - 1) / step, C.H = (P.H + step - 1) / step;
+    C.pitch = (C.W + 15) & ~15;
+    C.px_view_stride = (size_t)C.pitch * (size_t)C.H;
+    C.valid = valid, C.points = points;
+    return C;
+}
+// where the candidates of the fine views come from: cand [max_views][px_view_stride] 0/1 bytes; their ids in the view's compacted cloud
+// either from offsets -- the candidates are the valid pixels: the launch's slice of the scan launch_mesh_cells left, [view][mesh_chunks]
+// -- or, offsets == NULL, from vid [max_views][px_view_stride] (CcBuffers::vid)
+struct LodSource {
+    const uint8_t *cand;
+    const unsigned long long *offsets;
+    const int *vid;
+};
+// everything over the coarse grid Pc = lod_params(...): ids = the id plane beside Pc.valid / Pc.points; blk / chk / nrm: the scratch of
+// launch_compact_views / launch_mesh_views / launch_mesh_normals at Pc's sizes; xyz, normals [max_views][Pc.px_view_stride][3],
+// vertex_ids [max_views][Pc.px_view_stride], faces [max_views][face_stride][3]
+struct LodBuffers {
+    int *ids;
+    CompactScratch blk, chk, nrm;
+    float *xyz, *normals;
+    int *vertex_ids, *faces;
+    size_t face_stride;
+};
+int launch_mesh_lod(const KParams &P, const KParams &Pc, int first_view, int n_views, int step, float lod_edge, bool mean, const LodSource &src,
+                    const LodBuffers &b, bool normals, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

@@ -259,6 +259,17 @@ int launch_mesh_components(const KParams &P, int first_view, int n_views, float 
     return (int)hipGetLastError();
 }
 
+// behind launch_mesh_components over the same views: the keep bytes and their counts (all the level-of-detail call wants of the filter)
+int launch_mesh_keep(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream)
+{
+    const MeshLaunch L = mesh_launch(P, first_view, n_views);
+    const CompactScratch c = L.sliced(f.s, 2);
+    const size_t v0 = L.v0;
+    hipLaunchKernelGGL(k_cc_keep, L.grid, dim3(256), 0, (hipStream_t)stream, L.in.valid, (const uint8_t *)(b.cells + v0), P.W, P.H, P.pitch,
+                       P.px_view_stride, (const int *)(b.labels + v0), (const int *)(b.sizes + v0), min_vertices, f.keep + v0, c.cnt);
+    return (int)hipGetLastError();
+}
+
 // behind launch_mesh_components over the same views
 int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_vertices, const CcBuffers &b, const CcFiltered &f, void *stream)
 {
@@ -266,9 +277,8 @@ int launch_mesh_filter(const KParams &P, int first_view, int n_views, int min_ve
     const CompactScratch c = L.sliced(f.s, 2);
     const size_t v0 = L.v0;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_cc_keep, L.grid, dim3(256), 0, st, L.in.valid, (const uint8_t *)(b.cells + v0), P.W, P.H, P.pitch, P.px_view_stride,
-                       (const int *)(b.labels + v0), (const int *)(b.sizes + v0), min_vertices, f.keep + v0, c.cnt);
-    int rc = launch_compact_scan(c.cnt, c.off, L.n_chunks, 2 * n_views, c.tot, stream);
+    int rc = launch_mesh_keep(P, first_view, n_views, min_vertices, b, f, stream);
+    if (!rc) rc = launch_compact_scan(c.cnt, c.off, L.n_chunks, 2 * n_views, c.tot, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_cc_emit, L.grid, dim3(256), 0, st, (const uint8_t *)(f.keep + v0), (const uint8_t *)(b.cells + v0), L.in.points, (const int *)(b.vid + v0),
                        P.W, P.H, P.pitch, P.px_view_stride, (const unsigned *)c.cnt, (const unsigned long long *)c.off, f.xyz + 3 * v0, f.ids + v0,

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.11.0"
+#define SL3D_VERSION_STRING "0.12.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -531,6 +531,68 @@ int sl3d_mesh_smooth(sl3d_ctx *ctx, int first_view, int n_views, float max_edge,
  * xyz and in normals; xyz may be NULL; normals is looked at only with SL3D_SMOOTH_NORMALS (and may be NULL then) */
 int sl3d_get_mesh_smoothed(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int iterations, float lambda, float mu,
                            unsigned flags, float *xyz, float *normals, int64_t vertex_capacity, int64_t *n_vertices);
+
+/* ---- level-of-detail mesh of a view: one vertex per step x step pixel block (0.12.0) ----------------------------------------------
+ * The meshes above work at full pixel resolution: a 1080p view gives about 2 M vertices and 4 M faces.  The organized grid makes a
+ * lighter mesh cheap and exact: group the pixels into blocks, keep one vertex per block, mesh the coarse grid with the cell rules of
+ * sl3d_mesh_views.  Inputs: a view with a dense result, step in [1, 16], max_edge and min_vertices as for sl3d_mesh_views_filtered,
+ * lod_edge (mm, > 0, +inf allowed), flags.  Exact:
+ *   candidates      the pixels whose vertex is in the filtered mesh sl3d_mesh_views_filtered(first_view, n_views, max_edge, min_vertices)
+ *                   defines.  For min_vertices == 1 these are all valid pixels, whatever max_edge is (it must still be a valid argument).
+ *   blocks          the coarse grid has H' = ceil(H / step) rows and W' = ceil(W / step) columns; block (R, C) covers rows
+ *                   [R*step, min(R*step + step, H)) and columns [C*step, min(C*step + step, W)) of the WINDOW (blocks are anchored at the
+ *                   window's row 0 / column 0, not at the camera frame's).
+ *   representative  among a block's candidates (r, c) the one with the smallest integer
+ *                   d = (2(r - R*step) + 1 - step)^2 + (2(c - C*step) + 1 - step)^2 -- the distance to the centre of the FULL block, for
+ *                   blocks clipped by the window too; among equals the first in row-major scan order.  A block without a candidate
+ *                   gives an invalid coarse pixel.  At an even step the four centre pixels tie and the upper left one wins: a bias of
+ *                   half a pixel towards the window's origin, fixed and the same for every block.
+ *   position        without SL3D_LOD_MEAN the representative's float triple, copied bitwise.  With SL3D_LOD_MEAN the members of a block
+ *                   are the representative, always, and every other candidate q of the block with
+ *                   len2(q, rep) <= (double)lod_edge * (double)lod_edge (len2 of sl3d_mesh_views; a NaN len2 is not a member); k = their
+ *                   number.  k == 1: the representative's bits.  Otherwise, per component: s = +0, then s += (double)q over the members in
+ *                   row-major scan order of the block; m = s / (double)k; the position is (float)m.  Every operation is one IEEE double
+ *                   operation, nothing contracted; the cast rounds to nearest even.  A mean that never averages across a depth step
+ *                   wider than lod_edge.  (As for the smoothing: sign and payload of a NaN the arithmetic PRODUCES are not defined.)
+ *   vertices        the valid coarse pixels in row-major order of the coarse grid; the id of a vertex is its position in that order.
+ *   vertex_ids      vertex_ids[i] = the id of vertex i's representative in the view's compacted cloud, in the order of sl3d_get_cloud --
+ *                   the ORIGINAL id also for min_vertices > 1, exactly as for the filtered mesh.  Distinct, but not ascending: every id
+ *                   of a coarse row lies above those of the coarse row before it, while within a coarse row the representatives of
+ *                   neighbouring blocks may lie in different pixel rows.  Colours, normals and smoothed positions of the fine mesh
+ *                   follow by gather: rgb[vertex_ids], smoothed[vertex_ids].
+ *   faces           the definition of sl3d_mesh_views applied to the coarse grid -- the positions and the coarse valid map above -- with
+ *                   lod_edge for max_edge: at most 2(W'-1)(H'-1) faces per view.  The diagonal choice and the edge tests read the
+ *                   positions THIS call outputs.
+ *   normals         (SL3D_LOD_NORMALS) the definition of sl3d_mesh_normals applied to that coarse mesh.
+ *   identity        step == 1: vertices, faces and normals are those of sl3d_mesh_views(.., lod_edge) and sl3d_mesh_normals, bit for
+ *                   bit (every block has one pixel, d = 0, k = 1); with min_vertices == 1 as well vertex_ids is 0 .. n-1.
+ * The result is the same bit for bit whatever the batch, the launch shape or the run.  The launch sequence is fixed by the arguments
+ * alone (min_vertices == 1: the cell pass and its scan for the ids -- no component kernel; min_vertices > 1: the components' launches and
+ * the keep bytes of the filter, without its emit; then the block pass, the compaction and the mesh launches over the coarse grid, the
+ * ids, normals on request); nothing is read back but the counts.  The outputs live in buffers of their own, allocated on first use for
+ * the step asked and grown only when a later call needs more: points, valid, the clouds, the device mesh of sl3d_mesh_views, the normals,
+ * labels, filtered mesh and smoothed mesh earlier calls handed out are not modified and stay valid.  SL3D_E_INVALID_ARG, and nothing on
+ * the device changes, for: step outside [1, 16], a NaN or non-positive max_edge or lod_edge, min_vertices < 1, an unknown flag bit, a bad
+ * view range, NULL count pointers.  Not covered: groups, segments, the shim; components or smoothing of the coarse mesh itself. */
+#define SL3D_LOD_MEAN 1u
+#define SL3D_LOD_NORMALS 2u
+typedef struct sl3d_mesh_lod {        /* device-resident, valid until the next sl3d_mesh_views_lod / sl3d_get_meshes_lod */
+    const float *xyz;                 /* view first_view+k: n_vertices[k] triples at xyz + 3*k*view_stride_points */
+    const int32_t *faces;             /* n_faces[k] id triples at faces + 3*k*view_stride_faces */
+    const int32_t *vertex_ids;        /* n_vertices[k] original ids at vertex_ids + k*view_stride_points */
+    const float *normals;             /* layout of xyz; NULL without SL3D_LOD_NORMALS */
+    size_t view_stride_points, view_stride_faces;
+    int32_t grid_width, grid_height;  /* W', H' */
+} sl3d_mesh_lod;
+/* the level-of-detail meshes of views [first_view, first_view+n_views) on the device; device_mesh may be NULL */
+int sl3d_mesh_views_lod(sl3d_ctx *ctx, int first_view, int n_views, int step, float max_edge, int64_t min_vertices, float lod_edge,
+                        unsigned flags, sl3d_mesh_lod *device_mesh, int64_t *n_vertices, int64_t *n_faces);
+/* the same with a host copy under the capacity contract of sl3d_get_meshes: back to back, at most vertex_capacity entries in all in
+ * each of xyz, vertex_ids and normals, at most face_capacity triples in faces; any output pointer may be NULL (normals is looked at only
+ * with SL3D_LOD_NORMALS); the counts are always returned */
+int sl3d_get_meshes_lod(sl3d_ctx *ctx, int first_view, int n_views, int step, float max_edge, int64_t min_vertices, float lod_edge,
+                        unsigned flags, float *xyz, int32_t *vertex_ids, float *normals, int64_t vertex_capacity, int32_t *faces,
+                        int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces);
 
 /* register_point_clouds(unsigned, float tx, float ty, float tz, float rot_step)  9/register_point_clouds.cpp:23:
  * the compacted clouds of views [first_view, first_view+n_views) are rotated about the Y axis through (tx,ty,tz)

@@ -12,7 +12,11 @@ each against sl3d_mesh_views in alternating blocks in the same process, the rati
 each against sl3d_mesh_views in alternating blocks in the same process; the time per step is the difference to a run of 1 iteration
 (2 steps) over the 18 steps between them, so the cell, ring, scan and output launches and the read-back cancel; written to --out (default
 profiles/mesh_smooth_timing.json) as well as printed.
-usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components | --smooth [--out PATH]]"""
+--lod: the level-of-detail leg -- sl3d_mesh_views_lod at steps 2, 4 and 8 without and with SL3D_LOD_MEAN (min_vertices 1) and behind the
+filter (min_vertices = MIN_VERTICES), each against sl3d_mesh_views in alternating blocks in the same process, the ratio per case; one
+1080p view unless --only names another configuration; written to --out (default profiles/mesh_lod_timing.json) as well as
+printed.
+usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components | --smooth | --lod [--out PATH]]"""
 import argparse
 import importlib
 import json
@@ -36,6 +40,7 @@ CONFIGS = {"1080p_1": (1920, 1080, 1920, 1080, 1), "1080p_16": (1920, 1080, 1920
 N, FW = 10, 2
 MIN_VERTICES = 100
 SMOOTH = (10, 0.5, -0.53)  # iterations, lambda, mu of the smoothing leg
+LOD_STEPS = (2, 4, 8)      # of the level-of-detail leg
 
 
 def lasso(W, H, share=358580.0 / 1920000.0):
@@ -79,12 +84,22 @@ def main():
     ap.add_argument("--normals", action="store_true")
     ap.add_argument("--components", action="store_true")
     ap.add_argument("--smooth", action="store_true")
+    ap.add_argument("--lod", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "mesh_smooth_timing.json" if a.smooth else "mesh_components_timing.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "mesh_lod_timing.json" if a.lod else "mesh_smooth_timing.json" if a.smooth else "mesh_components_timing.json")
+    if a.lod and not a.only:
+        a.only = "1080p_1"
     syn = importlib.import_module("3dscan_amd.synth")
     scm = importlib.import_module("3dscan_amd.scanner")
-    if a.smooth:
+    if a.lod:
+        out = {"tool": "mesh_timing --lod", "reps": a.reps, "steps": list(LOD_STEPS), "min_vertices_of_the_filtered_case": MIN_VERTICES,
+               "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
+               "bytes_note": "block pass = 13 B per fine pixel read once (candidate byte + point) + 17 B per coarse pixel written; call, "
+                             "min_vertices 1 = cell pass 14 B/px (13 read, cell byte written) + block pass + the fine mesh's design bytes "
+                             "over the coarse grid (4 B per coarse pixel + 48 B per vertex + 12 B per vertex and face written) + 8 B per "
+                             "vertex (ids)", "runs": []}
+    elif a.smooth:
         out = {"tool": "mesh_timing --smooth", "reps": a.reps, "iterations": SMOOTH[0], "lambda": SMOOTH[1], "mu": SMOOTH[2],
                "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
                "bytes_note": "design, one step = 2 B/px (valid, ring) + 24 B per vertex (points read once, rows r-1 / r+1 counted as L2 hits, "
@@ -120,8 +135,30 @@ def main():
                 st = {}
                 np_mesh(np.ascontiguousarray(xyz[r0:r0 + 200]), np.ascontiguousarray(valid[r0:r0 + 200]), float("inf"), st)
                 med = float(np.float32(np.sqrt(np.median(st["len2"]))))
-                t_compact = 0.0 if a.normals or a.components or a.smooth else clock(lambda: sc.compact_views(0, V), a.reps)
+                t_compact = 0.0 if a.normals or a.components or a.smooth or a.lod else clock(lambda: sc.compact_views(0, V), a.reps)
                 for label, max_edge in (("inf", float("inf")), ("median", med)):
+                    if a.lod:
+                        _, nv, nf = sc.mesh_device(max_edge, 0, V)
+                        for step in LOD_STEPS:
+                            # the coarse grid's neighbours are `step` pixels apart: the fine bar scaled by the step (doubled: the diagonals)
+                            lod_edge = max_edge if label == "inf" else 2.0 * step * med
+                            m, cv, cf = sc.mesh_lod_device(step, lod_edge, 0, V)
+                            coarse = m.grid_width * m.grid_height * V
+                            block = 13 * W * H * V + 17 * coarse
+                            call = 14 * W * H * V + block + 4 * coarse + 68 * sum(cv) + 12 * sum(cf)
+                            run = {"config": name, "size": [W, H], "views": V, "selection": sel, "max_edge": label, "step": step,
+                                   "lod_edge_mm": None if label == "inf" else round(lod_edge, 6), "grid": [m.grid_width, m.grid_height],
+                                   "fine_vertices_per_view": round(sum(nv) / V), "fine_faces_per_view": round(sum(nf) / V),
+                                   "vertices_per_view": round(sum(cv) / V), "faces_per_view": round(sum(cf) / V),
+                                   "block_pass_model_bytes_per_view": block // V, "call_model_bytes_per_view": call // V}
+                            for tag, kw in (("plain", {}), ("mean", dict(mean=True)), ("mean_normals", dict(mean=True, normals=True)),
+                                            ("filtered", dict(max_edge=max_edge, min_vertices=MIN_VERTICES))):
+                                tl, tm = clock_alternating(lambda: sc.mesh_lod_device(step, lod_edge, 0, V, **kw), lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                                run.update({f"{tag}_us_per_call": round(tl * 1e6, 1), f"{tag}_mesh_us_per_call": round(tm * 1e6, 1),
+                                            f"{tag}_over_mesh": round(tl / tm, 3)})
+                            run["plain_call_model_tbs"] = round(call / (run["plain_us_per_call"] * 1e-6) / 1e12, 3)
+                            out["runs"].append(run)
+                        continue
                     if a.smooth:
                         it, lam, mu = SMOOTH
                         _, nv, nf = sc.mesh_device(max_edge, 0, V)
@@ -188,7 +225,7 @@ def main():
                         "design_bytes_per_view": design // V, "algorithmic_bytes_per_view": algorithmic // V,
                         "design_tbs": round(design / t / 1e12, 3), "design_over_achievable": round(design / t / 1e12 / ACHIEVABLE_TBS, 3),
                         "design_over_peak": round(design / t / 1e12 / PEAK_TBS, 3)})
-    if a.components or a.smooth:
+    if a.components or a.smooth or a.lod:
         with open(a.out, "w") as f:
             f.write(json.dumps(out) + "\n")
     print(json.dumps(out))
