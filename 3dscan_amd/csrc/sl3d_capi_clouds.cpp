@@ -1,7 +1,7 @@
 // sl3d_capi_clouds.cpp -- O1 / N2 / N3: ordered clouds straight from the fused kernel (segmented), their consumers (contiguous copy, host
 // downloads, registration), the compaction of a dense result with colour, turntable registration, the mesh over a dense result.
 // Device side: sl3d_clouds.hip (sl3d_mesh.hip for the faces and the cell pass, sl3d_mesh_normals.hip for the normals,
-// sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing, sl3d_mesh_lod.hip for the level-of-detail mesh).  Every consumer of a dense result keeps its
+// sl3d_mesh_components.hip for the components, sl3d_mesh_smooth.hip for the smoothing, sl3d_mesh_lod.hip for the level-of-detail mesh, sl3d_mesh_holes.hip for the hole filling).  Every consumer of a dense result keeps its
 // counts, their scan and the totals in a CompactScratch: ensure_scratch (sl3d_capi_internal.h) allocates one, ensure_plane a plane
 // beside it, read_totals brings its totals to the host.
 #include "sl3d_capi_internal.h"
@@ -936,6 +936,150 @@ try {
     ON_DEVICE(x);
     sl3d_mesh_lod m;
     rc = sl3d_mesh_views_lod(x, first_view, n_views, step, max_edge, min_vertices, lod_edge, flags, &m, n_vertices, n_faces);
+    if (rc) return rc;
+    rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc) rc = download_clamped(x, vertex_ids, m.vertex_ids, m.view_stride_points, n_views, n_vertices, vertex_capacity, 4);
+    if (!rc && m.normals) rc = download_clamped(x, normals, m.normals, m.view_stride_points, n_views, n_vertices, vertex_capacity);
+    if (!rc) rc = download_clamped(x, faces, m.faces, m.view_stride_faces, n_views, n_faces, face_capacity);
+    if (rc) return rc;
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// ---- the hole filling: small interior holes of a view's candidate map filled from their rims (include/sl3d.h: the definition;
+// sl3d_mesh_holes.h: its arithmetic and the union-find; sl3d_mesh_holes.hip: the kernels) ------------------------------------------------
+static int ensure_hole_buffers(sl3d_ctx *x, bool normals, bool fine_scan)
+{
+    const KParams &P = x->P;
+    const size_t mv = (size_t)x->cfg.max_views, px = mv * P.px_view_stride, chunks = mv * (size_t)mesh_chunks(P), blocks = mv * compact_blocks(P);
+    HoleBuffers &b = x->holes;
+    int rc = SL3D_OK;
+    if (!x->holes_ready) {
+        b.face_stride = mesh_face_stride(P);
+        rc = ensure_plane(x, &x->d_hole_valid, px);
+        if (!rc) rc = ensure_plane(x, &x->d_hole_points, 3 * px);
+        if (!rc) rc = ensure_plane(x, &b.labels, px);
+        if (!rc) rc = ensure_plane(x, &b.sizes, px);
+        if (!rc) rc = ensure_plane(x, &b.ids, px);
+        if (!rc) rc = ensure_plane(x, &x->d_hole_tot, 5 * mv);
+        if (!rc) rc = ensure_plane(x, &b.hol.cnt, 2 * chunks);
+        if (!rc) rc = ensure_plane(x, &b.hol.off, 2 * chunks);
+        if (!rc) rc = ensure_plane(x, &b.blk.cnt, blocks);
+        if (!rc) rc = ensure_plane(x, &b.blk.off, blocks);
+        if (!rc) rc = ensure_plane(x, &b.blk.tot, mv);
+        if (!rc) rc = ensure_plane(x, &b.chk.cnt, 2 * chunks);
+        if (!rc) rc = ensure_plane(x, &b.chk.off, 2 * chunks);
+        if (!rc) rc = ensure_plane(x, &b.xyz, 3 * px);
+        if (!rc) rc = ensure_plane(x, &b.vertex_ids, px);
+        if (!rc) rc = ensure_plane(x, &b.faces, 3 * mv * b.face_stride);
+        if (rc) return rc;
+        b.chk.tot = x->d_hole_tot, b.hol.tot = x->d_hole_tot + 2 * mv, b.failed = x->d_hole_tot + 4 * mv;
+        x->holes_ready = true;
+    }
+    if (normals && !x->holes_normals_ready) {
+        rc = ensure_plane(x, &b.normals, 3 * px);
+        if (!rc) rc = ensure_scratch(x, b.nrm, chunks, mv);
+        if (rc) return rc;
+        x->holes_normals_ready = true;
+    }
+    if (fine_scan && !x->holes_fine_ready) {
+        rc = ensure_plane(x, &x->d_hole_cells, px);
+        if (!rc) rc = ensure_scratch(x, x->hole_fine, chunks, mv);
+        if (rc) return rc;
+        x->holes_fine_ready = true;
+    }
+    return SL3D_OK;
+}
+
+static int check_hole_args(sl3d_ctx *x, int first_view, int n_views, float max_edge, int64_t min_vertices, int64_t max_hole, float fill_edge,
+                           unsigned flags, const int64_t *n_vertices, const int64_t *n_faces, const int64_t *n_holes, const int64_t *n_filled)
+{
+    const int rc = check_filter_args(x, first_view, n_views, max_edge, min_vertices, n_vertices, n_faces);
+    if (rc) return rc;
+    if (!n_holes || !n_filled) return fail(x, SL3D_E_INVALID_ARG, "null argument");
+    if (max_hole < 0) return fail(x, SL3D_E_INVALID_ARG, "max_hole must be >= 0 (0: nothing is filled)");
+    if (!(fill_edge > 0.0f)) return fail(x, SL3D_E_INVALID_ARG, "fill_edge must be > 0 (+inf: every span is usable)");  // (false for NaN)
+    if (flags & ~SL3D_FILL_NORMALS) return fail(x, SL3D_E_INVALID_ARG, "unknown hole-filling flag");
+    return SL3D_OK;
+}
+
+// min_vertices == 1: cells and scan (for the ids), the four hole kernels and the scan of their counts, the compaction's three and the
+// mesh's three launches over the filled grid, ids (+ the normals' three): 15 (18) launches.  min_vertices > 1: the components' four launches and the keep bytes in place
+// of the first two.  One read-back of the totals and the hole words (and, behind the components, one of their failure words)
+extern "C" int sl3d_mesh_fill_holes(sl3d_ctx *x, int first_view, int n_views, float max_edge, int64_t min_vertices, int64_t max_hole, float fill_edge,
+                                    unsigned flags, sl3d_mesh_holes *device_mesh, int64_t *n_vertices, int64_t *n_faces, int64_t *n_holes,
+                                    int64_t *n_filled)
+try {
+    int rc = check_hole_args(x, first_view, n_views, max_edge, min_vertices, max_hole, fill_edge, flags, n_vertices, n_faces, n_holes, n_filled);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    const KParams &P = x->P;
+    const bool normals = flags & SL3D_FILL_NORMALS, filtered = min_vertices > 1;
+    rc = ensure_hole_buffers(x, normals, !filtered);
+    if (!rc && filtered) rc = ensure_cc_buffers(x);
+    if (!rc && filtered) rc = ensure_ccf_buffers(x);
+    if (rc) return rc;
+    KParams F = P;
+    F.valid = x->d_hole_valid, F.points = x->d_hole_points;
+    LodSource src{};
+    if (filtered) {
+        CcBuffers b = x->cc;
+        b.labels_out = nullptr;
+        rc = launched(x, launch_mesh_components(P, first_view, n_views, max_edge, b, x->stream));
+        if (!rc) rc = launched(x, launch_mesh_keep(P, first_view, n_views, (int)std::min<int64_t>(min_vertices, INT32_MAX), b, x->ccf, x->stream));
+        src = LodSource{x->ccf.keep, nullptr, x->cc.vid};
+    } else {
+        const MeshLaunch L = mesh_launch(P, first_view, n_views);
+        const CompactScratch c = L.sliced(x->hole_fine, 1);
+        rc = launched(x, launch_mesh_cells(P, L, max_edge, x->d_hole_cells, nullptr, nullptr, nullptr, c, x->stream));
+        src = LodSource{P.valid, c.off, nullptr};
+    }
+    if (!rc)
+        rc = launched(x, launch_mesh_holes(P, F, first_view, n_views, max_edge, (int)std::min<int64_t>(max_hole, INT32_MAX), fill_edge, src, x->holes, normals,
+                                           x->stream));
+    if (rc) return rc;
+    const size_t mv = (size_t)x->cfg.max_views;
+    std::vector<unsigned long long> t(5 * mv);
+    HIPCHK(x, hipMemcpyAsync(t.data(), x->d_hole_tot, sizeof(unsigned long long) * t.size(), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    for (int k = 0; k < n_views; k++) {
+        const size_t v = (size_t)first_view + k;
+        if (t[4 * mv + v])
+            return fail(x, SL3D_E_INTERNAL, "hole filling: a walk of view " + std::to_string(v) + " ran out of its iteration bound");
+        n_vertices[k] = (int64_t)t[2 * v], n_faces[k] = (int64_t)t[2 * v + 1];
+        n_holes[k] = (int64_t)t[2 * mv + 2 * v], n_filled[k] = (int64_t)t[2 * mv + 2 * v + 1];
+    }
+    if (filtered) {
+        std::vector<unsigned long long> words;
+        CcTotals ct;
+        rc = read_cc_totals(x, first_view, n_views, words, ct);
+        if (rc) return rc;
+    }
+    if (device_mesh) {
+        const size_t v0 = (size_t)first_view * P.px_view_stride;
+        device_mesh->xyz = x->holes.xyz + 3 * v0;
+        device_mesh->faces = x->holes.faces + 3 * (size_t)first_view * x->holes.face_stride;
+        device_mesh->vertex_ids = x->holes.vertex_ids + v0;
+        device_mesh->normals = normals ? x->holes.normals + 3 * v0 : nullptr;
+        device_mesh->view_stride_points = P.px_view_stride;
+        device_mesh->view_stride_faces = x->holes.face_stride;
+    }
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// host copy: vertices, ids and normals of the views back to back, their faces back to back
+extern "C" int sl3d_get_meshes_holes_filled(sl3d_ctx *x, int first_view, int n_views, float max_edge, int64_t min_vertices, int64_t max_hole,
+                                            float fill_edge, unsigned flags, float *xyz, int32_t *vertex_ids, float *normals, int64_t vertex_capacity,
+                                            int32_t *faces, int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces, int64_t *n_holes,
+                                            int64_t *n_filled)
+try {
+    int rc = check_hole_args(x, first_view, n_views, max_edge, min_vertices, max_hole, fill_edge, flags, n_vertices, n_faces, n_holes, n_filled);
+    if (rc) return rc;
+    ON_DEVICE(x);
+    sl3d_mesh_holes m;
+    rc = sl3d_mesh_fill_holes(x, first_view, n_views, max_edge, min_vertices, max_hole, fill_edge, flags, &m, n_vertices, n_faces, n_holes, n_filled);
     if (rc) return rc;
     rc = download_clamped(x, xyz, m.xyz, m.view_stride_points, n_views, n_vertices, vertex_capacity);
     if (!rc) rc = download_clamped(x, vertex_ids, m.vertex_ids, m.view_stride_points, n_views, n_vertices, vertex_capacity, 4);

@@ -131,6 +131,17 @@ struct sl3d_ctx {
     uint8_t *d_lod_cells = nullptr;
     CompactScratch lod_fine{};
     size_t lod_cap[20] = {0};
+    // sl3d_mesh_fill_holes (all allocated on first use; the outputs share nothing with the calls above): the filled grid's valid / point
+    // planes and everything launched over them (HoleBuffers, sl3d_internal.h); hole_tot: the call's one read-back -- [max_views][2] the
+    // mesh totals (holes.chk.tot), [max_views][2] holes and filled pixels (holes.hol.tot), [max_views] holes.failed; for min_vertices == 1 the cell bytes and the chunk scratch of the
+    // cell pass that gives the ids
+    uint8_t *d_hole_valid = nullptr;
+    float *d_hole_points = nullptr;
+    HoleBuffers holes{};
+    unsigned long long *d_hole_tot = nullptr;
+    uint8_t *d_hole_cells = nullptr;
+    CompactScratch hole_fine{};
+    bool holes_ready = false, holes_normals_ready = false, holes_fine_ready = false;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -351,6 +351,25 @@ struct LodBuffers {
 };
 int launch_mesh_lod(const KParams &P, const KParams &Pc, int first_view, int n_views, int step, float lod_edge, bool mean, const LodSource &src,
                     const LodBuffers &b, bool normals, void *stream);
+// the ids of a grid's valid pixels in vertex order (k_lod_ids, sl3d_mesh_lod.hip): ids = the id plane beside Pc.valid, chk = the scratch
+// launch_mesh_views left over Pc, vertex_ids [max_views][Pc.px_view_stride]
+int launch_mesh_ids(const KParams &Pc, int first_view, int n_views, const CompactScratch &chk, const int *ids, int *vertex_ids, void *stream);
+// the hole filling (sl3d_mesh_holes.hip, sl3d_mesh_holes.h): the small interior holes of a view's candidate map filled from their rims.
+// The filled grid F -- P with valid / points planes of its own -- is a dense result, so it feeds launch_compact_views, launch_mesh_views
+// and launch_mesh_normals as they stand.  labels / sizes [max_views][px_view_stride]: the union-find over the non-candidate pixels and
+// the pixels of a component at its root; ids: the id plane beside F.valid / F.points; hol: cnt / off [max_views][2][mesh_chunks] (holes,
+// filled pixels per chunk), tot [max_views][2]; failed [max_views]: a word set when an iteration bound ran out; blk / chk / nrm, xyz,
+// normals, vertex_ids, faces: as LodBuffers', at P's sizes
+struct HoleBuffers {
+    int *labels, *sizes, *ids;
+    unsigned long long *failed;
+    CompactScratch hol, blk, chk, nrm;
+    float *xyz, *normals;
+    int *vertex_ids, *faces;
+    size_t face_stride;
+};
+int launch_mesh_holes(const KParams &P, const KParams &F, int first_view, int n_views, float max_edge, int max_hole, float fill_edge, const LodSource &src,
+                      const HoleBuffers &b, bool normals, void *stream);
 int launch_register(const float *in, float *out, long n, const float R4[4], float tx, float ty, float tz, void *stream);
 int launch_synth(const KParams &P, const DevCal &C, const SynthParams &S, int view, void *stream);
 int launch_undistort(const uint8_t *src, size_t sstride, uint8_t *dst, size_t dstride, int width, int height, int cn, const double K[9],

@@ -137,6 +137,15 @@ __global__ __launch_bounds__(256) void k_lod_ids(const uint8_t *__restrict__ val
     block_flush(out + (size_t)blockIdx.z * out_stride + offsets[chunk], s_ids, block_vertices);
 }
 
+int launch_mesh_ids(const KParams &Pc, int first_view, int n_views, const CompactScratch &chk, const int *ids, int *vertex_ids, void *stream)
+{
+    const MeshLaunch L = mesh_launch(Pc, first_view, n_views);
+    const CompactScratch c = L.sliced(chk, 2);
+    hipLaunchKernelGGL(k_lod_ids, L.grid, dim3(256), 0, (hipStream_t)stream, L.in.valid, ids + L.v0, Pc.W, Pc.H, Pc.pitch, Pc.px_view_stride,
+                       (const unsigned *)c.cnt, (const unsigned long long *)c.off, vertex_ids + L.v0, Pc.px_view_stride);
+    return (int)hipGetLastError();
+}
+
 int launch_mesh_lod(const KParams &P, const KParams &Pc, int first_view, int n_views, int step, float lod_edge, bool mean, const LodSource &src,
                     const LodBuffers &b, bool normals, void *stream)
 {
@@ -150,11 +159,7 @@ int launch_mesh_lod(const KParams &P, const KParams &Pc, int first_view, int n_v
     if (!rc) rc = launch_compact_views(Pc, first_view, n_views, b.blk, b.xyz + 3 * c0, nullptr, nullptr, stream);
     if (!rc) rc = launch_mesh_views(Pc, first_view, n_views, lod_edge, b.chk, b.faces, b.face_stride, stream);
     if (rc) return rc;
-    const MeshLaunch L = mesh_launch(Pc, first_view, n_views);
-    const CompactScratch c = L.sliced(b.chk, 2);
-    hipLaunchKernelGGL(k_lod_ids, L.grid, dim3(256), 0, st, L.in.valid, (const int *)(b.ids + c0), Pc.W, Pc.H, Pc.pitch, Pc.px_view_stride,
-                       (const unsigned *)c.cnt, (const unsigned long long *)c.off, b.vertex_ids + c0, Pc.px_view_stride);
-    rc = (int)hipGetLastError();
+    rc = launch_mesh_ids(Pc, first_view, n_views, b.chk, b.ids, b.vertex_ids, stream);
     if (!rc && normals) rc = launch_mesh_normals(Pc, first_view, n_views, lod_edge, b.nrm, b.normals, Pc.px_view_stride, stream);
     return rc;
 }

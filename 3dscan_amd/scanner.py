@@ -20,6 +20,7 @@ PATTERN_FRINGE, PATTERN_GRAY, PATTERN_INVERSE_GRAY, PATTERN_BINARY = 0, 1, 2, 3
 VALID_VERTICAL, VALID_HORIZONTAL, VALID_MERGED = 0, 1, 2
 SL3D_SMOOTH_FIX_BOUNDARY, SL3D_SMOOTH_NORMALS = 1, 2
 SL3D_LOD_MEAN, SL3D_LOD_NORMALS = 1, 2
+SL3D_FILL_NORMALS = 1
 
 # every symbol include/sl3d.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -29,7 +30,7 @@ ABI_SYMBOLS = (
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
-    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_mesh_components", "sl3d_get_mesh_components", "sl3d_mesh_views_filtered", "sl3d_get_meshes_filtered", "sl3d_mesh_smooth", "sl3d_get_mesh_smoothed", "sl3d_mesh_views_lod", "sl3d_get_meshes_lod", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
+    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_mesh_components", "sl3d_get_mesh_components", "sl3d_mesh_views_filtered", "sl3d_get_meshes_filtered", "sl3d_mesh_smooth", "sl3d_get_mesh_smoothed", "sl3d_mesh_views_lod", "sl3d_get_meshes_lod", "sl3d_mesh_fill_holes", "sl3d_get_meshes_holes_filled", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
     "sl3d_get_device_buffers", "sl3d_download", "sl3d_download_2d",
     "sl3d_group_create", "sl3d_group_destroy", "sl3d_group_last_error", "sl3d_group_size", "sl3d_group_stripe", "sl3d_group_transport",
     "sl3d_group_set_calibration", "sl3d_group_set_mask", "sl3d_group_set_frames", "sl3d_group_run", "sl3d_group_gather",
@@ -85,6 +86,13 @@ class MeshLod(C.Structure):
     sl3d_mesh_views_lod left in HBM, and the size of the coarse grid"""
     _fields_ = [("xyz", C.c_void_p), ("faces", C.c_void_p), ("vertex_ids", C.c_void_p), ("normals", C.c_void_p),
                 ("view_stride_points", C.c_size_t), ("view_stride_faces", C.c_size_t), ("grid_width", C.c_int32), ("grid_height", C.c_int32)]
+
+
+class MeshHoles(C.Structure):
+    """sl3d_mesh_holes: device addresses of the vertices, faces, original vertex ids (-1: filled) and (with SL3D_FILL_NORMALS, else
+    None) normals sl3d_mesh_fill_holes left in HBM"""
+    _fields_ = [("xyz", C.c_void_p), ("faces", C.c_void_p), ("vertex_ids", C.c_void_p), ("normals", C.c_void_p),
+                ("view_stride_points", C.c_size_t), ("view_stride_faces", C.c_size_t)]
 
 
 _lib = None
@@ -159,6 +167,13 @@ def load_library(path=None):
         L.sl3d_mesh_views_lod.argtypes = [vp, i, i, i, f, i64, f, u, C.POINTER(MeshLod), p64, p64]
         L.sl3d_get_meshes_lod.argtypes = [vp, i, i, i, f, i64, f, u, vp, vp, vp, i64, vp, i64, p64, p64]
     except AttributeError:   # a build before 0.12.0 under SL3D_LIB: everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        f, u, i64, p64 = C.c_float, C.c_uint, C.c_int64, C.POINTER(C.c_int64)
+        L.sl3d_mesh_fill_holes.argtypes = [vp, i, i, f, i64, i64, f, u, C.POINTER(MeshHoles), p64, p64, p64, p64]
+        L.sl3d_get_meshes_holes_filled.argtypes = [vp, i, i, f, i64, i64, f, u, vp, vp, vp, i64, vp, i64, p64, p64, p64, p64]
+    except AttributeError:   # a build before 0.13.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -793,6 +808,45 @@ class Scanner:
     def mesh_lod(self, step, lod_edge, view=0, max_edge=float("inf"), min_vertices=1, mean=False, normals=False):
         """(xyz, faces, vertex_ids) of one view, with normals=True (xyz, faces, vertex_ids, normals) (meshes_lod)."""
         return self.meshes_lod(step, lod_edge, view, 1, max_edge, min_vertices, mean, normals)[0]
+
+    @staticmethod
+    def _fill_args(max_edge, min_vertices, max_hole, fill_edge, normals):
+        return float(max_edge), int(min_vertices), int(max_hole), float(fill_edge), SL3D_FILL_NORMALS if normals else 0
+
+    def mesh_fill_holes_device(self, max_hole, fill_edge, first_view=0, n_views=1, max_edge=float("inf"), min_vertices=1, normals=False):
+        """sl3d_mesh_fill_holes: the hole-filled meshes of a batch of views left in HBM; returns (MeshHoles, vertex counts, face
+        counts, hole counts, filled-pixel counts)."""
+        m = MeshHoles()
+        nv, nf, nh, nfl = ((C.c_int64 * n_views)() for _ in range(4))
+        args = self._fill_args(max_edge, min_vertices, max_hole, fill_edge, normals)
+        self._chk(self.L.sl3d_mesh_fill_holes(self._h, first_view, n_views, *args, C.byref(m), nv, nf, nh, nfl), "sl3d_mesh_fill_holes")
+        return m, [int(c) for c in nv], [int(c) for c in nf], [int(c) for c in nh], [int(c) for c in nfl]
+
+    def meshes_fill_holes(self, max_hole, fill_edge, first_view=0, n_views=1, max_edge=float("inf"), min_vertices=1, normals=False, stats=False):
+        """The meshes of every view with their small interior holes filled: a list of (xyz float32 (n, 3), faces int32 (m, 3),
+        vertex_ids int32 (n,)), with normals=True of (xyz, faces, vertex_ids, normals); with stats=True every tuple ends in
+        (n_holes, n_filled).  A hole is a 4-connected component of at most max_hole non-candidate pixels that touches no border of the
+        window -- the candidates: the vertices of meshes_filtered(max_edge, min_vertices), all valid pixels for min_vertices = 1.  A hole
+        pixel is interpolated between the nearest candidates of its row and of its column; a span whose mean sample spacing exceeds
+        fill_edge is not used, so a depth step is not bridged.  vertex_ids[i] is the id the vertex has in cloud() / mesh(), -1 for a
+        filled vertex (include/sl3d.h: the exact definition)."""
+        nv, nf, nh, nfl = ((C.c_int64 * n_views)() for _ in range(4))
+        args = (self._h, first_view, n_views) + self._fill_args(max_edge, min_vertices, max_hole, fill_edge, normals)
+        self._chk(self.L.sl3d_get_meshes_holes_filled(*args, None, None, None, 0, None, 0, nv, nf, nh, nfl), "sl3d_get_meshes_holes_filled")
+        tv, tf = sum(nv), sum(nf)
+        xyz, ids, faces = np.empty((tv, 3), dtype=np.float32), np.empty(tv, dtype=np.int32), np.empty((tf, 3), dtype=np.int32)
+        nrm = np.empty((tv, 3), dtype=np.float32) if normals else None
+        self._chk(self.L.sl3d_get_meshes_holes_filled(*args, xyz.ctypes.data, ids.ctypes.data, nrm.ctypes.data if normals else None, tv,
+                                                      faces.ctypes.data, tf, nv, nf, nh, nfl), "sl3d_get_meshes_holes_filled")
+        out = [_cut(xyz, nv), _cut(faces, nf), _cut(ids, nv)] + ([_cut(nrm, nv)] if normals else [])
+        if stats:
+            out.append([(int(a), int(b)) for a, b in zip(nh, nfl)])
+        return list(zip(*out))
+
+    def mesh_fill_holes(self, max_hole, fill_edge, view=0, max_edge=float("inf"), min_vertices=1, normals=False, stats=False):
+        """(xyz, faces, vertex_ids) of one view, with normals=True (xyz, faces, vertex_ids, normals), with stats=True followed by
+        (n_holes, n_filled) (meshes_fill_holes)."""
+        return self.meshes_fill_holes(max_hole, fill_edge, view, 1, max_edge, min_vertices, normals, stats)[0]
 
     def set_texture(self, bgr, view=0):
         """The colour image save_point_cloud() takes r,g,b from: (H, W, 3) uint8, B,G,R order (cvLoadImage)."""

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.12.0"
+#define SL3D_VERSION_STRING "0.13.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -593,6 +593,72 @@ int sl3d_mesh_views_lod(sl3d_ctx *ctx, int first_view, int n_views, int step, fl
 int sl3d_get_meshes_lod(sl3d_ctx *ctx, int first_view, int n_views, int step, float max_edge, int64_t min_vertices, float lod_edge,
                         unsigned flags, float *xyz, int32_t *vertex_ids, float *normals, int64_t vertex_capacity, int32_t *faces,
                         int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces);
+
+/* ---- small holes of a view's mesh filled from their rims (0.13.0) -------------------------------------------------------------------
+ * A structured-light scan has dropouts -- specular pixels, pixels the modulation test rejects, the pixels of the fragments
+ * sl3d_mesh_views_filtered drops -- and the meshes above leave them open.  The organized grid makes closing the small ones cheap and
+ * exact.  Inputs: a view with a dense result (window W x H), max_edge and min_vertices as for sl3d_mesh_views_filtered, max_hole
+ * (pixels, >= 0), fill_edge (mm, > 0, +inf allowed), flags.  Exact:
+ *   candidates      as for the level-of-detail mesh: the valid pixels, or for min_vertices > 1 the pixels whose vertex
+ *                   sl3d_mesh_views_filtered(first_view, n_views, max_edge, min_vertices) keeps.
+ *   hole            a 4-connected component of non-candidate pixels of the window that contains no pixel of row 0, row H-1, column 0 or
+ *                   column W-1 and has at most max_hole pixels.  Two holes that touch only at a corner are two components, each judged
+ *                   by its own size.  n_holes counts the qualifying components.
+ *   rim             of a hole pixel (r, c): L, R, U, D, the nearest candidates to its left, right, above and below.  They exist: a
+ *                   walk along a line stays inside the component until it meets a candidate, and the component touches no border.
+ *                   dl = c - c_L, dr = c_R - c, du = r - r_U, dd = r_D - r, all >= 1.
+ *   usable          the row interpolant is usable iff len2(L, R) <= t * t with t = (double)fill_edge * (double)(dl + dr) (len2 of
+ *                   sl3d_mesh_views; a NaN len2 is not usable); the column interpolant likewise with U, D and du + dd.  The rule: the
+ *                   mean sample spacing along the span is at most fill_edge -- it keeps the fill from bridging a depth step or an
+ *                   outlier on the rim.
+ *   position        per component k, in double, every operation one IEEE operation in this order, nothing contracted:
+ *                     h = ((double)dr * L_k + (double)dl * R_k) / (double)(dl + dr)
+ *                     v = ((double)dd * U_k + (double)du * D_k) / (double)(du + dd)
+ *                   both usable: (float)(((double)(du + dd) * h + (double)(dl + dr) * v) / (double)((dl + dr) + (du + dd)));
+ *                   one usable: (float)h or (float)v; none: the pixel stays empty -- its hole counts in n_holes, the pixel not in
+ *                   n_filled.  The casts round to nearest even.  (Sign and payload of a NaN the arithmetic PRODUCES are not defined.)
+ *                   The rim consists of candidates only: a filled pixel never serves as the rim of another.
+ *   filled grid     points: candidates keep their bits, filled pixels carry the position above.  valid: candidates and filled pixels,
+ *                   and no other pixel -- for min_vertices > 1 that leaves out the valid pixels of dropped fragments, which a hole may
+ *                   swallow and overwrite.
+ *   vertices        the valid pixels of the filled grid in scan order; the id of a vertex is its position in that order.
+ *   vertex_ids      for a candidate its id in the view's compacted cloud, in the order of sl3d_get_cloud -- the ORIGINAL id also for
+ *                   min_vertices > 1, as for the filtered mesh; for a filled vertex -1.  Ascending apart from the -1s.
+ *   faces           the definition of sl3d_mesh_views applied to the filled grid with max_edge.
+ *   normals         (SL3D_FILL_NORMALS) the definition of sl3d_mesh_normals applied to that mesh.
+ *   identity        max_hole == 0 and min_vertices == 1: vertices, faces and normals are those of sl3d_mesh_views / sl3d_mesh_normals bit
+ *                   for bit, vertex_ids is 0 .. n-1.  For min_vertices > 1 and max_hole == 0 the result is the mesh of the CANDIDATE MAP:
+ *                   as for the level-of-detail mesh at step 1 this is not the filtered mesh -- two kept vertices that the filter
+ *                   separated only by dropping a fragment between them may share a face here if their edge is short.
+ * The result is the same bit for bit whatever the batch, the launch shape or the run.  The launch sequence is fixed by the arguments
+ * alone (candidates and ids as for the level-of-detail mesh; four launches that label the holes by a bounded lock-free union-find over
+ * the non-candidate pixels and fill them, and the scan of their counts; the compaction and the mesh launches over the filled grid, the
+ * ids, normals on request);
+ * nothing is read back but the counts and the failure words.  The outputs live in buffers of their own, allocated on first use: points,
+ * valid, the clouds, the device mesh of sl3d_mesh_views, the normals, labels, filtered, smoothed and level-of-detail meshes earlier calls
+ * handed out are not modified and stay valid.  SL3D_E_INVALID_ARG, and nothing on the device changes, for: a NaN or non-positive max_edge
+ * or fill_edge, max_hole < 0, min_vertices < 1, an unknown flag bit, a bad view range, NULL count pointers.  Not covered: groups,
+ * segments, the shim; components, smoothing or level of detail of the filled mesh; colours of filled vertices. */
+#define SL3D_FILL_NORMALS 1u
+typedef struct sl3d_mesh_holes {      /* device-resident, valid until the next sl3d_mesh_fill_holes / sl3d_get_meshes_holes_filled */
+    const float *xyz;                 /* view first_view+k: n_vertices[k] triples at xyz + 3*k*view_stride_points */
+    const int32_t *faces;             /* n_faces[k] id triples at faces + 3*k*view_stride_faces */
+    const int32_t *vertex_ids;        /* n_vertices[k] original ids (-1: filled) at vertex_ids + k*view_stride_points */
+    const float *normals;             /* layout of xyz; NULL without SL3D_FILL_NORMALS */
+    size_t view_stride_points, view_stride_faces;
+} sl3d_mesh_holes;
+/* the hole-filled meshes of views [first_view, first_view+n_views) on the device; device_mesh may be NULL.  n_holes[k]: the qualifying
+ * holes of view first_view+k, n_filled[k]: the pixels filled */
+int sl3d_mesh_fill_holes(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int64_t min_vertices, int64_t max_hole,
+                         float fill_edge, unsigned flags, sl3d_mesh_holes *device_mesh, int64_t *n_vertices, int64_t *n_faces,
+                         int64_t *n_holes, int64_t *n_filled);
+/* the same with a host copy under the capacity contract of sl3d_get_meshes_lod: back to back, at most vertex_capacity entries in all in
+ * each of xyz, vertex_ids and normals, at most face_capacity triples in faces; any output pointer may be NULL (normals is looked at only
+ * with SL3D_FILL_NORMALS); the counts are always returned */
+int sl3d_get_meshes_holes_filled(sl3d_ctx *ctx, int first_view, int n_views, float max_edge, int64_t min_vertices, int64_t max_hole,
+                                 float fill_edge, unsigned flags, float *xyz, int32_t *vertex_ids, float *normals,
+                                 int64_t vertex_capacity, int32_t *faces, int64_t face_capacity, int64_t *n_vertices, int64_t *n_faces,
+                                 int64_t *n_holes, int64_t *n_filled);
 
 /* register_point_clouds(unsigned, float tx, float ty, float tz, float rot_step)  9/register_point_clouds.cpp:23:
  * the compacted clouds of views [first_view, first_view+n_views) are rotated about the Y axis through (tx,ty,tz)

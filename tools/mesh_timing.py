@@ -16,7 +16,11 @@ profiles/mesh_smooth_timing.json) as well as printed.
 filter (min_vertices = MIN_VERTICES), each against sl3d_mesh_views in alternating blocks in the same process, the ratio per case; one
 1080p view unless --only names another configuration; written to --out (default profiles/mesh_lod_timing.json) as well as
 printed.
-usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components | --smooth | --lod [--out PATH]]"""
+--fill: the hole-filling leg -- sl3d_mesh_fill_holes at max_hole 16 and 256, min_vertices 1 and MIN_VERTICES, on one and on 16 views of 1080p,
+the default mask and the 19 % lasso each with a seeded 1 % of their pixels knocked out, max_edge 4 and fill_edge 2 median edge lengths, each
+against sl3d_mesh_views in alternating blocks in the same process, the ratio per case; written to --out (default
+profiles/mesh_fill_timing.json) as well as printed.
+usage: mesh_timing.py [--reps N] [--only 1080p_1|1080p_16|12mp_3] [--normals | --components | --smooth | --lod | --fill [--out PATH]]"""
 import argparse
 import importlib
 import json
@@ -41,6 +45,8 @@ N, FW = 10, 2
 MIN_VERTICES = 100
 SMOOTH = (10, 0.5, -0.53)  # iterations, lambda, mu of the smoothing leg
 LOD_STEPS = (2, 4, 8)      # of the level-of-detail leg
+FILL_MAX_HOLES = (16, 256)  # of the hole-filling leg
+FILL_KNOCKED_OUT = 0.01
 
 
 def lasso(W, H, share=358580.0 / 1920000.0):
@@ -85,14 +91,21 @@ def main():
     ap.add_argument("--components", action="store_true")
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--lod", action="store_true")
+    ap.add_argument("--fill", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "mesh_lod_timing.json" if a.lod else "mesh_smooth_timing.json" if a.smooth else "mesh_components_timing.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "mesh_fill_timing.json" if a.fill else "mesh_lod_timing.json" if a.lod else "mesh_smooth_timing.json" if a.smooth else "mesh_components_timing.json")
     if a.lod and not a.only:
         a.only = "1080p_1"
     syn = importlib.import_module("3dscan_amd.synth")
     scm = importlib.import_module("3dscan_amd.scanner")
-    if a.lod:
+    if a.fill:
+        out = {"tool": "mesh_timing --fill", "reps": a.reps, "max_holes": list(FILL_MAX_HOLES), "min_vertices_of_the_filtered_case": MIN_VERTICES,
+               "knocked_out_share": FILL_KNOCKED_OUT, "max_edge": "4 median edges", "fill_edge": "2 median edges",
+               "bytes_note": "hole kernels = init 1 B/px read + 8 written, union 2 B/px, flatten 1 B/px + 8 per non-candidate, fill 13 B per "
+                             "candidate read + 17 B/px written + 5 B per non-candidate: about 32 B/px; the call adds the cell pass (14 B/px) "
+                             "and the mesh's design bytes over the filled grid", "runs": []}
+    elif a.lod:
         out = {"tool": "mesh_timing --lod", "reps": a.reps, "steps": list(LOD_STEPS), "min_vertices_of_the_filtered_case": MIN_VERTICES,
                "achievable_tbs": ACHIEVABLE_TBS, "peak_tbs": PEAK_TBS,
                "bytes_note": "block pass = 13 B per fine pixel read once (candidate byte + point) + 17 B per coarse pixel written; call, "
@@ -120,11 +133,13 @@ def main():
                              "points 12 B per vertex 3x (scatter, count, emit) + 12 B per vertex and per face written; algorithmic = 13 B/px read once "
                              "+ 12 B per vertex and per face written", "runs": []}
     for name, (W, H, PW, PH, V) in CONFIGS.items():
-        if a.only and a.only != name:
+        if (a.only and a.only != name) or (a.fill and not a.only and name == "12mp_3"):
             continue
         with scm.Scanner(W, H, PW, PH, N, N, FW, FW, max_views=V) as sc:
             sc.set_calibration(*syn.cal_tuple(syn.synth_rig(W, H, PW, PH)))
             for sel, mask in (("default", syn.default_mask(W, H)), ("lasso_19pct", lasso(W, H))):
+                if a.fill:
+                    mask = mask & (np.random.default_rng(11).random((H, W)) >= FILL_KNOCKED_OUT).astype(np.uint8)
                 for v in range(V):
                     sc.set_mask(mask, view=v)
                     sc.synth_view(v, plane=(0.75 * (v % 16), 0.05, 0.05 - 0.003 * (v % 16)), view_id=v, noise=2)
@@ -135,6 +150,23 @@ def main():
                 st = {}
                 np_mesh(np.ascontiguousarray(xyz[r0:r0 + 200]), np.ascontiguousarray(valid[r0:r0 + 200]), float("inf"), st)
                 med = float(np.float32(np.sqrt(np.median(st["len2"]))))
+                if a.fill:
+                    max_edge, fill_edge = 4.0 * med, 2.0 * med
+                    _, nv, nf = sc.mesh_device(max_edge, 0, V)
+                    for max_hole in FILL_MAX_HOLES:
+                        for min_vertices in (1, MIN_VERTICES):
+                            kw = dict(max_edge=max_edge, min_vertices=min_vertices)
+                            _, fv, ff, nh, nfl = sc.mesh_fill_holes_device(max_hole, fill_edge, 0, V, **kw)
+                            tf, tm = clock_alternating(lambda: sc.mesh_fill_holes_device(max_hole, fill_edge, 0, V, **kw),
+                                                       lambda: sc.mesh_device(max_edge, 0, V), a.reps)
+                            out["runs"].append({"config": name, "size": [W, H], "views": V, "selection": sel, "max_edge_mm": round(max_edge, 6),
+                                                "fill_edge_mm": round(fill_edge, 6), "max_hole": max_hole, "min_vertices": min_vertices,
+                                                "mesh_vertices_per_view": round(sum(nv) / V), "mesh_faces_per_view": round(sum(nf) / V),
+                                                "vertices_per_view": round(sum(fv) / V), "faces_per_view": round(sum(ff) / V),
+                                                "holes_per_view": round(sum(nh) / V), "filled_per_view": round(sum(nfl) / V),
+                                                "us_per_call": round(tf * 1e6, 1), "mesh_us_per_call": round(tm * 1e6, 1),
+                                                "over_mesh": round(tf / tm, 3)})
+                    continue
                 t_compact = 0.0 if a.normals or a.components or a.smooth or a.lod else clock(lambda: sc.compact_views(0, V), a.reps)
                 for label, max_edge in (("inf", float("inf")), ("median", med)):
                     if a.lod:
@@ -225,7 +257,7 @@ def main():
                         "design_bytes_per_view": design // V, "algorithmic_bytes_per_view": algorithmic // V,
                         "design_tbs": round(design / t / 1e12, 3), "design_over_achievable": round(design / t / 1e12 / ACHIEVABLE_TBS, 3),
                         "design_over_peak": round(design / t / 1e12 / PEAK_TBS, 3)})
-    if a.components or a.smooth or a.lod:
+    if a.components or a.smooth or a.lod or a.fill:
         with open(a.out, "w") as f:
             f.write(json.dumps(out) + "\n")
     print(json.dumps(out))
