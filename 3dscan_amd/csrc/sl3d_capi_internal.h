@@ -4,6 +4,7 @@
 //   sl3d_capi_run.cpp      the per-stage entry points, every fused launch (run_fused), getters, the host-buffer pipeline
 //   sl3d_capi_clouds.cpp   O1 / N2 / N3: ordered clouds, their consumers, colour, registration
 //   sl3d_capi_next.cpp     N1 / N4: patterns, synthetic captures, cvUndistort2, plain device copies
+//   sl3d_capi_period.cpp   the period repair between stage 4 and stage 5 (sl3d_repair_periods)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -142,6 +142,11 @@ struct sl3d_ctx {
     uint8_t *d_hole_cells = nullptr;
     CompactScratch hole_fine{};
     bool holes_ready = false, holes_normals_ready = false, holes_fine_ready = false;
+    // sl3d_repair_periods (allocated on first use): the jump plane of one view, the wide plane beside it for an axis of 8 or more Gray
+    // planes, and [max_views][2][2] words: repaired and unrepairable pixels of the last pass over a view's axis
+    int8_t *d_period_jump = nullptr;
+    int *d_period_wide = nullptr;
+    unsigned *d_period_counts = nullptr;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

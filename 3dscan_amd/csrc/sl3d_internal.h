@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -208,6 +208,15 @@ int launch_cam_table(const KParams &P, const DevCal *d_cal, int kind, double *ou
 int launch_wrap(const KParams &P, int view, int axis, void *stream);
 int launch_unwrap(const KParams &P, int view, int axis, void *stream);
 int launch_corr(const KParams &P, int view, void *stream);
+// the period repair of one axis of one view (sl3d_period.hip, sl3d_period.h): jump [px_view_stride] bytes and, for an axis of 8 or more
+// Gray planes (else NULL), wide [px_view_stride] ints -- scratch the two launches hand j over in; counts: the two words the launch ADDS
+// the repaired and the unrepairable pixels to
+struct PeriodPlanes {
+    int8_t *jump;
+    int *wide;
+    unsigned *counts;
+};
+int launch_period_repair(const KParams &P, int view, int axis, int radius, const PeriodPlanes &b, void *stream);
 int launch_tri(const KParams &P, const DevCal &C, int view, void *stream);
 // counts per block (or chunk) of a launch's views, their exclusive scan (k_compact_scan) and the views' totals: the scratch of every
 // consumer of a dense result.  Compaction (O1 / N2): cnt / off hold one slot per view OF A LAUNCH (slot k: view first_view + k), a slot =

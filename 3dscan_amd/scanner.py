@@ -26,7 +26,7 @@ SL3D_FILL_NORMALS = 1
 ABI_SYMBOLS = (
     "sl3d_version", "sl3d_strerror", "sl3d_last_error", "sl3d_create", "sl3d_destroy",
     "sl3d_set_calibration", "sl3d_get_projection_matrices", "sl3d_set_mask", "sl3d_set_masks", "sl3d_set_masks_modulated", "sl3d_get_modulation", "sl3d_set_mask_colrow", "sl3d_set_frames_range", "sl3d_get_global_colrow", "sl3d_set_frames", "sl3d_copy_view", "sl3d_synth_view", "sl3d_get_frames",
-    "sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_compute_c_p_map", "sl3d_triangulate",
+    "sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_compute_c_p_map", "sl3d_triangulate", "sl3d_repair_periods",
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
@@ -174,6 +174,11 @@ def load_library(path=None):
         L.sl3d_mesh_fill_holes.argtypes = [vp, i, i, f, i64, i64, f, u, C.POINTER(MeshHoles), p64, p64, p64, p64]
         L.sl3d_get_meshes_holes_filled.argtypes = [vp, i, i, f, i64, i64, f, u, vp, vp, vp, i64, vp, i64, p64, p64, p64, p64]
     except AttributeError:   # a build before 0.13.0 under SL3D_LIB: everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        L.sl3d_repair_periods.argtypes = [vp, i, i, i, C.POINTER(C.c_uint32)]
+    except AttributeError:   # a build before 0.14.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -441,6 +446,17 @@ class Scanner:
 
     def unwrap_phase(self, pattern_type, view=0):
         self._chk(self.L.sl3d_unwrap_phase(self._h, view, pattern_type), "sl3d_unwrap_phase")
+
+    def repair_periods(self, axis, radius=4, view=0, want_counts=True):
+        """sl3d_repair_periods between unwrap_phase and compute_c_p_map: whole 2*Pi periods taken out of the absolute phase of one axis
+        against the lower median of the samples within `radius` pixels along the coded direction; (repaired, unrepairable) pixels of the pass.
+        want_counts=False: the call stays asynchronous and returns None."""
+        if not want_counts:
+            self._chk(self.L.sl3d_repair_periods(self._h, view, axis, radius, None), "sl3d_repair_periods")
+            return None
+        counts = (C.c_uint32 * 2)()
+        self._chk(self.L.sl3d_repair_periods(self._h, view, axis, radius, counts), "sl3d_repair_periods")
+        return int(counts[0]), int(counts[1])
 
     def compute_c_p_map(self, view=0):
         self._chk(self.L.sl3d_compute_c_p_map(self._h, view), "sl3d_compute_c_p_map")

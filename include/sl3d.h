@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.13.0"
+#define SL3D_VERSION_STRING "0.14.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -241,6 +241,31 @@ int sl3d_unwrap_phase(sl3d_ctx *ctx, int view, int axis);
 int sl3d_compute_c_p_map(sl3d_ctx *ctx, int view);
 /* void triangulate()                             7/triangulation.cpp:1444  */
 int sl3d_triangulate(sl3d_ctx *ctx, int view);
+
+/* ---- 2*Pi period jumps of the absolute phase repaired (0.14.0; needs SL3D_FLAG_KEEP_STAGES) ----------------------------------------
+ * The absolute phase is wrapped + Pi + 2*Pi*code (4/phase_unwrap.cpp:278-316), which is right only where the Gray-code period boundary
+ * and the wrap of the fringe phase fall on the same camera pixel.  Defocus and the >= 0 tie rule of the Gray decode move the code edge by
+ * a pixel or a few on a real rig: in that band the code is off by one, the correspondence by exactly fringe_width projector pixels.
+ * This call takes whole periods out of one axis of one view, between stage 4 and stage 5, with no extra pattern.
+ *   A SAMPLE of the axis is a pixel whose axis valid byte is 1 and that lies where stage 4 defines the absolute phase: window columns
+ *   1..width-2 for the vertical axis, window rows 1..height-2 for the horizontal one.  The neighbourhood of a pixel is the 2*radius + 1
+ *   pixels along the direction the axis encodes (the row for the vertical axis, the column for the horizontal one), the pixel included,
+ *   clipped to the context's window.  For every sample p, from the planes as they were when the call was enqueued (every pixel decides
+ *   from the same state, not from its neighbours' repairs):
+ *     1. S = the absolute phases of the samples of its neighbourhood, n = |S|;  n < radius + 1: p is left as it is
+ *     2. m = the lower median of S (element (n - 1) / 2 of S sorted ascending)
+ *     3. j = (long)rint(((double)unwrapped_p - (double)m) / ((2.0 * 22.0) / 7.0)), half to even;  j == 0: p is left as it is
+ *     4. k = code_p - j;  k < 0 or k >= 2^n_gray: p is left as it is and counted as unrepairable
+ *     5. code_p = k, unwrapped_p = (float)((double)wrapped_p + (((double)k * 2.0) * 22.0) / 7.0) (stage 4's expression), counted as repaired
+ *   The wrapped phase, the valid maps and the stage-4 debug image are not touched.  An integer correction and one recomputation by the
+ *   reference's own formula: bit-for-bit reproducible.  A second call is a second pass over the result of the first.
+ * Call order: sl3d_compute_wrapped_phase and sl3d_unwrap_phase of both axes, sl3d_repair_periods per axis, sl3d_compute_c_p_map,
+ * sl3d_triangulate -- everything downstream (sl3d_get_points, the clouds, the meshes) then sees the repaired scan.  After sl3d_run on a
+ * KEEP_STAGES context the same planes exist, so sl3d_repair_periods + sl3d_compute_c_p_map + sl3d_triangulate works there too.
+ * counts[0] = repaired, counts[1] = unrepairable pixels of this pass; counts may be NULL (then the call stays asynchronous), otherwise the
+ * call synchronises.  SL3D_E_INVALID_ARG for a bad view, an axis outside {0, 1} or a radius outside 1..8; SL3D_E_STATE without
+ * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes.  A refused call changes nothing. */
+int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t counts[2]);
 
 /* ---- the fused hot path ------------------------------------------------------------------- */
 /* Stages 3(v) 3(h) 4(v) 4(h) 5 7 in main()'s order (m_tech_project_console.cpp:372-395) plus the
