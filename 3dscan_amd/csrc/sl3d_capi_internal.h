@@ -5,6 +5,7 @@
 //   sl3d_capi_clouds.cpp   O1 / N2 / N3: ordered clouds, their consumers, colour, registration
 //   sl3d_capi_next.cpp     N1 / N4: patterns, synthetic captures, cvUndistort2, plain device copies
 //   sl3d_capi_period.cpp   the period repair between stage 4 and stage 5 (sl3d_repair_periods)
+//   sl3d_capi_subpixel.cpp stage 7 from the continuous correspondences, its residual plane (sl3d_triangulate_subpixel and its getters)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,6 +98,20 @@ SL3D_INTERNAL int sync_for_caller(sl3d_ctx *x);
         const int rc_ = sync_for_caller(x);    \
         if (rc_) return rc_;                   \
     } while (0)
+
+// the window of one view's plane (`comps` elements per pixel, rows P.pitch pixels apart, at src) into the caller's rows (out: not
+// NULL), then the wait
+template <typename T>
+inline int download_plane(sl3d_ctx *x, const T *src, int comps, T *out, size_t out_stride_elems)
+{
+    const KParams &P = x->P;
+    if (out_stride_elems < (size_t)P.W * comps) return fail(x, SL3D_E_INVALID_ARG, "output stride too small");
+    ON_DEVICE(x);
+    HIPCHK(x, hipMemcpy2DAsync(out, out_stride_elems * sizeof(T), src, (size_t)P.pitch * comps * sizeof(T), (size_t)P.W * comps * sizeof(T),
+                               P.H, hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
 
 // every fused launch of the library (sl3d_capi_run.cpp)
 SL3D_INTERNAL bool maskin_launch(const sl3d_ctx *x, int first_view, int n_views, bool keep);

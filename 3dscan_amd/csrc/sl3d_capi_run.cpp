@@ -300,14 +300,7 @@ static int get_plane(sl3d_ctx *x, int view, const T *dev_base, int comps, T *out
     if (rc) return rc;
     if (!out) return fail(x, SL3D_E_INVALID_ARG, "null output");
     if (!dev_base) return fail(x, SL3D_E_STATE, "plane not available (SL3D_FLAG_KEEP_STAGES not set?)");
-    const KParams &P = x->P;
-    if (out_stride_elems < (size_t)P.W * comps) return fail(x, SL3D_E_INVALID_ARG, "output stride too small");
-    ON_DEVICE(x);
-    const T *src = dev_base + (size_t)view * P.px_view_stride * comps;
-    HIPCHK(x, hipMemcpy2DAsync(out, out_stride_elems * sizeof(T), src, (size_t)P.pitch * comps * sizeof(T), (size_t)P.W * comps * sizeof(T),
-                               P.H, hipMemcpyDeviceToHost, x->stream));
-    SYNC_FOR_CALLER(x);
-    return SL3D_OK;
+    return download_plane(x, dev_base + (size_t)view * x->P.px_view_stride * comps, comps, out, out_stride_elems);
 }
 
 extern "C" int sl3d_get_valid_map(sl3d_ctx *x, int view, int which, uint8_t *out, size_t stride)

@@ -147,6 +147,12 @@ struct sl3d_ctx {
     int8_t *d_period_jump = nullptr;
     int *d_period_wide = nullptr;
     unsigned *d_period_counts = nullptr;
+    // sl3d_triangulate_subpixel (allocated on first use): the residual plane [max_views][px_view_stride]; for a caller that wants the
+    // counts a word per block of the launch and [max_views][2] words, the triangulated and the rejected pixels of the call's views;
+    // sl3d_get_correspondences_subpixel: (xs, ys) of one view
+    float *d_residual = nullptr;
+    unsigned *d_subpixel_partials = nullptr, *d_subpixel_counts = nullptr;
+    double *d_subpixel_xy = nullptr;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

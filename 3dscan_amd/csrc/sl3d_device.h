@@ -235,12 +235,19 @@ __device__ __forceinline__ float unwrap_value(float wrapped_shifted, int code)
     return (float)((double)wrapped_shifted + k);
 }
 
+// fw*(phi/(2.0*Pi)): the double stage 5 hands to lrint   5/compute_correspondance.cpp:648,659 -- the continuous projector coordinate
+// (sl3d_subpixel.hip triangulates from it as it is)
+__device__ __forceinline__ double correspond_arg(float unwrapped, int fw)
+{
+    const double c = 2.0 * PI_REF;  // (2.0*Pi) -> (2.0*22.0)/7.0, folded at compile time exactly as on the host
+    return (double)fw * div_exact((double)unwrapped, c, 1.0 / c);
+}
+
 // lrint(fw*(phi/(2.0*Pi))) with the FE_INVALID and range rejections   5/compute_correspondance.cpp:648-675
 // returns true if the coordinate is accepted.  phi is 0 (unset) or a positive finite absolute phase.
 __device__ __forceinline__ bool correspond(float unwrapped, int fw, int limit, long &out, double &out_d)
 {
-    const double c = 2.0 * PI_REF;  // (2.0*Pi) -> (2.0*22.0)/7.0, folded at compile time exactly as on the host
-    const double a = (double)fw * div_exact((double)unwrapped, c, 1.0 / c);
+    const double a = correspond_arg(unwrapped, fw);
     const double r = rint(a);  // round-half-even, the default rounding mode lrint runs under
     // FE_INVALID <=> NaN, inf or outside long; those and out-of-range values both clear the pixel.  The range test is made on
     // the double itself (NaN compares false), so no out-of-range value is ever converted to an integer.

@@ -26,7 +26,7 @@ SL3D_FILL_NORMALS = 1
 ABI_SYMBOLS = (
     "sl3d_version", "sl3d_strerror", "sl3d_last_error", "sl3d_create", "sl3d_destroy",
     "sl3d_set_calibration", "sl3d_get_projection_matrices", "sl3d_set_mask", "sl3d_set_masks", "sl3d_set_masks_modulated", "sl3d_get_modulation", "sl3d_set_mask_colrow", "sl3d_set_frames_range", "sl3d_get_global_colrow", "sl3d_set_frames", "sl3d_copy_view", "sl3d_synth_view", "sl3d_get_frames",
-    "sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_compute_c_p_map", "sl3d_triangulate", "sl3d_repair_periods",
+    "sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_compute_c_p_map", "sl3d_triangulate", "sl3d_repair_periods", "sl3d_triangulate_subpixel", "sl3d_get_residuals", "sl3d_get_correspondences_subpixel",
     "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
     "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
     "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
@@ -179,6 +179,13 @@ def load_library(path=None):
     try:
         L.sl3d_repair_periods.argtypes = [vp, i, i, i, C.POINTER(C.c_uint32)]
     except AttributeError:   # a build before 0.14.0 under SL3D_LIB: everything else still loads
+        if not os.environ.get("SL3D_LIB"):
+            raise
+    try:
+        L.sl3d_triangulate_subpixel.argtypes = [vp, i, i, C.c_double, C.POINTER(C.c_uint32)]
+        L.sl3d_get_residuals.argtypes = [vp, i, vp, C.c_size_t]
+        L.sl3d_get_correspondences_subpixel.argtypes = [vp, i, vp, C.c_size_t]
+    except AttributeError:   # a build before 0.15.0 under SL3D_LIB: everything else still loads
         if not os.environ.get("SL3D_LIB"):
             raise
     L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
@@ -464,6 +471,18 @@ class Scanner:
     def triangulate(self, view=0):
         self._chk(self.L.sl3d_triangulate(self._h, view), "sl3d_triangulate")
 
+    def triangulate_subpixel(self, first_view=0, n_views=1, max_residual=float("inf"), want_counts=True):
+        """sl3d_triangulate_subpixel in place of triangulate, after compute_c_p_map: stage 7 from the continuous projector coordinates
+        (the doubles stage 5 rounds) for a batch of views in one launch, the reprojection residual of every solve kept as a plane
+        (residuals); a finite max_residual rejects the pixels whose stored residual is not <= it.  Returns a list of
+        (triangulated, rejected) per view; want_counts=False: the call stays asynchronous and returns None."""
+        if not want_counts:
+            self._chk(self.L.sl3d_triangulate_subpixel(self._h, first_view, n_views, float(max_residual), None), "sl3d_triangulate_subpixel")
+            return None
+        counts = (C.c_uint32 * (2 * max(n_views, 1)))()
+        self._chk(self.L.sl3d_triangulate_subpixel(self._h, first_view, n_views, float(max_residual), counts), "sl3d_triangulate_subpixel")
+        return [(int(counts[2 * k]), int(counts[2 * k + 1])) for k in range(n_views)]
+
     def run_stages(self, view=0):
         """main()'s order (m_tech_project_console.cpp:372-395) through the per-stage kernels."""
         self.compute_wrapped_phase(0, view); self.compute_wrapped_phase(1, view)
@@ -623,6 +642,17 @@ class Scanner:
     def intersection_points(self, view=0):
         out = np.empty((self.H, self.W, 3), dtype=np.float64)
         self._chk(self.L.sl3d_get_intersection_points(self._h, view, out.ctypes.data), "sl3d_get_intersection_points")
+        return out
+
+    def residuals(self, view=0):
+        """The reprojection residual (undistorted pixels, camera and projector together) of every pixel the last triangulate_subpixel
+        over the view triangulated; NaN elsewhere."""
+        return self._plane("sl3d_get_residuals", np.float32, view)
+
+    def correspondences_subpixel(self, view=0):
+        """(H, W, 2) float64: the continuous projector coordinates (xs, ys) stage 5 rounds into c_p_map; NaN where either axis is invalid."""
+        out = np.empty((self.H, self.W, 2), dtype=np.float64)
+        self._chk(self.L.sl3d_get_correspondences_subpixel(self._h, view, out.ctypes.data, self.W), "sl3d_get_correspondences_subpixel")
         return out
 
     def points(self, view=0):

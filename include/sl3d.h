@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.14.0"
+#define SL3D_VERSION_STRING "0.15.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -266,6 +266,41 @@ int sl3d_triangulate(sl3d_ctx *ctx, int view);
  * call synchronises.  SL3D_E_INVALID_ARG for a bad view, an axis outside {0, 1} or a radius outside 1..8; SL3D_E_STATE without
  * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes.  A refused call changes nothing. */
 int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t counts[2]);
+
+/* ---- sub-pixel triangulation with a reprojection residual (0.15.0; needs SL3D_FLAG_KEEP_STAGES) -------------------------------------
+ * Stage 5 rounds every projector coordinate to an integer (lrint, 5/compute_correspondance.cpp:648,659) before stage 7 triangulates
+ * from it: up to half a projector pixel per axis, which shows as depth terraces in every surface built on the scan.  This call is an
+ * alternative to sl3d_triangulate, after sl3d_compute_c_p_map, that triangulates from the doubles lrint was handed instead.  c_p_map
+ * and the parity contract are not touched.  All views of a call are triangulated by ONE launch.  For every window pixel of views
+ * [first_view, first_view + n_views) whose merged valid byte is 1:
+ *   1. xs = (double)fringe_width_v * ((double)unwrapped_v / ((2.0 * 22.0) / 7.0)), ys likewise from the horizontal axis: exactly the
+ *      arguments of stage 5's lrint, so rint(xs), rint(ys) is the pixel's c_p_map entry
+ *   2. (u, v) = the camera pixel, (u', v') = (xs, ys), each undistorted (the five iterations of cvUndistortPoints, the projector's at the
+ *      continuous point) and re-projected by its K, as stage 7 does with the integers
+ *   3. X = the least-squares point of stage 7's 4 x 3 system at (u, v, u', v'), with its rule X = 0 where the determinant is 0
+ *   4. per device D with projection matrix A_D (sl3d_get_projection_matrices): h = A_D * (X, 1), e_D = (h0/h2 - u_D, h1/h2 - v_D);
+ *      residual = (float)sqrt(e_cam . e_cam + e_proj . e_proj): the reprojection error in undistorted pixels, camera and projector
+ *      together -- the one degree of freedom the system has to spare, a consistency measure of the two decoded axes.  (It does not see
+ *      every wrong decode: a period error along the epipolar direction leaves it small.  It is no replacement for sl3d_repair_periods.)
+ *   5. only if max_residual is finite: the pixel is rejected iff !((double)residual <= max_residual), decided on the stored float
+ *   6. points = (float)X, intersection_points = X, the residual plane = residual; a rejected pixel gets merged valid 0, points NaN,
+ *      intersection_points 0 and keeps its residual.  Every other pixel of those views gets points NaN, intersection_points 0, residual
+ *      NaN, as after sl3d_triangulate.  c_p_map, the per-axis planes and the per-axis valid maps are not touched.
+ * Everything that reads the dense result (sl3d_get_points, sl3d_compact_views, sl3d_get_cloud, the meshes and their consumers) then sees
+ * the sub-pixel scan.  sl3d_compute_c_p_map undoes the rejections; sl3d_compute_c_p_map + sl3d_triangulate restores the integer result.
+ * Works after sl3d_run on a KEEP_STAGES context, and after sl3d_repair_periods + sl3d_compute_c_p_map.
+ * counts: NULL (the call stays asynchronous) or n_views pairs; counts[2k] = pixels of view first_view + k triangulated (merged valid 1 on
+ * entry), counts[2k + 1] = those of them rejected; then a second small launch adds them up and the call synchronises.
+ * SL3D_E_INVALID_ARG for bad views or a max_residual that is NaN or <= 0 (+infinity: no pixel is rejected); SL3D_E_STATE without
+ * SL3D_FLAG_KEEP_STAGES or before sl3d_set_calibration.  A refused call changes nothing. */
+int sl3d_triangulate_subpixel(sl3d_ctx *ctx, int first_view, int n_views, double max_residual, uint32_t *counts);
+/* The residual plane of a view, out[row * stride_elems + col]: NaN on every pixel the last sl3d_triangulate_subpixel over the view did
+ * not triangulate (and on a view none has run over).  SL3D_E_STATE before the context's first sl3d_triangulate_subpixel. */
+int sl3d_get_residuals(sl3d_ctx *ctx, int view, float *out, size_t stride_elems);
+/* (xs, ys) of step 1 for every window pixel, xy[(row * stride_elems + col) * 2 + {0, 1}], bit for bit those expressions; NaN where
+ * either per-axis valid byte is not 1 (the pixels stage 5 does not form them for).  Computed from the stage-4 planes as they are: no
+ * sl3d_compute_c_p_map is needed, a rejection does not show.  SL3D_E_STATE without SL3D_FLAG_KEEP_STAGES. */
+int sl3d_get_correspondences_subpixel(sl3d_ctx *ctx, int view, double *xy, size_t stride_elems);
 
 /* ---- the fused hot path ------------------------------------------------------------------- */
 /* Stages 3(v) 3(h) 4(v) 4(h) 5 7 in main()'s order (m_tech_project_console.cpp:372-395) plus the
