@@ -22,23 +22,6 @@ SL3D_SMOOTH_FIX_BOUNDARY, SL3D_SMOOTH_NORMALS = 1, 2
 SL3D_LOD_MEAN, SL3D_LOD_NORMALS = 1, 2
 SL3D_FILL_NORMALS = 1
 
-# every symbol include/sl3d.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = (
-    "sl3d_version", "sl3d_strerror", "sl3d_last_error", "sl3d_create", "sl3d_destroy",
-    "sl3d_set_calibration", "sl3d_get_projection_matrices", "sl3d_set_mask", "sl3d_set_masks", "sl3d_set_masks_modulated", "sl3d_get_modulation", "sl3d_set_mask_colrow", "sl3d_set_frames_range", "sl3d_get_global_colrow", "sl3d_set_frames", "sl3d_copy_view", "sl3d_synth_view", "sl3d_get_frames",
-    "sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_compute_c_p_map", "sl3d_triangulate", "sl3d_repair_periods", "sl3d_triangulate_subpixel", "sl3d_get_residuals", "sl3d_get_correspondences_subpixel",
-    "sl3d_run", "sl3d_run_clouds", "sl3d_get_cloud_counts", "sl3d_get_cloud_segments", "sl3d_download_clouds", "sl3d_register_clouds", "sl3d_fused_kernel_name", "sl3d_last_fused_kernel_name", "sl3d_launch_counts", "sl3d_camera_table_bytes_per_pixel", "sl3d_run_timed", "sl3d_synchronize", "sl3d_timer_start", "sl3d_timer_stop",
-    "sl3d_get_valid_map", "sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code",
-    "sl3d_get_debug_image", "sl3d_get_c_p_map", "sl3d_get_intersection_points", "sl3d_get_points",
-    "sl3d_get_cloud", "sl3d_set_texture", "sl3d_get_cloud_rgb", "sl3d_compact", "sl3d_compact_views", "sl3d_get_clouds", "sl3d_mesh_views", "sl3d_get_meshes", "sl3d_mesh_normals", "sl3d_get_mesh_normals", "sl3d_mesh_components", "sl3d_get_mesh_components", "sl3d_mesh_views_filtered", "sl3d_get_meshes_filtered", "sl3d_mesh_smooth", "sl3d_get_mesh_smoothed", "sl3d_mesh_views_lod", "sl3d_get_meshes_lod", "sl3d_mesh_fill_holes", "sl3d_get_meshes_holes_filled", "sl3d_register_views", "sl3d_transform_cloud", "sl3d_host_alloc", "sl3d_host_free", "sl3d_process_views", "sl3d_undistort", "sl3d_set_frames_raw", "sl3d_pattern_counts", "sl3d_generate_pattern",
-    "sl3d_get_device_buffers", "sl3d_download", "sl3d_download_2d",
-    "sl3d_group_create", "sl3d_group_destroy", "sl3d_group_last_error", "sl3d_group_size", "sl3d_group_stripe", "sl3d_group_transport",
-    "sl3d_group_set_calibration", "sl3d_group_set_mask", "sl3d_group_set_frames", "sl3d_group_run", "sl3d_group_gather",
-    "sl3d_group_get_points", "sl3d_group_download_points", "sl3d_group_process_views", "sl3d_group_get_device_buffers", "sl3d_group_run_clouds", "sl3d_group_gather_clouds",
-    "sl3d_group_get_cloud", "sl3d_group_synchronize",
-)
-
-
 class Sl3dError(RuntimeError):
     pass
 
@@ -95,11 +78,125 @@ class MeshHoles(C.Structure):
                 ("view_stride_points", C.c_size_t), ("view_stride_faces", C.c_size_t)]
 
 
+_vp, _i, _u, _f, _d, _sz, _i64 = C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t, C.c_int64
+_pvp, _pi, _pu, _pf, _psz, _p64 = (C.POINTER(t) for t in (_vp, _i, _u, _f, _sz, _i64))
+
+# The C ABI as ctypes sees it, stated by hand and independently of include/sl3d.h (tests/test_binding.py holds one against the other):
+# a row per exported function in the header's order -- (name, argtypes) or, where the function does not return an int status,
+# (name, argtypes, restype).  A new function gets its row here and nothing else; load_library applies the table.
+_PROTOTYPES = (
+    ("sl3d_version", [], C.c_char_p),
+    ("sl3d_strerror", [_i], C.c_char_p),
+    ("sl3d_last_error", [_vp], C.c_char_p),
+    ("sl3d_create", [C.POINTER(Config), _pvp]),
+    ("sl3d_destroy", [_vp], None),
+    ("sl3d_set_calibration", [_vp] + [_vp] * 8),
+    ("sl3d_get_projection_matrices", [_vp, _vp, _vp]),
+    ("sl3d_set_mask", [_vp, _i, _vp, _sz]),
+    ("sl3d_set_masks", [_vp, _i, _i, _vp, _sz, _sz]),
+    ("sl3d_set_masks_modulated", [_vp, _i, _i, _d, _vp, _sz, _sz]),
+    ("sl3d_get_modulation", [_vp, _i, _i, _vp, _sz]),
+    ("sl3d_set_mask_colrow", [_vp, _i, _vp]),
+    ("sl3d_set_frames_range", [_vp, _i, _i, _i, _vp, _i, _sz]),
+    ("sl3d_get_global_colrow", [_vp, _i, _i, _vp, _i, _i]),
+    ("sl3d_set_frames", [_vp, _i, _i, _vp, _i, _sz]),
+    ("sl3d_copy_view", [_vp, _i, _i]),
+    ("sl3d_synth_view", [_vp, _i, _vp, C.c_uint64, _i, _i, _f, _f]),
+    ("sl3d_get_frames", [_vp, _i, _i, _vp, _i, _sz]),
+    ("sl3d_compute_wrapped_phase", [_vp, _i, _i]),
+    ("sl3d_unwrap_phase", [_vp, _i, _i]),
+    ("sl3d_compute_c_p_map", [_vp, _i]),
+    ("sl3d_triangulate", [_vp, _i]),
+    ("sl3d_repair_periods", [_vp, _i, _i, _i, _pu]),
+    ("sl3d_triangulate_subpixel", [_vp, _i, _i, _d, _pu]),
+    ("sl3d_get_residuals", [_vp, _i, _vp, _sz]),
+    ("sl3d_get_correspondences_subpixel", [_vp, _i, _vp, _sz]),
+    ("sl3d_run", [_vp, _i, _i]),
+    ("sl3d_run_clouds", [_vp, _i, _i]),
+    ("sl3d_get_cloud_counts", [_vp, _i, _i, _pvp, _psz, _p64]),
+    ("sl3d_get_cloud_segments", [_vp, _i, _i, C.POINTER(CloudSegments), _p64]),
+    ("sl3d_download_clouds", [_vp, _i, _i, _vp, _i64, _p64]),
+    ("sl3d_register_clouds", [_vp, _i, _i, _f, _f, _f, _f, _vp, _i64, _p64]),
+    ("sl3d_fused_kernel_name", [_vp, _i, _i, C.c_char_p, _sz]),
+    ("sl3d_last_fused_kernel_name", [_vp, C.c_char_p, _sz]),
+    ("sl3d_launch_counts", [_vp, _p64, _p64]),
+    ("sl3d_camera_table_bytes_per_pixel", [_vp, _i]),
+    ("sl3d_run_timed", [_vp, _i, _i, _pf]),
+    ("sl3d_synchronize", [_vp]),
+    ("sl3d_timer_start", [_vp]),
+    ("sl3d_timer_stop", [_vp, _pf]),
+    ("sl3d_get_valid_map", [_vp, _i, _i, _vp, _sz]),
+    ("sl3d_get_wrapped_phase", [_vp, _i, _i, _vp, _sz]),
+    ("sl3d_get_unwrapped_phase", [_vp, _i, _i, _vp, _sz]),
+    ("sl3d_get_code", [_vp, _i, _i, _vp, _sz]),
+    ("sl3d_get_debug_image", [_vp, _i, _i, _i, _vp, _sz]),
+    ("sl3d_get_c_p_map", [_vp, _i, _vp]),
+    ("sl3d_get_intersection_points", [_vp, _i, _vp]),
+    ("sl3d_get_points", [_vp, _i, _vp, _vp]),
+    ("sl3d_get_cloud", [_vp, _i, _vp, _i64, _p64]),
+    ("sl3d_set_texture", [_vp, _i, _vp, _sz]),
+    ("sl3d_get_cloud_rgb", [_vp, _i, _vp, _vp, _i64, _p64]),
+    ("sl3d_compact", [_vp, _i, _pvp, _p64]),
+    ("sl3d_compact_views", [_vp, _i, _i, _pvp, _psz, _p64]),
+    ("sl3d_get_clouds", [_vp, _i, _i, _vp, _i64, _p64]),
+    ("sl3d_mesh_views", [_vp, _i, _i, _f, C.POINTER(Mesh), _p64, _p64]),
+    ("sl3d_get_meshes", [_vp, _i, _i, _f, _vp, _i64, _vp, _i64, _p64, _p64]),
+    ("sl3d_mesh_normals", [_vp, _i, _i, _f, _pvp, _psz, _p64]),
+    ("sl3d_get_mesh_normals", [_vp, _i, _i, _f, _vp, _i64, _p64]),
+    ("sl3d_mesh_components", [_vp, _i, _i, _f, _pvp, _psz, _p64, _p64]),
+    ("sl3d_get_mesh_components", [_vp, _i, _i, _f, _vp, _i64, _p64, _p64]),
+    ("sl3d_mesh_views_filtered", [_vp, _i, _i, _f, _i64, C.POINTER(MeshFiltered), _p64, _p64]),
+    ("sl3d_get_meshes_filtered", [_vp, _i, _i, _f, _i64, _vp, _vp, _i64, _vp, _i64, _p64, _p64]),
+    ("sl3d_mesh_smooth", [_vp, _i, _i, _f, _i, _f, _f, _u, C.POINTER(MeshSmoothed), _p64]),
+    ("sl3d_get_mesh_smoothed", [_vp, _i, _i, _f, _i, _f, _f, _u, _vp, _vp, _i64, _p64]),
+    ("sl3d_mesh_views_lod", [_vp, _i, _i, _i, _f, _i64, _f, _u, C.POINTER(MeshLod), _p64, _p64]),
+    ("sl3d_get_meshes_lod", [_vp, _i, _i, _i, _f, _i64, _f, _u, _vp, _vp, _vp, _i64, _vp, _i64, _p64, _p64]),
+    ("sl3d_mesh_fill_holes", [_vp, _i, _i, _f, _i64, _i64, _f, _u, C.POINTER(MeshHoles), _p64, _p64, _p64, _p64]),
+    ("sl3d_get_meshes_holes_filled", [_vp, _i, _i, _f, _i64, _i64, _f, _u, _vp, _vp, _vp, _i64, _vp, _i64, _p64, _p64, _p64, _p64]),
+    ("sl3d_register_views", [_vp, _i, _i, _f, _f, _f, _f, _vp, _i64, _p64]),
+    ("sl3d_transform_cloud", [_vp, _vp, _i64, _f, _f, _f, _f, _vp]),
+    ("sl3d_host_alloc", [_sz], _vp),
+    ("sl3d_host_free", [_vp], None),
+    ("sl3d_process_views", [_vp, _i, _vp, _sz, _vp, _vp]),
+    ("sl3d_undistort", [_vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp, _sz]),
+    ("sl3d_set_frames_raw", [_vp, _i, _i, _vp, _i, _sz]),
+    ("sl3d_pattern_counts", [_i, _i, _pi, _pi]),
+    ("sl3d_generate_pattern", [_vp, _i, _i, _i, _vp, _sz, _pvp, _psz]),
+    ("sl3d_get_device_buffers", [_vp, C.POINTER(DeviceBuffers)]),
+    ("sl3d_download", [_vp, _vp, _vp, _sz]),
+    ("sl3d_download_2d", [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
+    ("sl3d_group_create", [C.POINTER(Config), _pi, _i, _pvp]),
+    ("sl3d_group_destroy", [_vp], None),
+    ("sl3d_group_last_error", [_vp], C.c_char_p),
+    ("sl3d_group_size", [_vp]),
+    ("sl3d_group_stripe", [_vp, _i, _pi, _pi, _pi, _pvp]),
+    ("sl3d_group_transport", [_vp], C.c_char_p),
+    ("sl3d_group_set_calibration", [_vp] + [_vp] * 8),
+    ("sl3d_group_set_mask", [_vp, _i, _vp, _sz]),
+    ("sl3d_group_set_frames", [_vp, _i, _i, _vp, _i, _sz]),
+    ("sl3d_group_run", [_vp, _i, _i]),
+    ("sl3d_group_gather", [_vp, _i, _i]),
+    ("sl3d_group_get_points", [_vp, _i, _vp, _vp]),
+    ("sl3d_group_download_points", [_vp, _i, _i, _vp, _vp]),
+    ("sl3d_group_process_views", [_vp, _i, _vp, _sz, _vp, _vp]),
+    ("sl3d_group_get_device_buffers", [_vp, C.POINTER(DeviceBuffers)]),
+    ("sl3d_group_run_clouds", [_vp, _i, _i]),
+    ("sl3d_group_gather_clouds", [_vp, _i, _i, _p64]),
+    ("sl3d_group_get_cloud", [_vp, _i, _vp, _i64, _p64]),
+    ("sl3d_group_synchronize", [_vp]),
+)
+# every symbol include/sl3d.h declares (tests check the library exports all of them)
+ABI_SYMBOLS = tuple(row[0] for row in _PROTOTYPES)
+
 _lib = None
 
 
 def load_library(path=None):
-    """dlopen the product library; raises if it has not been built (no CPU fallback exists)."""
+    """dlopen the product library; raises if it has not been built (no CPU fallback exists).
+
+    Missing symbols have one rule: with SL3D_LIB set (another build of the library, A/B runs with tools/ab.sh) a function the loaded
+    build lacks is skipped, whatever release it came with, and a later call to it fails with AttributeError; without SL3D_LIB any
+    missing function raises here."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -108,158 +205,14 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    vp, i = C.c_void_p, C.c_int
-    L.sl3d_version.restype = C.c_char_p
-    L.sl3d_strerror.restype = C.c_char_p
-    L.sl3d_strerror.argtypes = [i]
-    L.sl3d_last_error.restype = C.c_char_p
-    L.sl3d_last_error.argtypes = [vp]
-    L.sl3d_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    L.sl3d_destroy.argtypes = [vp]
-    L.sl3d_destroy.restype = None
-    L.sl3d_set_calibration.argtypes = [vp] + [vp] * 8
-    L.sl3d_get_projection_matrices.argtypes = [vp, vp, vp]
-    L.sl3d_set_mask.argtypes = [vp, i, vp, C.c_size_t]
-    L.sl3d_set_frames.argtypes = [vp, i, i, vp, i, C.c_size_t]
-    try:
-        L.sl3d_set_masks.argtypes = [vp, i, i, vp, C.c_size_t, C.c_size_t]
-        L.sl3d_last_fused_kernel_name.argtypes = [vp, C.c_char_p, C.c_size_t]
-        L.sl3d_camera_table_bytes_per_pixel.argtypes = [vp, i]
-    except AttributeError:   # an older build of the library under SL3D_LIB (A/B runs against a previous round)
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        L.sl3d_set_masks_modulated.argtypes = [vp, i, i, C.c_double, vp, C.c_size_t, C.c_size_t]
-        L.sl3d_get_modulation.argtypes = [vp, i, i, vp, C.c_size_t]
-    except AttributeError:   # a build before 0.7.0 under SL3D_LIB (A/B runs against the parent): everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        L.sl3d_mesh_views.argtypes = [vp, i, i, C.c_float, C.POINTER(Mesh), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.sl3d_get_meshes.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    except AttributeError:   # a build before 0.8.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        L.sl3d_mesh_normals.argtypes = [vp, i, i, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-        L.sl3d_get_mesh_normals.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, C.POINTER(C.c_int64)]
-    except AttributeError:   # a build before 0.9.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        p64 = C.POINTER(C.c_int64)
-        L.sl3d_mesh_components.argtypes = [vp, i, i, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), p64, p64]
-        L.sl3d_get_mesh_components.argtypes = [vp, i, i, C.c_float, vp, C.c_int64, p64, p64]
-        L.sl3d_mesh_views_filtered.argtypes = [vp, i, i, C.c_float, C.c_int64, C.POINTER(MeshFiltered), p64, p64]
-        L.sl3d_get_meshes_filtered.argtypes = [vp, i, i, C.c_float, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, p64, p64]
-    except AttributeError:   # a build before 0.10.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        f, u = C.c_float, C.c_uint
-        L.sl3d_mesh_smooth.argtypes = [vp, i, i, f, i, f, f, u, C.POINTER(MeshSmoothed), C.POINTER(C.c_int64)]
-        L.sl3d_get_mesh_smoothed.argtypes = [vp, i, i, f, i, f, f, u, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
-    except AttributeError:   # a build before 0.11.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        f, u, i64, p64 = C.c_float, C.c_uint, C.c_int64, C.POINTER(C.c_int64)
-        L.sl3d_mesh_views_lod.argtypes = [vp, i, i, i, f, i64, f, u, C.POINTER(MeshLod), p64, p64]
-        L.sl3d_get_meshes_lod.argtypes = [vp, i, i, i, f, i64, f, u, vp, vp, vp, i64, vp, i64, p64, p64]
-    except AttributeError:   # a build before 0.12.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        f, u, i64, p64 = C.c_float, C.c_uint, C.c_int64, C.POINTER(C.c_int64)
-        L.sl3d_mesh_fill_holes.argtypes = [vp, i, i, f, i64, i64, f, u, C.POINTER(MeshHoles), p64, p64, p64, p64]
-        L.sl3d_get_meshes_holes_filled.argtypes = [vp, i, i, f, i64, i64, f, u, vp, vp, vp, i64, vp, i64, p64, p64, p64, p64]
-    except AttributeError:   # a build before 0.13.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        L.sl3d_repair_periods.argtypes = [vp, i, i, i, C.POINTER(C.c_uint32)]
-    except AttributeError:   # a build before 0.14.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    try:
-        L.sl3d_triangulate_subpixel.argtypes = [vp, i, i, C.c_double, C.POINTER(C.c_uint32)]
-        L.sl3d_get_residuals.argtypes = [vp, i, vp, C.c_size_t]
-        L.sl3d_get_correspondences_subpixel.argtypes = [vp, i, vp, C.c_size_t]
-    except AttributeError:   # a build before 0.15.0 under SL3D_LIB: everything else still loads
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    L.sl3d_set_mask_colrow.argtypes = [vp, i, vp]
-    L.sl3d_set_frames_range.argtypes = [vp, i, i, i, vp, i, C.c_size_t]
-    L.sl3d_get_global_colrow.argtypes = [vp, i, i, vp, i, i]
-    for n in ("sl3d_compute_wrapped_phase", "sl3d_unwrap_phase", "sl3d_copy_view"):
-        getattr(L, n).argtypes = [vp, i, i]
-    for n in ("sl3d_compute_c_p_map", "sl3d_triangulate"):
-        getattr(L, n).argtypes = [vp, i]
-    L.sl3d_synth_view.argtypes = [vp, i, vp, C.c_uint64, i, i, C.c_float, C.c_float]
-    L.sl3d_get_frames.argtypes = [vp, i, i, vp, i, C.c_size_t]
-    L.sl3d_run.argtypes = [vp, i, i]
-    L.sl3d_run_clouds.argtypes = [vp, i, i]
-    L.sl3d_get_cloud_counts.argtypes = [vp, i, i, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-    L.sl3d_get_cloud_segments.argtypes = [vp, i, i, C.POINTER(CloudSegments), C.POINTER(C.c_int64)]
-    L.sl3d_download_clouds.argtypes = [vp, i, i, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_register_clouds.argtypes = [vp, i, i, C.c_float, C.c_float, C.c_float, C.c_float, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_run_timed.argtypes = [vp, i, i, C.POINTER(C.c_float)]
-    try:
-        L.sl3d_fused_kernel_name.argtypes = [vp, i, i, C.c_char_p, C.c_size_t]
-    except AttributeError:   # an older build of the library under SL3D_LIB (A/B runs against a previous round): the name is cosmetic
-        if not os.environ.get("SL3D_LIB"):
-            raise
-    L.sl3d_synchronize.argtypes = [vp]
-    L.sl3d_timer_start.argtypes = [vp]
-    L.sl3d_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
-    L.sl3d_get_valid_map.argtypes = [vp, i, i, vp, C.c_size_t]
-    for n in ("sl3d_get_wrapped_phase", "sl3d_get_unwrapped_phase", "sl3d_get_code"):
-        getattr(L, n).argtypes = [vp, i, i, vp, C.c_size_t]
-    L.sl3d_get_debug_image.argtypes = [vp, i, i, i, vp, C.c_size_t]
-    L.sl3d_get_c_p_map.argtypes = [vp, i, vp]
-    L.sl3d_get_intersection_points.argtypes = [vp, i, vp]
-    L.sl3d_get_points.argtypes = [vp, i, vp, vp]
-    L.sl3d_get_cloud.argtypes = [vp, i, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_compact_views.argtypes = [vp, i, i, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-    L.sl3d_get_clouds.argtypes = [vp, i, i, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_set_texture.argtypes = [vp, i, vp, C.c_size_t]
-    L.sl3d_get_cloud_rgb.argtypes = [vp, i, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_compact.argtypes = [vp, i, C.POINTER(vp), C.POINTER(C.c_int64)]
-    L.sl3d_register_views.argtypes = [vp, i, i, C.c_float, C.c_float, C.c_float, C.c_float, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_host_alloc.restype = vp
-    L.sl3d_host_alloc.argtypes = [C.c_size_t]
-    L.sl3d_host_free.restype = None
-    L.sl3d_host_free.argtypes = [vp]
-    L.sl3d_process_views.argtypes = [vp, i, vp, C.c_size_t, vp, vp]
-    L.sl3d_set_frames_raw.argtypes = [vp, i, i, vp, i, C.c_size_t]
-    L.sl3d_undistort.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, C.c_size_t]
-    L.sl3d_pattern_counts.argtypes = [i, i, C.POINTER(i), C.POINTER(i)]
-    L.sl3d_generate_pattern.argtypes = [vp, i, i, i, vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.sl3d_transform_cloud.argtypes = [vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, vp]
-    L.sl3d_download.argtypes = [vp, vp, vp, C.c_size_t]
-    L.sl3d_download_2d.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.sl3d_get_device_buffers.argtypes = [vp, C.POINTER(DeviceBuffers)]
-    L.sl3d_group_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_int), i, C.POINTER(vp)]
-    L.sl3d_group_destroy.argtypes = [vp]
-    L.sl3d_group_destroy.restype = None
-    L.sl3d_group_last_error.restype = C.c_char_p
-    L.sl3d_group_last_error.argtypes = [vp]
-    L.sl3d_group_transport.restype = C.c_char_p
-    L.sl3d_group_transport.argtypes = [vp]
-    L.sl3d_group_size.argtypes = [vp]
-    L.sl3d_group_stripe.argtypes = [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(vp)]
-    L.sl3d_group_set_calibration.argtypes = [vp] + [vp] * 8
-    L.sl3d_group_set_mask.argtypes = [vp, i, vp, C.c_size_t]
-    L.sl3d_group_set_frames.argtypes = [vp, i, i, vp, i, C.c_size_t]
-    for n in ("sl3d_group_run", "sl3d_group_gather", "sl3d_group_run_clouds"):
-        getattr(L, n).argtypes = [vp, i, i]
-    L.sl3d_group_gather_clouds.argtypes = [vp, i, i, C.POINTER(C.c_int64)]
-    L.sl3d_group_get_points.argtypes = [vp, i, vp, vp]
-    L.sl3d_group_download_points.argtypes = [vp, i, i, vp, vp]
-    L.sl3d_group_process_views.argtypes = [vp, i, vp, C.c_size_t, vp, vp]
-    L.sl3d_group_get_device_buffers.argtypes = [vp, C.POINTER(DeviceBuffers)]
-    L.sl3d_group_get_cloud.argtypes = [vp, i, vp, C.c_int64, C.POINTER(C.c_int64)]
-    L.sl3d_group_synchronize.argtypes = [vp]
+    for name, argtypes, *restype in _PROTOTYPES:
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            if not os.environ.get("SL3D_LIB"):
+                raise
+            continue
+        fn.argtypes, fn.restype = argtypes, restype[0] if restype else C.c_int
     if path is None:
         _lib = L
     return L
@@ -281,29 +234,22 @@ def _cut(flat, counts):
     return [flat[e - n:e] for n, e in zip(counts, ends)]
 
 
-class Scanner:
-    """One context = one GPU + one stream + the HBM-resident frame stacks of `max_views` views."""
+def _ptrs(arrs):
+    """The void* array the C side takes for a list of planes."""
+    return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
 
-    def __init__(self, width, height, proj_width, proj_height, n_gray_v, n_gray_h, fringe_width_v, fringe_width_h,
-                 n_fringe=3, n_codes_v=0, n_codes_h=0, max_views=1, device=0, keep_stages=False,
-                 full_size=None, origin=(0, 0), stream=None, eager_mask=False, serial_launches=False):
-        """eager_mask: SL3D_FLAG_EAGER_MASK -- every mask is prepared by k_mask_prepare when it is set; by default a timed context
-        defers masks of up to 4 views to the next launch over them (the fused kernel evaluates the selection itself)."""
-        self.L = load_library()
-        fw, fh = full_size if full_size else (width, height)
-        self.cfg = Config(width, height, fw, fh, origin[0], origin[1], proj_width, proj_height, n_fringe,
-                          n_gray_v, n_gray_h, fringe_width_v, fringe_width_h, n_codes_v, n_codes_h,
-                          max_views, device, (SL3D_FLAG_KEEP_STAGES if keep_stages else 0) | (SL3D_FLAG_EAGER_MASK if eager_mask else 0) |
-                          (SL3D_FLAG_SERIAL_LAUNCHES if serial_launches else 0), stream)
-        self.W, self.H = width, height
-        self._h = C.c_void_p()
-        rc = self.L.sl3d_create(C.byref(self.cfg), C.byref(self._h))
-        if rc != 0:
-            raise Sl3dError(f"sl3d_create: {self.L.sl3d_strerror(rc).decode()}: {self.L.sl3d_last_error(None).decode()}")
+
+_XYZ, _RGB, _TRI, _IDS = (np.float32, 3), (np.uint8, 3), (np.int32, 3), (np.int32,)   # an output array: (dtype, *shape of one row)
+
+
+class _Handle:
+    """What Scanner and Group share: the life of the handle, the status check, the calling idioms of the C ABI written once each, and
+    the methods that differ by the symbol prefix alone."""
+    _prefix = "sl3d_"
 
     def close(self):
         if getattr(self, "_h", None):
-            self.L.sl3d_destroy(self._h)
+            getattr(self.L, self._prefix + "destroy")(self._h)
             self._h = None
         for p in getattr(self, "_pinned", []):
             self.L.sl3d_host_free(p)
@@ -323,24 +269,138 @@ class Scanner:
 
     def _chk(self, rc, what):
         if rc != 0:
-            raise Sl3dError(f"{what}: {self.L.sl3d_strerror(rc).decode()}: {self.L.sl3d_last_error(self._h).decode()}")
+            last_error = getattr(self.L, self._prefix + "last_error")
+            raise Sl3dError(f"{what}: {self.L.sl3d_strerror(rc).decode()}: {last_error(self._h).decode()}")
 
-    # ---- inputs -------------------------------------------------------------------------------
+    def _call(self, name, *args):
+        """<prefix><name>(handle, *args), checked."""
+        name = self._prefix + name
+        self._chk(getattr(self.L, name)(self._h, *args), name)
+
+    def _planes(self, planes):
+        """(the H x W uint8 planes as contiguous arrays -- keep them alive over the call --, their pointer array)"""
+        arrs = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
+        for a in arrs:
+            assert a.shape == (self.H, self.W), a.shape
+        return arrs, _ptrs(arrs)
+
+    def _plane(self, fn, dtype, view, *pre, comps=1, tail=None):
+        """A fresh (H, W) or (H, W, comps) image filled by fn(handle, view, *pre, image, *tail); tail: by default the row stride in elements."""
+        shape = (self.H, self.W) if comps == 1 else (self.H, self.W, comps)
+        out = np.empty(shape, dtype=dtype)
+        self._chk(getattr(self.L, fn)(self._h, view, *pre, out.ctypes.data, *((self.W * comps,) if tail is None else tail)), fn)
+        return out
+
+    def _counts(self, fn, n_counts, first_view, n_views, *args):
+        """fn(handle, first_view, n_views, *args, count arrays...) with n_counts arrays of n_views int64: the counts as lists of int."""
+        counts = [(C.c_int64 * n_views)() for _ in range(n_counts)]
+        self._chk(getattr(self.L, fn)(self._h, first_view, n_views, *args, *counts), fn)
+        return [[int(c) for c in a] for a in counts]
+
+    def _fill(self, fn, args, *specs):
+        """Size then fill with one count: fn(handle, *args, outputs..., capacity, &n) is called with null outputs and capacity 0 for n,
+        then with fresh arrays of n rows, one per spec (dtype, *shape of a row); returns the arrays."""
+        n, f = C.c_int64(0), getattr(self.L, fn)
+        self._chk(f(self._h, *args, *[None] * len(specs), 0, C.byref(n)), fn)
+        outs = [np.empty((n.value,) + s[1:], dtype=s[0]) for s in specs]
+        self._chk(f(self._h, *args, *[o.ctypes.data for o in outs], n.value, C.byref(n)), fn)
+        return outs
+
+    def _fill_views(self, fn, first_view, n_views, args, *groups, n_counts):
+        """Size then fill for a batch of views: fn(handle, first_view, n_views, *args, vertex outputs..., vertex capacity[, face outputs...,
+        face capacity], count arrays...) is called with null outputs and capacities 0 for the per-view counts, then with arrays of their
+        sums.  groups: the vertex outputs and, where the function has them, the face outputs, each a list in the C order of (dtype,
+        *shape of a row) for a fresh array, None for an output that is not requested (it stays null) or a 2-D array to fill; the first
+        of a group is always requested.  Of the n_counts count arrays of n_views int64 the first holds the vertex counts, the second
+        (with faces) the face counts.  Returns, per group, the list of its outputs cut per view (None for a null one), then the count arrays."""
+        counts, f = [(C.c_int64 * n_views)() for _ in range(n_counts)], getattr(self.L, fn)
+
+        def call(filled):
+            outs = []
+            for arrs in filled:
+                outs += [None if a is None else a.ctypes.data for a in arrs] + [0 if arrs[0] is None else len(arrs[0])]
+            self._chk(f(self._h, first_view, n_views, *args, *outs, *counts), fn)
+
+        call([[None] * len(g) for g in groups])
+        filled = []
+        for g, c in zip(groups, counts):
+            filled.append([s if s is None or isinstance(s, np.ndarray) else np.empty((sum(c),) + s[1:], dtype=s[0]) for s in g])
+            assert all(a is None or len(a) >= sum(c) for a in filled[-1])
+        call(filled)
+        return (*[[None if a is None else _cut(a, c) for a in arrs] for arrs, c in zip(filled, counts)], counts)
+
+    # ---- what Scanner and Group differ in by the prefix alone -----------------------------------
     def set_calibration(self, Kc, dc, rc, tc, Kp, dp, rp, tp):
         a = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (Kc, dc, rc, tc, Kp, dp, rp, tp)]
         assert [v.size for v in a] == [9, 5, 3, 3, 9, 5, 3, 3]
-        self._chk(self.L.sl3d_set_calibration(self._h, *[v.ctypes.data for v in a]), "sl3d_set_calibration")
+        self._call("set_calibration", *[v.ctypes.data for v in a])
 
+    def set_mask(self, full_frame_mask, view=0):
+        m = np.ascontiguousarray(full_frame_mask, dtype=np.uint8)
+        assert m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
+        self._call("set_mask", view, m.ctypes.data, m.strides[0])
+
+    def set_frames(self, axis, planes, view=0):
+        arrs, ptrs = self._planes(planes)
+        self._call("set_frames", view, axis, ptrs, len(arrs), arrs[0].strides[0])
+
+    def points(self, view=0):
+        xyz = np.empty((self.H, self.W, 3), dtype=np.float32)
+        return xyz, self._plane(self._prefix + "get_points", np.uint8, view, xyz.ctypes.data, tail=())
+
+    def cloud(self, view=0):
+        return self._fill(self._prefix + "get_cloud", (view,), _XYZ)[0]
+
+    def _process_views(self, frames, xyz, valid):
+        n, ppv, H, W = frames.shape
+        assert (H, W) == (self.H, self.W) and frames.dtype == np.uint8 and frames.strides[3] == 1 and frames.strides[2] >= W
+        if xyz is None:
+            xyz = np.empty((n, H, W, 3), dtype=np.float32)
+        if valid is None:
+            valid = np.empty((n, H, W), dtype=np.uint8)
+        ptrs = _ptrs([frames[v, p] for v in range(n) for p in range(ppv)])
+        self._call("process_views", n, ptrs, frames.strides[2], xyz.ctypes.data, valid.ctypes.data)
+        return xyz, valid
+
+
+class Scanner(_Handle):
+    """One context = one GPU + one stream + the HBM-resident frame stacks of `max_views` views."""
+
+    def __init__(self, width, height, proj_width, proj_height, n_gray_v, n_gray_h, fringe_width_v, fringe_width_h,
+                 n_fringe=3, n_codes_v=0, n_codes_h=0, max_views=1, device=0, keep_stages=False,
+                 full_size=None, origin=(0, 0), stream=None, eager_mask=False, serial_launches=False):
+        """eager_mask: SL3D_FLAG_EAGER_MASK -- every mask is prepared by k_mask_prepare when it is set; by default a timed context
+        defers masks of up to 4 views to the next launch over them (the fused kernel evaluates the selection itself)."""
+        self.L = load_library()
+        fw, fh = full_size if full_size else (width, height)
+        self.cfg = Config(width, height, fw, fh, origin[0], origin[1], proj_width, proj_height, n_fringe,
+                          n_gray_v, n_gray_h, fringe_width_v, fringe_width_h, n_codes_v, n_codes_h,
+                          max_views, device, (SL3D_FLAG_KEEP_STAGES if keep_stages else 0) | (SL3D_FLAG_EAGER_MASK if eager_mask else 0) |
+                          (SL3D_FLAG_SERIAL_LAUNCHES if serial_launches else 0), stream)
+        self.W, self.H = width, height
+        self._h = C.c_void_p()
+        rc = self.L.sl3d_create(C.byref(self.cfg), C.byref(self._h))
+        if rc != 0:
+            raise Sl3dError(f"sl3d_create: {self.L.sl3d_strerror(rc).decode()}: {self.L.sl3d_last_error(None).decode()}")
+
+    # ---- inputs -------------------------------------------------------------------------------
     def projection_matrices(self):
         """(A_cam, A_proj): the 3x4 matrices K [R|t] the library derived from the calibration (T0, compute_A)."""
         a, b = np.zeros(12), np.zeros(12)
         self._chk(self.L.sl3d_get_projection_matrices(self._h, a.ctypes.data, b.ctypes.data), "sl3d_get_projection_matrices")
         return a.reshape(3, 4), b.reshape(3, 4)
 
-    def set_mask(self, full_frame_mask, view=0):
-        m = np.ascontiguousarray(full_frame_mask, dtype=np.uint8)
-        assert m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
-        self._chk(self.L.sl3d_set_mask(self._h, view, m.ctypes.data, m.strides[0]), "sl3d_set_mask")
+    def _mask_args(self, m, first_view, n_views):
+        """(number of views, address, row stride, view stride) of a mask argument m, a contiguous uint8 array: None, one full-frame mask
+        that n_views views get (by default all from first_view on: view stride 0) or a stack [n][full_height][full_width]."""
+        if m is None or m.ndim == 2:
+            assert m is None or m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
+            n, vs = (self.cfg.max_views - first_view if n_views is None else n_views), 0
+        else:
+            assert m.shape[1:] == (self.cfg.full_height, self.cfg.full_width), m.shape
+            n, vs = m.shape[0], m.strides[0]
+            assert n_views is None or n_views == n
+        return (n, None, 0, vs) if m is None else (n, m.ctypes.data, m.strides[-2], vs)
 
     def set_masks(self, masks, first_view=0, n_views=None):
         """One launch for several views.  masks: one full-frame mask (every view gets it) or an array [n][full_height][full_width]."""
@@ -350,43 +410,19 @@ class Scanner:
             for k in range(n):
                 self.set_mask(m if m.ndim == 2 else m[k], view=first_view + k)
             return
-        if m.ndim == 2:
-            assert m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
-            n, vs = (self.cfg.max_views - first_view if n_views is None else n_views), 0
-        else:
-            assert m.shape[1:] == (self.cfg.full_height, self.cfg.full_width), m.shape
-            n, vs = m.shape[0], m.strides[0]
-            assert n_views is None or n_views == n
-        self._chk(self.L.sl3d_set_masks(self._h, first_view, n, m.ctypes.data, m.strides[-2], vs), "sl3d_set_masks")
+        n, ptr, stride, vs = self._mask_args(m, first_view, n_views)
+        self._chk(self.L.sl3d_set_masks(self._h, first_view, n, ptr, stride, vs), "sl3d_set_masks")
 
     def set_masks_device(self, dev_ptr, stride, view_stride, first_view=0, n_views=1):
         """Masks that already live in device memory (a raw address, e.g. torch.Tensor.data_ptr())."""
         self._chk(self.L.sl3d_set_masks(self._h, first_view, n_views, C.c_void_p(dev_ptr), stride, view_stride), "sl3d_set_masks")
 
-    def set_frames(self, axis, planes, view=0):
-        arrs = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
-        for a in arrs:
-            assert a.shape == (self.H, self.W), a.shape
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        self._chk(self.L.sl3d_set_frames(self._h, view, axis, ptrs, len(arrs), arrs[0].strides[0]), "sl3d_set_frames")
-
     def set_masks_modulated(self, min_modulation, masks=None, first_view=0, n_views=None):
         """set_masks with the fringe-modulation test (sl3d_set_masks_modulated): a pixel stays selected iff its mask byte is 1 (no mask:
         every pixel) and the modulation gamma of both axes' fringes, as resident now, is > min_modulation.  masks: None, one full-frame
         mask (every view gets it) or an array [n][full_height][full_width].  Whole-frame contexts with 3 fringes only."""
-        if masks is None:
-            n = self.cfg.max_views - first_view if n_views is None else n_views
-            ptr, stride, vs = None, 0, 0
-        else:
-            m = np.ascontiguousarray(masks, dtype=np.uint8)
-            if m.ndim == 2:
-                assert m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
-                n, vs = (self.cfg.max_views - first_view if n_views is None else n_views), 0
-            else:
-                assert m.shape[1:] == (self.cfg.full_height, self.cfg.full_width), m.shape
-                n, vs = m.shape[0], m.strides[0]
-                assert n_views is None or n_views == n
-            ptr, stride = m.ctypes.data, m.strides[-2]
+        m = None if masks is None else np.ascontiguousarray(masks, dtype=np.uint8)
+        n, ptr, stride, vs = self._mask_args(m, first_view, n_views)
         self._chk(self.L.sl3d_set_masks_modulated(self._h, first_view, n, float(min_modulation), ptr, stride, vs), "sl3d_set_masks_modulated")
 
     def set_masks_modulated_device(self, min_modulation, dev_ptr, stride, view_stride, first_view=0, n_views=1):
@@ -396,9 +432,7 @@ class Scanner:
 
     def modulation(self, axis, view=0):
         """gamma of one axis (sl3d_get_modulation): float32 [H][W] of the window, NaN where the three fringe bytes are all 0."""
-        out = np.empty((self.H, self.W), dtype=np.float32)
-        self._chk(self.L.sl3d_get_modulation(self._h, view, axis, out.ctypes.data, self.W), "sl3d_get_modulation")
-        return out
+        return self._plane("sl3d_get_modulation", np.float32, view, axis)
 
     def set_mask_colrow(self, selected_region, view=0):
         """selected_region as the reference holds it: int32 array [full_width][full_height] ([col][row]), selected iff == 1."""
@@ -407,10 +441,7 @@ class Scanner:
         self._chk(self.L.sl3d_set_mask_colrow(self._h, view, m.ctypes.data), "sl3d_set_mask_colrow")
 
     def set_frames_range(self, axis, first_plane, planes, view=0):
-        arrs = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
-        for a in arrs:
-            assert a.shape == (self.H, self.W), a.shape
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        arrs, ptrs = self._planes(planes)
         self._chk(self.L.sl3d_set_frames_range(self._h, view, axis, first_plane, ptrs, len(arrs), arrs[0].strides[0]), "sl3d_set_frames_range")
 
     def global_colrow(self, which, view=0, out=None, row0=0):
@@ -425,10 +456,7 @@ class Scanner:
 
     def set_frames_raw(self, axis, planes, view=0):
         """set_frames for raw captures: undistorted on the device with the camera calibration (whole frames only)."""
-        arrs = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
-        for a in arrs:
-            assert a.shape == (self.H, self.W), a.shape
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        arrs, ptrs = self._planes(planes)
         self._chk(self.L.sl3d_set_frames_raw(self._h, view, axis, ptrs, len(arrs), arrs[0].strides[0]), "sl3d_set_frames_raw")
 
     def synth_view(self, view=0, plane=(0.0, 0.05, 0.05), seed=0x3D5CA11, view_id=None, noise=0, gain=0.8, offset=10.0):
@@ -439,8 +467,7 @@ class Scanner:
 
     def frames(self, axis, view=0):
         n = self.cfg.n_fringe + 2 * (self.cfg.n_gray_v if axis == 0 else self.cfg.n_gray_h)
-        arrs = [np.empty((self.H, self.W), dtype=np.uint8) for _ in range(n)]
-        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        arrs, ptrs = self._planes([np.empty((self.H, self.W), dtype=np.uint8) for _ in range(n)])
         self._chk(self.L.sl3d_get_frames(self._h, view, axis, ptrs, n, self.W), "sl3d_get_frames")
         return arrs
 
@@ -454,16 +481,19 @@ class Scanner:
     def unwrap_phase(self, pattern_type, view=0):
         self._chk(self.L.sl3d_unwrap_phase(self._h, view, pattern_type), "sl3d_unwrap_phase")
 
+    def _counted(self, fn, want_counts, n_pairs, *args):
+        """fn(handle, *args, counts) with room for n_pairs pairs of uint32: the pairs as tuples of int, which makes the call wait; or, with
+        want_counts=False, with null (the call stays asynchronous): None."""
+        counts = (C.c_uint32 * (2 * n_pairs))() if want_counts else None
+        self._chk(getattr(self.L, fn)(self._h, *args, counts), fn)
+        return [(int(counts[2 * k]), int(counts[2 * k + 1])) for k in range(n_pairs)] if want_counts else None
+
     def repair_periods(self, axis, radius=4, view=0, want_counts=True):
         """sl3d_repair_periods between unwrap_phase and compute_c_p_map: whole 2*Pi periods taken out of the absolute phase of one axis
         against the lower median of the samples within `radius` pixels along the coded direction; (repaired, unrepairable) pixels of the pass.
         want_counts=False: the call stays asynchronous and returns None."""
-        if not want_counts:
-            self._chk(self.L.sl3d_repair_periods(self._h, view, axis, radius, None), "sl3d_repair_periods")
-            return None
-        counts = (C.c_uint32 * 2)()
-        self._chk(self.L.sl3d_repair_periods(self._h, view, axis, radius, counts), "sl3d_repair_periods")
-        return int(counts[0]), int(counts[1])
+        c = self._counted("sl3d_repair_periods", want_counts, 1, view, axis, radius)
+        return c[0] if c else None
 
     def compute_c_p_map(self, view=0):
         self._chk(self.L.sl3d_compute_c_p_map(self._h, view), "sl3d_compute_c_p_map")
@@ -476,12 +506,8 @@ class Scanner:
         (the doubles stage 5 rounds) for a batch of views in one launch, the reprojection residual of every solve kept as a plane
         (residuals); a finite max_residual rejects the pixels whose stored residual is not <= it.  Returns a list of
         (triangulated, rejected) per view; want_counts=False: the call stays asynchronous and returns None."""
-        if not want_counts:
-            self._chk(self.L.sl3d_triangulate_subpixel(self._h, first_view, n_views, float(max_residual), None), "sl3d_triangulate_subpixel")
-            return None
-        counts = (C.c_uint32 * (2 * max(n_views, 1)))()
-        self._chk(self.L.sl3d_triangulate_subpixel(self._h, first_view, n_views, float(max_residual), counts), "sl3d_triangulate_subpixel")
-        return [(int(counts[2 * k]), int(counts[2 * k + 1])) for k in range(n_views)]
+        c = self._counted("sl3d_triangulate_subpixel", want_counts, max(n_views, 1), first_view, n_views, float(max_residual))
+        return c[:n_views] if c else None
 
     def run_stages(self, view=0):
         """main()'s order (m_tech_project_console.cpp:372-395) through the per-stage kernels."""
@@ -510,25 +536,15 @@ class Scanner:
     def cloud_segments(self, first_view=0, n_views=1):
         """(CloudSegments, [count per view]): the segmented clouds of the last run_clouds where they lie in HBM."""
         seg = CloudSegments()
-        counts = (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_get_cloud_segments(self._h, first_view, n_views, C.byref(seg), counts), "sl3d_get_cloud_segments")
-        return seg, [int(c) for c in counts]
+        return (seg, *self._counts("sl3d_get_cloud_segments", 1, first_view, n_views, C.byref(seg)))
 
     def download_clouds(self, first_view=0, n_views=1, out=None):
         """Host copies of the clouds of the last run_clouds: list of (n_k, 3) float32 arrays (views of `out`, a flat float32 buffer --
         pinned for the zero-copy route -- or of a fresh array)."""
-        counts = (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_download_clouds(self._h, first_view, n_views, None, 0, counts), "sl3d_download_clouds")
-        total = sum(counts)
-        if out is None:
-            out = np.empty(max(total, 1) * 3, dtype=np.float32)
-        assert out.dtype == np.float32 and out.size >= 3 * total
-        self._chk(self.L.sl3d_download_clouds(self._h, first_view, n_views, out.ctypes.data, out.size // 3, counts), "sl3d_download_clouds")
-        res, off = [], 0
-        for n in counts:
-            res.append(out[3 * off:3 * (off + n)].reshape(n, 3))
-            off += n
-        return res
+        assert out is None or out.dtype == np.float32
+        xyz = _XYZ if out is None else out.reshape(-1)[:out.size // 3 * 3].reshape(-1, 3)
+        (clouds,), _ = self._fill_views("sl3d_download_clouds", first_view, n_views, (), [xyz], n_counts=1)
+        return clouds
 
     def download_cloud_into(self, view, out):
         """ONE call of sl3d_download_clouds for one view into `out` (flat float32 buffer; capacity = out.size // 3 points): the number
@@ -541,12 +557,7 @@ class Scanner:
 
     def register_clouds(self, first_view, n_views, tx, ty, tz, rot_step):
         """register_views on the clouds of the last run_clouds (rotation applied while the segments are concatenated)."""
-        n = C.c_int64(0)
-        self._chk(self.L.sl3d_register_clouds(self._h, first_view, n_views, tx, ty, tz, rot_step, None, 0, C.byref(n)), "sl3d_register_clouds")
-        out = np.empty((n.value, 3), dtype=np.float32)
-        self._chk(self.L.sl3d_register_clouds(self._h, first_view, n_views, tx, ty, tz, rot_step, out.ctypes.data, n.value, C.byref(n)),
-                  "sl3d_register_clouds")
-        return out
+        return self._fill("sl3d_register_clouds", (first_view, n_views, tx, ty, tz, rot_step), _XYZ)[0]
 
     def fused_clouds(self, first_view=0, n_views=1):
         """run_clouds + host copies: list of (n_k, 3) float32 arrays in the reference's scan order."""
@@ -584,7 +595,6 @@ class Scanner:
     def launch_counts(self):
         """(fused launches that went to the context's stream, ... to its launch lanes)"""
         a, b = C.c_int64(), C.c_int64()
-        self.L.sl3d_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         self._chk(self.L.sl3d_launch_counts(self._h, C.byref(a), C.byref(b)), "sl3d_launch_counts")
         return a.value, b.value
 
@@ -613,12 +623,6 @@ class Scanner:
         self._chk(self.L.sl3d_synchronize(self._h), "sl3d_synchronize")
 
     # ---- outputs ------------------------------------------------------------------------------
-    def _plane(self, fn, dtype, view, *pre, comps=1):
-        shape = (self.H, self.W) if comps == 1 else (self.H, self.W, comps)
-        out = np.empty(shape, dtype=dtype)
-        self._chk(getattr(self.L, fn)(self._h, view, *pre, out.ctypes.data, self.W * comps), fn)
-        return out
-
     def valid_map(self, which=VALID_MERGED, view=0):
         return self._plane("sl3d_get_valid_map", np.uint8, view, which)
 
@@ -635,14 +639,10 @@ class Scanner:
         return self._plane("sl3d_get_debug_image", np.uint8, view, stage, axis)
 
     def c_p_map(self, view=0):
-        out = np.empty((self.H, self.W, 2), dtype=np.int64)
-        self._chk(self.L.sl3d_get_c_p_map(self._h, view, out.ctypes.data), "sl3d_get_c_p_map")
-        return out
+        return self._plane("sl3d_get_c_p_map", np.int64, view, comps=2, tail=())
 
     def intersection_points(self, view=0):
-        out = np.empty((self.H, self.W, 3), dtype=np.float64)
-        self._chk(self.L.sl3d_get_intersection_points(self._h, view, out.ctypes.data), "sl3d_get_intersection_points")
-        return out
+        return self._plane("sl3d_get_intersection_points", np.float64, view, comps=3, tail=())
 
     def residuals(self, view=0):
         """The reprojection residual (undistorted pixels, camera and projector together) of every pixel the last triangulate_subpixel
@@ -651,15 +651,7 @@ class Scanner:
 
     def correspondences_subpixel(self, view=0):
         """(H, W, 2) float64: the continuous projector coordinates (xs, ys) stage 5 rounds into c_p_map; NaN where either axis is invalid."""
-        out = np.empty((self.H, self.W, 2), dtype=np.float64)
-        self._chk(self.L.sl3d_get_correspondences_subpixel(self._h, view, out.ctypes.data, self.W), "sl3d_get_correspondences_subpixel")
-        return out
-
-    def points(self, view=0):
-        xyz = np.empty((self.H, self.W, 3), dtype=np.float32)
-        valid = np.empty((self.H, self.W), dtype=np.uint8)
-        self._chk(self.L.sl3d_get_points(self._h, view, xyz.ctypes.data, valid.ctypes.data), "sl3d_get_points")
-        return xyz, valid
+        return self._plane("sl3d_get_correspondences_subpixel", np.float64, view, comps=2, tail=(self.W,))
 
     def download_views(self, first_view, n_views, xyz, valid):
         """Dense results of views [first_view, first_view + n_views) into caller arrays (n, H, W, 3) f32 / (n, H, W) u8 (pinned
@@ -673,45 +665,26 @@ class Scanner:
                                               b.valid_pitch, self.W, self.H), "sl3d_download_2d")
         self.synchronize()
 
-    def cloud(self, view=0):
-        n = C.c_int64(0)
-        self._chk(self.L.sl3d_get_cloud(self._h, view, None, 0, C.byref(n)), "sl3d_get_cloud")
-        out = np.empty((n.value, 3), dtype=np.float32)
-        self._chk(self.L.sl3d_get_cloud(self._h, view, out.ctypes.data, n.value, C.byref(n)), "sl3d_get_cloud")
-        return out
-
     def compact_views(self, first_view, n_views):
         """Batched device compaction (three launches for all views); returns the per-view counts, clouds stay in HBM."""
-        counts = (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_compact_views(self._h, first_view, n_views, None, None, counts), "sl3d_compact_views")
-        return [int(c) for c in counts]
+        return self._counts("sl3d_compact_views", 1, first_view, n_views, None, None)[0]
 
     def clouds(self, first_view, n_views):
         """The compacted clouds of a batch of views as a list of (n_k, 3) float32 arrays."""
-        counts = (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_get_clouds(self._h, first_view, n_views, None, 0, counts), "sl3d_get_clouds")
-        total = sum(counts)
-        flat = np.empty((total, 3), dtype=np.float32)
-        self._chk(self.L.sl3d_get_clouds(self._h, first_view, n_views, flat.ctypes.data, total, counts), "sl3d_get_clouds")
-        return _cut(flat, counts)
+        (clouds,), _ = self._fill_views("sl3d_get_clouds", first_view, n_views, (), [_XYZ], n_counts=1)
+        return clouds
 
     def mesh_device(self, max_edge, first_view=0, n_views=1):
         """sl3d_mesh_views: the meshes of a batch of views left in HBM; returns (Mesh, vertex counts, face counts)."""
-        m, nv, nf = Mesh(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_mesh_views(self._h, first_view, n_views, float(max_edge), C.byref(m), nv, nf), "sl3d_mesh_views")
-        return m, [int(c) for c in nv], [int(c) for c in nf]
+        m = Mesh()
+        return (m, *self._counts("sl3d_mesh_views", 2, first_view, n_views, float(max_edge), C.byref(m)))
 
     def meshes(self, max_edge, first_view=0, n_views=1):
         """The meshes of a batch of views: a list of (xyz float32 (n, 3), faces int32 (m, 3)); xyz is the view's compacted cloud (the
         valid pixels in scan order), a face three indices into it.  Neighbouring valid pixels are connected unless an edge longer than
         max_edge (mm; float('inf'): no test) lies between them (include/sl3d.h: the exact definition)."""
-        nv, nf = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_get_meshes(self._h, first_view, n_views, float(max_edge), None, 0, None, 0, nv, nf), "sl3d_get_meshes")
-        tv, tf = sum(nv), sum(nf)
-        xyz, faces = np.empty((tv, 3), dtype=np.float32), np.empty((tf, 3), dtype=np.int32)
-        self._chk(self.L.sl3d_get_meshes(self._h, first_view, n_views, float(max_edge), xyz.ctypes.data, tv, faces.ctypes.data, tf, nv, nf),
-                  "sl3d_get_meshes")
-        return list(zip(_cut(xyz, nv), _cut(faces, nf)))
+        (xyz,), (faces,), _ = self._fill_views("sl3d_get_meshes", first_view, n_views, (float(max_edge),), [_XYZ], [_TRI], n_counts=2)
+        return list(zip(xyz, faces))
 
     def mesh(self, max_edge, view=0):
         """(xyz, faces) of one view (meshes)."""
@@ -720,20 +693,16 @@ class Scanner:
     def mesh_normals_device(self, max_edge, first_view=0, n_views=1):
         """sl3d_mesh_normals: the vertex normals of the meshes of a batch of views left in HBM; returns (device address, stride between
         the views in float triples, vertex counts)."""
-        dev, stride, nv = C.c_void_p(), C.c_size_t(), (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_mesh_normals(self._h, first_view, n_views, float(max_edge), C.byref(dev), C.byref(stride), nv), "sl3d_mesh_normals")
-        return dev.value, stride.value, [int(c) for c in nv]
+        dev, stride = C.c_void_p(), C.c_size_t()
+        counts = self._counts("sl3d_mesh_normals", 1, first_view, n_views, float(max_edge), C.byref(dev), C.byref(stride))
+        return (dev.value, stride.value, *counts)
 
     def meshes_normals(self, max_edge, first_view=0, n_views=1):
         """The vertex normals of meshes(max_edge, first_view, n_views): a list of (n_k, 3) float32 arrays, row i the unit normal of
         vertex i -- the normalised sum of the area-weighted normals of the faces around it, zero for a vertex in no face.  The
         orientation follows the faces; nothing is flipped towards the camera (include/sl3d.h: the exact definition)."""
-        nv = (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_get_mesh_normals(self._h, first_view, n_views, float(max_edge), None, 0, nv), "sl3d_get_mesh_normals")
-        tv = sum(nv)
-        flat = np.empty((tv, 3), dtype=np.float32)
-        self._chk(self.L.sl3d_get_mesh_normals(self._h, first_view, n_views, float(max_edge), flat.ctypes.data, tv, nv), "sl3d_get_mesh_normals")
-        return _cut(flat, nv)
+        (normals,), _ = self._fill_views("sl3d_get_mesh_normals", first_view, n_views, (float(max_edge),), [_XYZ], n_counts=1)
+        return normals
 
     def mesh_normals(self, max_edge, view=0):
         """(n, 3) float32 normals of the vertices of mesh(max_edge, view) (meshes_normals)."""
@@ -742,22 +711,16 @@ class Scanner:
     def mesh_components_device(self, max_edge, first_view=0, n_views=1):
         """sl3d_mesh_components: the component labels of the meshes of a batch of views left in HBM; returns (device address, stride
         between the views in labels, vertex counts, component counts)."""
-        dev, stride, nv, nc = C.c_void_p(), C.c_size_t(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_mesh_components(self._h, first_view, n_views, float(max_edge), C.byref(dev), C.byref(stride), nv, nc),
-                  "sl3d_mesh_components")
-        return dev.value, stride.value, [int(c) for c in nv], [int(c) for c in nc]
+        dev, stride = C.c_void_p(), C.c_size_t()
+        counts = self._counts("sl3d_mesh_components", 2, first_view, n_views, float(max_edge), C.byref(dev), C.byref(stride))
+        return (dev.value, stride.value, *counts)
 
     def meshes_components(self, max_edge, first_view=0, n_views=1):
         """The connected components of meshes(max_edge, first_view, n_views): a list of (n_k,) int32 arrays, entry i the smallest vertex
         id of the component of vertex i (two vertices are connected iff they share a face; a vertex in no face is a component of its
         own).  The roots are the i with labels[i] == i (include/sl3d.h: the exact definition)."""
-        nv, nc = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_get_mesh_components(self._h, first_view, n_views, float(max_edge), None, 0, nv, nc), "sl3d_get_mesh_components")
-        tv = sum(nv)
-        flat = np.empty(tv, dtype=np.int32)
-        self._chk(self.L.sl3d_get_mesh_components(self._h, first_view, n_views, float(max_edge), flat.ctypes.data, tv, nv, nc),
-                  "sl3d_get_mesh_components")
-        return _cut(flat, nv)
+        (labels,), _ = self._fill_views("sl3d_get_mesh_components", first_view, n_views, (float(max_edge),), [_IDS], n_counts=2)
+        return labels
 
     def mesh_components(self, max_edge, view=0):
         """(n,) int32 component labels of the vertices of mesh(max_edge, view) (meshes_components)."""
@@ -766,24 +729,17 @@ class Scanner:
     def mesh_filtered_device(self, max_edge, min_vertices, first_view=0, n_views=1):
         """sl3d_mesh_views_filtered: the filtered meshes of a batch of views left in HBM; returns (MeshFiltered, vertex counts, face
         counts)."""
-        m, nv, nf = MeshFiltered(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_mesh_views_filtered(self._h, first_view, n_views, float(max_edge), int(min_vertices), C.byref(m), nv, nf),
-                  "sl3d_mesh_views_filtered")
-        return m, [int(c) for c in nv], [int(c) for c in nf]
+        m = MeshFiltered()
+        return (m, *self._counts("sl3d_mesh_views_filtered", 2, first_view, n_views, float(max_edge), int(min_vertices), C.byref(m)))
 
     def meshes_filtered(self, max_edge, min_vertices, first_view=0, n_views=1):
         """meshes(max_edge, first_view, n_views) without the components of fewer than min_vertices vertices: a list of (xyz float32
         (n, 3), faces int32 (m, 3), vertex_ids int32 (n,)); the kept vertices in order, the original faces among them with the new ids,
         vertex_ids[i] the id new vertex i has in mesh() -- mesh_normals(...)[vertex_ids] and cloud_rgb()[1][vertex_ids] are the normals
         and colours of the filtered mesh (include/sl3d.h: the exact definition)."""
-        nv, nf = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        args = (self._h, first_view, n_views, float(max_edge), int(min_vertices))
-        self._chk(self.L.sl3d_get_meshes_filtered(*args, None, None, 0, None, 0, nv, nf), "sl3d_get_meshes_filtered")
-        tv, tf = sum(nv), sum(nf)
-        xyz, ids, faces = np.empty((tv, 3), dtype=np.float32), np.empty(tv, dtype=np.int32), np.empty((tf, 3), dtype=np.int32)
-        self._chk(self.L.sl3d_get_meshes_filtered(*args, xyz.ctypes.data, ids.ctypes.data, tv, faces.ctypes.data, tf, nv, nf),
-                  "sl3d_get_meshes_filtered")
-        return list(zip(_cut(xyz, nv), _cut(faces, nf), _cut(ids, nv)))
+        args = (float(max_edge), int(min_vertices))
+        (xyz, ids), (faces,), _ = self._fill_views("sl3d_get_meshes_filtered", first_view, n_views, args, [_XYZ, _IDS], [_TRI], n_counts=2)
+        return list(zip(xyz, faces, ids))
 
     def mesh_filtered(self, max_edge, min_vertices, view=0):
         """(xyz, faces, vertex_ids) of one view (meshes_filtered)."""
@@ -797,24 +753,18 @@ class Scanner:
     def mesh_smoothed_device(self, max_edge, first_view=0, n_views=1, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, normals=False):
         """sl3d_mesh_smooth: the smoothed vertices (and normals) of the meshes of a batch of views left in HBM; returns (MeshSmoothed,
         vertex counts)."""
-        m, nv = MeshSmoothed(), (C.c_int64 * n_views)()
+        m = MeshSmoothed()
         args = self._smooth_args(max_edge, iterations, lam, mu, fix_boundary, normals)
-        self._chk(self.L.sl3d_mesh_smooth(self._h, first_view, n_views, *args, C.byref(m), nv), "sl3d_mesh_smooth")
-        return m, [int(c) for c in nv]
+        return (m, *self._counts("sl3d_mesh_smooth", 1, first_view, n_views, *args, C.byref(m)))
 
     def meshes_smoothed(self, max_edge, first_view=0, n_views=1, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, normals=False):
         """The vertices of meshes(max_edge, first_view, n_views) after `iterations` Taubin iterations over the 1-ring (one step with lam,
         one with mu; mu = 0: plain Laplacian smoothing): a list of (n_k, 3) float32 arrays, or of (vertices, normals) pairs with
         normals=True -- the normals of the smoothed mesh.  Faces and vertex ids are those of meshes(); fix_boundary keeps the vertices of
         edges with one face where they are (include/sl3d.h: the exact definition)."""
-        nv = (C.c_int64 * n_views)()
-        args = (self._h, first_view, n_views) + self._smooth_args(max_edge, iterations, lam, mu, fix_boundary, normals)
-        self._chk(self.L.sl3d_get_mesh_smoothed(*args, None, None, 0, nv), "sl3d_get_mesh_smoothed")
-        tv = sum(nv)
-        xyz = np.empty((tv, 3), dtype=np.float32)
-        nrm = np.empty((tv, 3), dtype=np.float32) if normals else None
-        self._chk(self.L.sl3d_get_mesh_smoothed(*args, xyz.ctypes.data, nrm.ctypes.data if normals else None, tv, nv), "sl3d_get_mesh_smoothed")
-        return list(zip(_cut(xyz, nv), _cut(nrm, nv))) if normals else _cut(xyz, nv)
+        args = self._smooth_args(max_edge, iterations, lam, mu, fix_boundary, normals)
+        (xyz, nrm), _ = self._fill_views("sl3d_get_mesh_smoothed", first_view, n_views, args, [_XYZ, _XYZ if normals else None], n_counts=1)
+        return list(zip(xyz, nrm)) if normals else xyz
 
     def mesh_smoothed(self, max_edge, view=0, iterations=10, lam=0.5, mu=-0.53, fix_boundary=False, normals=False):
         """(n, 3) float32 smoothed vertices of mesh(max_edge, view), or (vertices, normals) with normals=True (meshes_smoothed)."""
@@ -828,10 +778,9 @@ class Scanner:
     def mesh_lod_device(self, step, lod_edge, first_view=0, n_views=1, max_edge=float("inf"), min_vertices=1, mean=False, normals=False):
         """sl3d_mesh_views_lod: the level-of-detail meshes of a batch of views left in HBM; returns (MeshLod, vertex counts, face
         counts)."""
-        m, nv, nf = MeshLod(), (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
+        m = MeshLod()
         args = self._lod_args(step, max_edge, min_vertices, lod_edge, mean, normals)
-        self._chk(self.L.sl3d_mesh_views_lod(self._h, first_view, n_views, *args, C.byref(m), nv, nf), "sl3d_mesh_views_lod")
-        return m, [int(c) for c in nv], [int(c) for c in nf]
+        return (m, *self._counts("sl3d_mesh_views_lod", 2, first_view, n_views, *args, C.byref(m)))
 
     def meshes_lod(self, step, lod_edge, first_view=0, n_views=1, max_edge=float("inf"), min_vertices=1, mean=False, normals=False):
         """One vertex per step x step pixel block of every view, meshed over the coarse grid with the cell rules of meshes() and
@@ -840,16 +789,10 @@ class Scanner:
         meshes_filtered(max_edge, min_vertices), all valid pixels for min_vertices = 1 --, with mean=True the mean of the block's
         candidates within lod_edge of it.  vertex_ids[i] is the id the representative has in cloud() / mesh(): cloud_rgb()[1][vertex_ids]
         and mesh_smoothed(...)[vertex_ids] are the colours and the smoothed positions (include/sl3d.h: the exact definition)."""
-        nv, nf = (C.c_int64 * n_views)(), (C.c_int64 * n_views)()
-        args = (self._h, first_view, n_views) + self._lod_args(step, max_edge, min_vertices, lod_edge, mean, normals)
-        self._chk(self.L.sl3d_get_meshes_lod(*args, None, None, None, 0, None, 0, nv, nf), "sl3d_get_meshes_lod")
-        tv, tf = sum(nv), sum(nf)
-        xyz, ids, faces = np.empty((tv, 3), dtype=np.float32), np.empty(tv, dtype=np.int32), np.empty((tf, 3), dtype=np.int32)
-        nrm = np.empty((tv, 3), dtype=np.float32) if normals else None
-        self._chk(self.L.sl3d_get_meshes_lod(*args, xyz.ctypes.data, ids.ctypes.data, nrm.ctypes.data if normals else None, tv, faces.ctypes.data,
-                                             tf, nv, nf), "sl3d_get_meshes_lod")
-        out = [_cut(xyz, nv), _cut(faces, nf), _cut(ids, nv)] + ([_cut(nrm, nv)] if normals else [])
-        return list(zip(*out))
+        args = self._lod_args(step, max_edge, min_vertices, lod_edge, mean, normals)
+        (xyz, ids, nrm), (faces,), _ = self._fill_views("sl3d_get_meshes_lod", first_view, n_views, args,
+                                                        [_XYZ, _IDS, _XYZ if normals else None], [_TRI], n_counts=2)
+        return list(zip(xyz, faces, ids, *([nrm] if normals else [])))
 
     def mesh_lod(self, step, lod_edge, view=0, max_edge=float("inf"), min_vertices=1, mean=False, normals=False):
         """(xyz, faces, vertex_ids) of one view, with normals=True (xyz, faces, vertex_ids, normals) (meshes_lod)."""
@@ -863,10 +806,8 @@ class Scanner:
         """sl3d_mesh_fill_holes: the hole-filled meshes of a batch of views left in HBM; returns (MeshHoles, vertex counts, face
         counts, hole counts, filled-pixel counts)."""
         m = MeshHoles()
-        nv, nf, nh, nfl = ((C.c_int64 * n_views)() for _ in range(4))
         args = self._fill_args(max_edge, min_vertices, max_hole, fill_edge, normals)
-        self._chk(self.L.sl3d_mesh_fill_holes(self._h, first_view, n_views, *args, C.byref(m), nv, nf, nh, nfl), "sl3d_mesh_fill_holes")
-        return m, [int(c) for c in nv], [int(c) for c in nf], [int(c) for c in nh], [int(c) for c in nfl]
+        return (m, *self._counts("sl3d_mesh_fill_holes", 4, first_view, n_views, *args, C.byref(m)))
 
     def meshes_fill_holes(self, max_hole, fill_edge, first_view=0, n_views=1, max_edge=float("inf"), min_vertices=1, normals=False, stats=False):
         """The meshes of every view with their small interior holes filled: a list of (xyz float32 (n, 3), faces int32 (m, 3),
@@ -876,15 +817,10 @@ class Scanner:
         pixel is interpolated between the nearest candidates of its row and of its column; a span whose mean sample spacing exceeds
         fill_edge is not used, so a depth step is not bridged.  vertex_ids[i] is the id the vertex has in cloud() / mesh(), -1 for a
         filled vertex (include/sl3d.h: the exact definition)."""
-        nv, nf, nh, nfl = ((C.c_int64 * n_views)() for _ in range(4))
-        args = (self._h, first_view, n_views) + self._fill_args(max_edge, min_vertices, max_hole, fill_edge, normals)
-        self._chk(self.L.sl3d_get_meshes_holes_filled(*args, None, None, None, 0, None, 0, nv, nf, nh, nfl), "sl3d_get_meshes_holes_filled")
-        tv, tf = sum(nv), sum(nf)
-        xyz, ids, faces = np.empty((tv, 3), dtype=np.float32), np.empty(tv, dtype=np.int32), np.empty((tf, 3), dtype=np.int32)
-        nrm = np.empty((tv, 3), dtype=np.float32) if normals else None
-        self._chk(self.L.sl3d_get_meshes_holes_filled(*args, xyz.ctypes.data, ids.ctypes.data, nrm.ctypes.data if normals else None, tv,
-                                                      faces.ctypes.data, tf, nv, nf, nh, nfl), "sl3d_get_meshes_holes_filled")
-        out = [_cut(xyz, nv), _cut(faces, nf), _cut(ids, nv)] + ([_cut(nrm, nv)] if normals else [])
+        args = self._fill_args(max_edge, min_vertices, max_hole, fill_edge, normals)
+        (xyz, ids, nrm), (faces,), (_, _, nh, nfl) = self._fill_views("sl3d_get_meshes_holes_filled", first_view, n_views, args,
+                                                                      [_XYZ, _IDS, _XYZ if normals else None], [_TRI], n_counts=4)
+        out = [xyz, faces, ids] + ([nrm] if normals else [])
         if stats:
             out.append([(int(a), int(b)) for a, b in zip(nh, nfl)])
         return list(zip(*out))
@@ -902,21 +838,11 @@ class Scanner:
 
     def cloud_rgb(self, view=0):
         """(n,3) float32 xyz and (n,3) uint8 r,g,b of the valid pixels in the reference's scan order."""
-        n = C.c_int64(0)
-        self._chk(self.L.sl3d_get_cloud_rgb(self._h, view, None, None, 0, C.byref(n)), "sl3d_get_cloud_rgb")
-        xyz = np.empty((n.value, 3), dtype=np.float32)
-        rgb = np.empty((n.value, 3), dtype=np.uint8)
-        self._chk(self.L.sl3d_get_cloud_rgb(self._h, view, xyz.ctypes.data, rgb.ctypes.data, n.value, C.byref(n)), "sl3d_get_cloud_rgb")
-        return xyz, rgb
+        return tuple(self._fill("sl3d_get_cloud_rgb", (view,), _XYZ, _RGB))
 
     def register_views(self, first_view, n_views, tx, ty, tz, rot_step):
         """register_point_clouds(): rotate view k by k*rot_step degrees about Y through (tx,ty,tz), concatenate."""
-        n = C.c_int64(0)
-        self._chk(self.L.sl3d_register_views(self._h, first_view, n_views, tx, ty, tz, rot_step, None, 0, C.byref(n)), "sl3d_register_views")
-        out = np.empty((n.value, 3), dtype=np.float32)
-        self._chk(self.L.sl3d_register_views(self._h, first_view, n_views, tx, ty, tz, rot_step, out.ctypes.data, n.value, C.byref(n)),
-                  "sl3d_register_views")
-        return out
+        return self._fill("sl3d_register_views", (first_view, n_views, tx, ty, tz, rot_step), _XYZ)[0]
 
     def pinned(self, shape, dtype):
         """numpy array in pinned host memory (sl3d_host_alloc); freed when the Scanner is closed."""
@@ -930,15 +856,7 @@ class Scanner:
 
     def process_views(self, frames, xyz=None, valid=None):
         """frames: (n_views, planes_per_view, H, W) uint8 host array (pinned for full overlap); returns (xyz, valid)."""
-        n, ppv, H, W = frames.shape
-        assert (H, W) == (self.H, self.W) and frames.dtype == np.uint8 and frames.strides[3] == 1 and frames.strides[2] >= W
-        if xyz is None:
-            xyz = np.empty((n, H, W, 3), dtype=np.float32)
-        if valid is None:
-            valid = np.empty((n, H, W), dtype=np.uint8)
-        ptrs = (C.c_void_p * (n * ppv))(*[frames[v, p].ctypes.data for v in range(n) for p in range(ppv)])
-        self._chk(self.L.sl3d_process_views(self._h, n, ptrs, frames.strides[2], xyz.ctypes.data, valid.ctypes.data), "sl3d_process_views")
-        return xyz, valid
+        return self._process_views(frames, xyz, valid)
 
     def undistort(self, image, K, dist):
         """cvUndistort2 on an (H, W) or (H, W, 3) uint8 image (any size), on the device."""
@@ -969,9 +887,10 @@ class Scanner:
         return b
 
 
-class Group:
+class Group(_Handle):
     """sl3d_group_*: n row stripes of one frame window, stripe i on HIP device devices[i], assembled on stripe 0's GPU
     (RCCL send/recv between GPUs, device copies inside one)."""
+    _prefix = "sl3d_group_"
 
     def __init__(self, width, height, proj_width, proj_height, n_gray_v, n_gray_h, fringe_width_v, fringe_width_h, devices,
                  n_fringe=3, max_views=1, full_size=None, origin=(0, 0), flags=0):
@@ -986,27 +905,6 @@ class Group:
         if rc != 0:
             raise Sl3dError(f"sl3d_group_create: {self.L.sl3d_strerror(rc).decode()}: {self.L.sl3d_group_last_error(None).decode()}")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.sl3d_group_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise Sl3dError(f"{what}: {self.L.sl3d_strerror(rc).decode()}: {self.L.sl3d_group_last_error(self._h).decode()}")
-
     @property
     def transport(self):
         return self.L.sl3d_group_transport(self._h).decode()
@@ -1020,33 +918,11 @@ class Group:
             out.append((r0.value, n.value, d.value, h))
         return out
 
-    def set_calibration(self, Kc, dc, rc, tc, Kp, dp, rp, tp):
-        a = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel()) for v in (Kc, dc, rc, tc, Kp, dp, rp, tp)]
-        self._chk(self.L.sl3d_group_set_calibration(self._h, *[v.ctypes.data for v in a]), "sl3d_group_set_calibration")
-
-    def set_mask(self, full_frame_mask, view=0):
-        m = np.ascontiguousarray(full_frame_mask, dtype=np.uint8)
-        assert m.shape == (self.cfg.full_height, self.cfg.full_width), m.shape
-        self._chk(self.L.sl3d_group_set_mask(self._h, view, m.ctypes.data, m.strides[0]), "sl3d_group_set_mask")
-
-    def set_frames(self, axis, planes, view=0):
-        arrs = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
-        for a in arrs:
-            assert a.shape == (self.H, self.W), a.shape
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-        self._chk(self.L.sl3d_group_set_frames(self._h, view, axis, ptrs, len(arrs), arrs[0].strides[0]), "sl3d_group_set_frames")
-
     def run(self, first_view=0, n_views=1):
         self._chk(self.L.sl3d_group_run(self._h, first_view, n_views), "sl3d_group_run")
 
     def gather(self, first_view=0, n_views=1):
         self._chk(self.L.sl3d_group_gather(self._h, first_view, n_views), "sl3d_group_gather")
-
-    def points(self, view=0):
-        xyz = np.empty((self.H, self.W, 3), dtype=np.float32)
-        valid = np.empty((self.H, self.W), dtype=np.uint8)
-        self._chk(self.L.sl3d_group_get_points(self._h, view, xyz.ctypes.data, valid.ctypes.data), "sl3d_group_get_points")
-        return xyz, valid
 
     def download_points(self, first_view=0, n_views=1, xyz=None, valid=None):
         """Every stripe's rows straight into the caller's dense host images (no gather to the root): (n, H, W, 3) f32, (n, H, W) u8."""
@@ -1060,30 +936,13 @@ class Group:
 
     def process_views(self, frames, xyz=None, valid=None):
         """frames: (n_views, planes_per_view, H, W) uint8 host array (pinned for concurrent DMA); returns (xyz, valid) dense images."""
-        n, ppv, H, W = frames.shape
-        assert (H, W) == (self.H, self.W) and frames.dtype == np.uint8 and frames.strides[3] == 1 and frames.strides[2] >= W
-        if xyz is None:
-            xyz = np.empty((n, H, W, 3), dtype=np.float32)
-        if valid is None:
-            valid = np.empty((n, H, W), dtype=np.uint8)
-        ptrs = (C.c_void_p * (n * ppv))(*[frames[v, p].ctypes.data for v in range(n) for p in range(ppv)])
-        self._chk(self.L.sl3d_group_process_views(self._h, n, ptrs, frames.strides[2], xyz.ctypes.data, valid.ctypes.data), "sl3d_group_process_views")
-        return xyz, valid
+        return self._process_views(frames, xyz, valid)
 
     def run_clouds(self, first_view=0, n_views=1):
         self._chk(self.L.sl3d_group_run_clouds(self._h, first_view, n_views), "sl3d_group_run_clouds")
 
     def gather_clouds(self, first_view=0, n_views=1):
-        counts = (C.c_int64 * n_views)()
-        self._chk(self.L.sl3d_group_gather_clouds(self._h, first_view, n_views, counts), "sl3d_group_gather_clouds")
-        return [int(c) for c in counts]
-
-    def cloud(self, view=0):
-        n = C.c_int64(0)
-        self._chk(self.L.sl3d_group_get_cloud(self._h, view, None, 0, C.byref(n)), "sl3d_group_get_cloud")
-        out = np.empty((n.value, 3), dtype=np.float32)
-        self._chk(self.L.sl3d_group_get_cloud(self._h, view, out.ctypes.data, n.value, C.byref(n)), "sl3d_group_get_cloud")
-        return out
+        return self._counts("sl3d_group_gather_clouds", 1, first_view, n_views)[0]
 
     def synchronize(self):
         self._chk(self.L.sl3d_group_synchronize(self._h), "sl3d_group_synchronize")
