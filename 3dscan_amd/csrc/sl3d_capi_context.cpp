@@ -112,6 +112,7 @@ try {
     } unwind{x};
     x->cfg = c;
     x->keep = (c.flags & SL3D_FLAG_KEEP_STAGES) != 0;
+    x->subpixel = (c.flags & SL3D_FLAG_SUBPIXEL) != 0;
 #define CREATE_CHK(call)                                                                 \
     do {                                                                                 \
         hipError_t e_ = (call);                                                          \
@@ -132,7 +133,8 @@ try {
     CREATE_CHK(hipEventCreate(&x->ev1));
     // (launch lanes: only beside a stream nobody else can see, never in the parity mode; SL3D_NO_LAUNCH_LANES=1 in the environment
     // switches them off for a whole process -- A/B measurements of programs that cannot pass the flag)
-    x->lanes_ok = x->own_stream && !(c.flags & (SL3D_FLAG_SERIAL_LAUNCHES | SL3D_FLAG_KEEP_STAGES)) && !getenv("SL3D_NO_LAUNCH_LANES");
+    // (nor on a SL3D_FLAG_SUBPIXEL context: its one launch per call stays on the context's stream)
+    x->lanes_ok = x->own_stream && !(c.flags & (SL3D_FLAG_SERIAL_LAUNCHES | SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL)) && !getenv("SL3D_NO_LAUNCH_LANES");
 
     KParams &P = x->P;
     P.W = c.width; P.H = c.height; P.fullW = c.full_width; P.fullH = c.full_height;
@@ -203,6 +205,10 @@ try {
     CREATE_CHK(hipMemsetAsync(x->d_points, 0, V * P.px_view_stride * 3 * sizeof(float), x->stream));
     CREATE_CHK(hipMemsetAsync(x->d_band, 0, V * P.px_view_stride, x->stream));
     P.frames = x->d_frames; P.mask = x->d_mask; P.points = x->d_points; P.valid = x->d_valid; P.band = x->d_band;
+    if (x->subpixel) {  // the residual plane of sl3d_run, NaN everywhere: the views no call has run over yet (as sl3d_triangulate_subpixel leaves them)
+        ALLOC(x->d_residual, V * P.px_view_stride);
+        CREATE_CHK(hipMemsetAsync(x->d_residual, 0xff, V * P.px_view_stride * sizeof(float), x->stream));
+    }
     {
         // one-time (per process and device) proof that the device atan2 reproduces the host libm bit for bit
         static std::mutex mu;

@@ -114,6 +114,10 @@ inline int download_plane(sl3d_ctx *x, const T *src, int comps, T *out, size_t o
 }
 
 // every fused launch of the library (sl3d_capi_run.cpp)
+// THE routing decision of a SL3D_FLAG_SUBPIXEL context: does a dense launch of this context go out as k_subpixel_fused instead of a
+// k_fused instantiation?  (With SL3D_FLAG_KEEP_STAGES it stays the parity kernel, and k_subpixel follows it.)  run_fused launches by it,
+// sl3d_fused_kernel_name, sl3d_last_fused_kernel_name and sl3d_camera_table_bytes_per_pixel report by it
+inline bool subpixel_fused_route(const sl3d_ctx *x) { return x->subpixel && !x->keep; }
 SL3D_INTERNAL bool maskin_launch(const sl3d_ctx *x, int first_view, int n_views, bool keep);
 SL3D_INTERNAL int small_launch_overlaps(sl3d_ctx *x, int first_view, int n_views, bool *overlap);
 SL3D_INTERNAL int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap = false);

@@ -131,10 +131,31 @@ int small_launch_overlaps(sl3d_ctx *x, int first_view, int n_views, bool *overla
     return *overlap ? SL3D_OK : lanes_wait(x);
 }
 
-// every fused launch of the library goes through here: the kernel is chosen by what is known about the views' masks NOW, and
-// launch_fused records the instantiation that ran (sl3d_last_fused_kernel_name reports it, not a later prediction)
-// may_overlap: the caller (sl3d_run, sl3d_run_clouds) took the QUIET form of ON_DEVICE for a small launch on a context with lanes
+static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap);
+
+// every fused launch of the library goes through here.  A SL3D_FLAG_SUBPIXEL context (subpixel_fused_route): the timed one launches k_subpixel_fused on the context's stream, behind the
+// preparation of whatever masks of the views are still deferred; the parity one launches what it always does and k_subpixel
+// (+infinity, no counts) behind it.  Either way sl3d_run leaves the same scan.
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
+{
+    if (!x->subpixel) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
+    int rc;
+    if (subpixel_fused_route(x)) {
+        if ((rc = flush_masks(x, first_view, n_views))) return rc;
+        x->launches_on_stream++;
+        rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->stream));
+    } else {
+        if ((rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap))) return rc;
+        rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->stream));
+    }
+    if (!rc) x->residual_ready = true;
+    return rc;
+}
+
+// every k_fused launch: the kernel is chosen by what is known about the views' masks NOW, and launch_fused records the instantiation
+// that ran (sl3d_last_fused_kernel_name reports it, not a later prediction)
+// may_overlap: the caller (sl3d_run, sl3d_run_clouds) took the QUIET form of ON_DEVICE for a small launch on a context with lanes
+static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
     const bool prefer_gated = sparse_views(x, first_view, n_views);
     const bool maskin = maskin_launch(x, first_view, n_views, keep);
@@ -200,8 +221,9 @@ extern "C" int sl3d_launch_counts(sl3d_ctx *x, int64_t *on_stream, int64_t *on_l
 extern "C" int sl3d_last_fused_kernel_name(sl3d_ctx *x, char *buf, size_t capacity)
 try {
     if (!x || !buf || capacity == 0) return fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: null argument");
-    if (x->last_fused.nmax == 0) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
-    const int n = fused_key_name(x->last_fused, buf, capacity);
+    const bool sub = subpixel_fused_route(x);  // (every launch of such a context is k_subpixel_fused)
+    if (sub ? !x->residual_ready : x->last_fused.nmax == 0) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
+    const int n = sub ? snprintf(buf, capacity, "%s", SL3D_SUBPIXEL_FUSED_NAME) : fused_key_name(x->last_fused, buf, capacity);
     return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: buffer too small");
 }
 SL3D_CATCH(x)
@@ -226,6 +248,11 @@ extern "C" int sl3d_fused_kernel_name(sl3d_ctx *x, int n_views, int clouds, char
 try {
     if (!x || !buf || capacity == 0 || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: null argument");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called (the rig class is part of the name)");
+    if (subpixel_fused_route(x)) {
+        if (clouds) return fail(x, SL3D_E_UNSUPPORTED, "fused_kernel_name: a SL3D_FLAG_SUBPIXEL context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)");
+        const int n = snprintf(buf, capacity, "%s", SL3D_SUBPIXEL_FUSED_NAME);
+        return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: buffer too small");
+    }
     const bool fits = n_views <= x->cfg.max_views, gated = fits && sparse_views(x, 0, n_views);
     const int n = fused_key_name(fused_choice(x->P, x->rig, n_views, x->keep, clouds ? 2 : 0, gated, fits && maskin_launch(x, 0, n_views, x->keep)), buf, capacity);
     return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: buffer too small");
@@ -236,7 +263,7 @@ extern "C" int sl3d_camera_table_bytes_per_pixel(sl3d_ctx *x, int n_views)
 try {
     if (!x || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "camera_table_bytes_per_pixel: null context or no views");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called");
-    if (!x->P.cam_tab) return 0;
+    if (!x->P.cam_tab || subpixel_fused_route(x)) return 0;  // (k_subpixel_fused iterates the camera's undistortion itself)
     if (x->P.cam_tab_kind == 2) return 16;
     (void)n_views;
     return 8;

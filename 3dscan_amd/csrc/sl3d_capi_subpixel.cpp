@@ -32,6 +32,7 @@ try {
     unsigned *cnt = x->d_subpixel_counts;
     int rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, max_residual, x->d_residual, counts ? x->d_subpixel_partials : nullptr, cnt, x->stream));
     if (rc) return rc;
+    x->residual_ready = true;
     if (counts) {
         HIPCHK(x, hipMemcpyAsync(counts, cnt, 2 * (size_t)n_views * sizeof(unsigned), hipMemcpyDeviceToHost, x->stream));
         SYNC_FOR_CALLER(x);
@@ -45,7 +46,10 @@ try {
     int rc = check_view(x, view);
     if (rc) return rc;
     if (!out) return fail(x, SL3D_E_INVALID_ARG, "null output");
-    if (!x->d_residual) return fail(x, SL3D_E_STATE, "no residuals: sl3d_triangulate_subpixel has not been called");
+    if (!x->d_residual || !x->residual_ready)
+        return fail(x, SL3D_E_STATE, subpixel_fused_route(x) ? "no residuals: sl3d_run has not been called on this SL3D_FLAG_SUBPIXEL context"
+                                     : x->subpixel         ? "no residuals: neither sl3d_run nor sl3d_triangulate_subpixel has been called"
+                                                           : "no residuals: sl3d_triangulate_subpixel has not been called");
     return download_plane(x, x->d_residual + (size_t)view * x->P.px_view_stride, 1, out, stride);
 }
 SL3D_CATCH(x)

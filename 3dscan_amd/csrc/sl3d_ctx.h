@@ -20,6 +20,8 @@ struct sl3d_ctx {
     bool have_cal = false;
     int rig = 0;
     bool keep = false;
+    // SL3D_FLAG_SUBPIXEL: sl3d_run leaves the sub-pixel scan.  Which launch that takes is subpixel_fused_route (sl3d_capi_internal.h)
+    bool subpixel = false;
     bool own_stream = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -149,8 +151,10 @@ struct sl3d_ctx {
     unsigned *d_period_counts = nullptr;
     // sl3d_triangulate_subpixel (allocated on first use): the residual plane [max_views][px_view_stride]; for a caller that wants the
     // counts a word per block of the launch and [max_views][2] words, the triangulated and the rejected pixels of the call's views;
-    // sl3d_get_correspondences_subpixel: (xs, ys) of one view
+    // sl3d_get_correspondences_subpixel: (xs, ys) of one view.  A SL3D_FLAG_SUBPIXEL context allocates the residual plane when it is
+    // created; residual_ready: a call has written residuals (sl3d_get_residuals refuses before)
     float *d_residual = nullptr;
+    bool residual_ready = false;
     unsigned *d_subpixel_partials = nullptr, *d_subpixel_counts = nullptr;
     double *d_subpixel_xy = nullptr;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set

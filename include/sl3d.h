@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.15.0"
+#define SL3D_VERSION_STRING "0.16.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -78,7 +78,22 @@ enum sl3d_flags {
      * a view a lane still works on goes behind it); every other call first makes the context's stream wait for both, so nothing a
      * caller can observe changes -- only the time: one view per launch from HBM, back to back, 25.8 -> 21.8 us per launch.  With this
      * flag every launch goes to the context's one stream (the behaviour up to 0.5; A/B measurements, and the time of a LONE launch). */
-    SL3D_FLAG_SERIAL_LAUNCHES = 64u
+    SL3D_FLAG_SERIAL_LAUNCHES = 64u,
+    /* (0.16.0) sl3d_run() -- and with it sl3d_run_timed, sl3d_process_views and the group calls built on them -- leaves the SUB-PIXEL
+     * scan: after sl3d_run(ctx, first_view, n_views) the points and valid planes of those views and the residual plane hold, bit for
+     * bit, what sl3d_compute_wrapped_phase + sl3d_unwrap_phase of both axes, sl3d_compute_c_p_map and sl3d_triangulate_subpixel(
+     * first_view, n_views, +infinity, NULL) leave on a KEEP_STAGES context with the same configuration, calibration, masks and frames
+     * (steps 1-4 and 6 at sl3d_triangulate_subpixel; nothing is rejected by the residual -- sl3d_get_residuals hands the plane out for
+     * the caller to threshold).  May be combined with every other flag.
+     *   Without KEEP_STAGES: ONE launch of a kernel of its own (k_subpixel_fused: frames in; points, valid and residuals out; no stage
+     *   plane in between) on the context's stream -- such a context has no launch lanes -- behind the preparation of whatever masks
+     *   of the views are still deferred.  sl3d_run_clouds has no sub-pixel form: SL3D_E_UNSUPPORTED (sl3d_run + sl3d_compact_views).
+     *   The per-stage calls, sl3d_triangulate_subpixel and sl3d_get_correspondences_subpixel stay SL3D_E_STATE as on every timed context.
+     *   With KEEP_STAGES: sl3d_run() launches what it always does (all stage planes, c_p_map) and sl3d_triangulate_subpixel's kernel
+     *   behind it; sl3d_compute_c_p_map + sl3d_triangulate restores the integer result.
+     * Every consumer of the dense planes (getters, compactions, colour, registration, meshes) sees the sub-pixel scan.  sl3d_group_create
+     * hands the flag to its stripes.  A context without the flag behaves exactly as before. */
+    SL3D_FLAG_SUBPIXEL = 128u
     /* (8u was SL3D_FLAG_CLOUDS_LOOKBACK until 0.3: contiguous clouds in one pass by a decoupled look-back between tiles.  Removed
      * in 0.4 -- every tile waited for its predecessors, 0.53 of the roofline against 0.67 for the segmented clouds; a consumer
      * that wants one contiguous device array asks sl3d_get_cloud_counts for it.) */
@@ -267,7 +282,7 @@ int sl3d_triangulate(sl3d_ctx *ctx, int view);
  * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes.  A refused call changes nothing. */
 int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t counts[2]);
 
-/* ---- sub-pixel triangulation with a reprojection residual (0.15.0; needs SL3D_FLAG_KEEP_STAGES) -------------------------------------
+/* ---- sub-pixel triangulation with a reprojection residual (0.15.0; needs SL3D_FLAG_KEEP_STAGES -- the timed mode has it as SL3D_FLAG_SUBPIXEL) --
  * Stage 5 rounds every projector coordinate to an integer (lrint, 5/compute_correspondance.cpp:648,659) before stage 7 triangulates
  * from it: up to half a projector pixel per axis, which shows as depth terraces in every surface built on the scan.  This call is an
  * alternative to sl3d_triangulate, after sl3d_compute_c_p_map, that triangulates from the doubles lrint was handed instead.  c_p_map
@@ -295,7 +310,9 @@ int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t 
  * SL3D_FLAG_KEEP_STAGES or before sl3d_set_calibration.  A refused call changes nothing. */
 int sl3d_triangulate_subpixel(sl3d_ctx *ctx, int first_view, int n_views, double max_residual, uint32_t *counts);
 /* The residual plane of a view, out[row * stride_elems + col]: NaN on every pixel the last sl3d_triangulate_subpixel over the view did
- * not triangulate (and on a view none has run over).  SL3D_E_STATE before the context's first sl3d_triangulate_subpixel. */
+ * not triangulate (and on a view none has run over).  SL3D_E_STATE before the context's first sl3d_triangulate_subpixel.
+ * On a SL3D_FLAG_SUBPIXEL context sl3d_run writes the plane too (it exists from sl3d_create on): SL3D_E_STATE before the first sl3d_run
+ * (with KEEP_STAGES: before the first sl3d_run or sl3d_triangulate_subpixel), the text names the missing call. */
 int sl3d_get_residuals(sl3d_ctx *ctx, int view, float *out, size_t stride_elems);
 /* (xs, ys) of step 1 for every window pixel, xy[(row * stride_elems + col) * 2 + {0, 1}], bit for bit those expressions; NaN where
  * either per-axis valid byte is not 1 (the pixels stage 5 does not form them for).  Computed from the stage-4 planes as they are: no
@@ -305,12 +322,15 @@ int sl3d_get_correspondences_subpixel(sl3d_ctx *ctx, int view, double *xy, size_
 /* ---- the fused hot path ------------------------------------------------------------------- */
 /* Stages 3(v) 3(h) 4(v) 4(h) 5 7 in main()'s order (m_tech_project_console.cpp:372-395) plus the
  * float cast of 8/save_point_cloud.cpp:100-102, for views [first_view, first_view+n_views), as ONE
- * kernel launch that reads every frame byte once and writes xyz (f32) + valid (u8). Asynchronous. */
+ * kernel launch that reads every frame byte once and writes xyz (f32) + valid (u8). Asynchronous.
+ * On a SL3D_FLAG_SUBPIXEL context: the sub-pixel scan and its residual plane instead (see the flag) -- still one launch per call
+ * without KEEP_STAGES, the parity launch + sl3d_triangulate_subpixel's with it. */
 int sl3d_run(sl3d_ctx *ctx, int first_view, int n_views);
 /* The same pass with the compaction of 8/save_point_cloud.cpp:33-37,85-104 INSIDE the kernel: instead of the dense xyz plane every
  * view's valid points are written once, compacted in the reference's row-major scan order, plus the valid map:
  * ~47 + 12*valid_fraction + 1 bytes per pixel instead of 60 for the dense pass + 25 for a separate compaction.  Timed mode only
- * (no SL3D_FLAG_KEEP_STAGES).  Asynchronous.
+ * (no SL3D_FLAG_KEEP_STAGES), and the integer scan only: SL3D_E_UNSUPPORTED on a SL3D_FLAG_SUBPIXEL context, nothing changed (sl3d_run +
+ * sl3d_compact_views give its clouds).  Asynchronous.
  *   SEGMENTED clouds.  Every wave of the kernel compacts the 256 consecutive scan pixels it owns into its own fixed slot
  *   (points [256*s, 256*s + count_s) of the view's region) and stores count_s.  The counts become offsets by a small scan kernel
  *   right behind a launch of more than 4 views; a launch of up to 4 views -- the reference's one scan per call -- leaves the scan
@@ -353,7 +373,9 @@ int sl3d_register_clouds(sl3d_ctx *ctx, int first_view, int n_views, float tx, f
                          int64_t *total);
 /* Name of the fused-kernel instantiation sl3d_run (clouds = 0) / sl3d_run_clouds (clouds = 1) launches for a batch of n_views views
  * with this context's configuration and calibration, spelled as rocprofv3 --kernel-trace prints it: benchmarks name the kernel
- * their roofline figure is about without restating the library's dispatch rules. */
+ * their roofline figure is about without restating the library's dispatch rules.  On a SL3D_FLAG_SUBPIXEL context without KEEP_STAGES
+ * this, and sl3d_last_fused_kernel_name after the first sl3d_run, is "sl3d::k_subpixel_fused" (clouds = 1: SL3D_E_UNSUPPORTED), and
+ * sl3d_camera_table_bytes_per_pixel is 0: that kernel reads no table. */
 int sl3d_fused_kernel_name(sl3d_ctx *ctx, int n_views, int clouds, char *buf, size_t capacity);
 /* The instantiation the LAST fused launch of this context ran (sl3d_run, sl3d_run_clouds, sl3d_run_timed, sl3d_process_views): the
  * choice is recorded when the launch is made -- it depends on what was known about the views' masks at that moment (a small
