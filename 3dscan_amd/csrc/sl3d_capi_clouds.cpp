@@ -56,6 +56,7 @@ try {
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called");
     if (x->keep) return fail(x, SL3D_E_STATE, "sl3d_run_clouds is the timed mode: create the context without SL3D_FLAG_KEEP_STAGES");
     if (x->subpixel) return fail(x, SL3D_E_UNSUPPORTED, "sl3d_run_clouds has no sub-pixel form (SL3D_FLAG_SUBPIXEL): use sl3d_run + sl3d_compact_views");
+    if (x->repair) return fail(x, SL3D_E_UNSUPPORTED, "sl3d_run_clouds has no period-repaired form (SL3D_FLAG_REPAIR_PERIODS): use sl3d_run + sl3d_compact_views");
     ON_DEVICE_QUIET(x);
     // (a small launch goes beside the one before it, sl3d_ctx.h: launch lanes -- once the cloud buffers exist; its consumers join)
     bool overlap = false;

@@ -113,6 +113,7 @@ try {
     x->cfg = c;
     x->keep = (c.flags & SL3D_FLAG_KEEP_STAGES) != 0;
     x->subpixel = (c.flags & SL3D_FLAG_SUBPIXEL) != 0;
+    x->repair = (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0;
 #define CREATE_CHK(call)                                                                 \
     do {                                                                                 \
         hipError_t e_ = (call);                                                          \
@@ -133,8 +134,9 @@ try {
     CREATE_CHK(hipEventCreate(&x->ev1));
     // (launch lanes: only beside a stream nobody else can see, never in the parity mode; SL3D_NO_LAUNCH_LANES=1 in the environment
     // switches them off for a whole process -- A/B measurements of programs that cannot pass the flag)
-    // (nor on a SL3D_FLAG_SUBPIXEL context: its one launch per call stays on the context's stream)
-    x->lanes_ok = x->own_stream && !(c.flags & (SL3D_FLAG_SERIAL_LAUNCHES | SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL)) && !getenv("SL3D_NO_LAUNCH_LANES");
+    // (nor on a SL3D_FLAG_SUBPIXEL or SL3D_FLAG_REPAIR_PERIODS context: its one launch per call stays on the context's stream)
+    x->lanes_ok = x->own_stream && !(c.flags & (SL3D_FLAG_SERIAL_LAUNCHES | SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL | SL3D_FLAG_REPAIR_PERIODS)) &&
+                  !getenv("SL3D_NO_LAUNCH_LANES");
 
     KParams &P = x->P;
     P.W = c.width; P.H = c.height; P.fullW = c.full_width; P.fullH = c.full_height;

@@ -117,7 +117,19 @@ inline int download_plane(sl3d_ctx *x, const T *src, int comps, T *out, size_t o
 // THE routing decision of a SL3D_FLAG_SUBPIXEL context: does a dense launch of this context go out as k_subpixel_fused instead of a
 // k_fused instantiation?  (With SL3D_FLAG_KEEP_STAGES it stays the parity kernel, and k_subpixel follows it.)  run_fused launches by it,
 // sl3d_fused_kernel_name, sl3d_last_fused_kernel_name and sl3d_camera_table_bytes_per_pixel report by it
-inline bool subpixel_fused_route(const sl3d_ctx *x) { return x->subpixel && !x->keep; }
+inline bool subpixel_fused_route(const sl3d_ctx *x) { return x->subpixel && !x->keep && !x->repair; }
+// ... and of a SL3D_FLAG_REPAIR_PERIODS context: k_repair_fused, with the sub-pixel ending if the context has SL3D_FLAG_SUBPIXEL too.  (With
+// SL3D_FLAG_KEEP_STAGES: the parity kernel, the staged repair of both axes, stage 5 and stage 7 or k_subpixel behind it.)  The same four
+// report by it; own_kernel_route: either of the two -- one launch per call on the context's stream, no k_fused instantiation, no camera table
+inline bool repair_fused_route(const sl3d_ctx *x) { return x->repair && !x->keep; }
+inline bool own_kernel_route(const sl3d_ctx *x) { return subpixel_fused_route(x) || repair_fused_route(x); }
+inline const char *own_kernel_name(const sl3d_ctx *x)
+{
+    return !repair_fused_route(x) ? SL3D_SUBPIXEL_FUSED_NAME : x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;
+}
+// the launches of sl3d_repair_periods (sl3d_capi_period.cpp): one pass over one axis of one view behind whatever the stream holds; the
+// counts are added to the view's and the axis's two words of d_period_counts, which the caller has cleared if it reads them
+SL3D_INTERNAL int period_repair_enqueue(sl3d_ctx *x, int view, int axis, int radius);
 SL3D_INTERNAL bool maskin_launch(const sl3d_ctx *x, int first_view, int n_views, bool keep);
 SL3D_INTERNAL int small_launch_overlaps(sl3d_ctx *x, int first_view, int n_views, bool *overlap);
 SL3D_INTERNAL int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap = false);

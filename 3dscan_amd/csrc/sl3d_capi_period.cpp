@@ -5,6 +5,18 @@
 
 static_assert(SL3D_E_INVALID_ARG == -1 && SL3D_E_STATE == -4 && SL3D_E_UNSUPPORTED == -5, "period_check_args returns these values");
 
+// (arguments checked by the caller: a KEEP_STAGES context, an axis with Gray planes)
+int period_repair_enqueue(sl3d_ctx *x, int view, int axis, int radius)
+{
+    const bool wide = (axis == 0 ? x->P.Nv : x->P.Nh) >= 8;
+    int rc = ensure_plane(x, &x->d_period_jump, x->P.px_view_stride);
+    if (!rc && wide) rc = ensure_plane(x, &x->d_period_wide, x->P.px_view_stride);
+    if (!rc) rc = ensure_plane(x, &x->d_period_counts, (size_t)x->cfg.max_views * 4);
+    if (rc) return rc;
+    const PeriodPlanes b = {x->d_period_jump, wide ? x->d_period_wide : nullptr, x->d_period_counts + 4 * (size_t)view + 2 * (size_t)axis};
+    return launched(x, launch_period_repair(x->P, view, axis, radius, b, x->stream));
+}
+
 extern "C" int sl3d_repair_periods(sl3d_ctx *x, int view, int axis, int radius, uint32_t counts[2])
 try {
     if (!x) return SL3D_E_INVALID_ARG;
@@ -16,14 +28,11 @@ try {
         return fail(x, status, axis != 0 && axis != 1 ? "axis must be 0 or 1" : "repair_periods: radius must be 1..8");
     }
     ON_DEVICE(x);
-    int rc = ensure_plane(x, &x->d_period_jump, x->P.px_view_stride);
-    if (!rc && (axis == 0 ? x->P.Nv : x->P.Nh) >= 8) rc = ensure_plane(x, &x->d_period_wide, x->P.px_view_stride);
-    if (!rc) rc = ensure_plane(x, &x->d_period_counts, (size_t)x->cfg.max_views * 4);
+    int rc = ensure_plane(x, &x->d_period_counts, (size_t)x->cfg.max_views * 4);
     if (rc) return rc;
     unsigned *cnt = x->d_period_counts + 4 * (size_t)view + 2 * (size_t)axis;
     HIPCHK(x, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned), x->stream));
-    const PeriodPlanes b = {x->d_period_jump, (axis == 0 ? x->P.Nv : x->P.Nh) >= 8 ? x->d_period_wide : nullptr, cnt};
-    if ((rc = launched(x, launch_period_repair(x->P, view, axis, radius, b, x->stream)))) return rc;
+    if ((rc = period_repair_enqueue(x, view, axis, radius))) return rc;
     if (counts) {
         HIPCHK(x, hipMemcpyAsync(counts, cnt, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, x->stream));
         SYNC_FOR_CALLER(x);

@@ -136,19 +136,33 @@ static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int 
 // every fused launch of the library goes through here.  A SL3D_FLAG_SUBPIXEL context (subpixel_fused_route): the timed one launches k_subpixel_fused on the context's stream, behind the
 // preparation of whatever masks of the views are still deferred; the parity one launches what it always does and k_subpixel
 // (+infinity, no counts) behind it.  Either way sl3d_run leaves the same scan.
+// A SL3D_FLAG_REPAIR_PERIODS context (repair_fused_route) likewise: the timed one launches k_repair_fused -- with the sub-pixel ending
+// if it has SL3D_FLAG_SUBPIXEL too -- and the parity one launches what it always does, then one pass of the staged repair over every axis
+// that has Gray planes, then stage 5 again and stage 7 (or k_subpixel) over the repaired phases.
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
-    if (!x->subpixel) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
+    if (!x->subpixel && !x->repair) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
     int rc;
-    if (subpixel_fused_route(x)) {
+    if (own_kernel_route(x)) {
         if ((rc = flush_masks(x, first_view, n_views))) return rc;
         x->launches_on_stream++;
-        rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->stream));
+        if (repair_fused_route(x)) rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream));
+        else rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->stream));
+        if (!rc) x->own_kernel_ran = true;
     } else {
         if ((rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap))) return rc;
-        rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->stream));
+        if (x->repair) {
+            for (int view = first_view; view < first_view + n_views; view++) {
+                for (int axis = 0; axis < 2; axis++)
+                    if ((axis == 0 ? x->P.Nv : x->P.Nh) != 0 && (rc = period_repair_enqueue(x, view, axis, SL3D_REPAIR_FUSED_RADIUS))) return rc;
+                if ((rc = launched(x, launch_corr(x->P, view, x->stream)))) return rc;
+                if (!x->subpixel && (rc = launched(x, launch_tri(x->P, x->C, view, x->stream)))) return rc;
+            }
+        }
+        if (x->subpixel)
+            rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->stream));
     }
-    if (!rc) x->residual_ready = true;
+    if (!rc && x->subpixel) x->residual_ready = true;
     return rc;
 }
 
@@ -221,9 +235,9 @@ extern "C" int sl3d_launch_counts(sl3d_ctx *x, int64_t *on_stream, int64_t *on_l
 extern "C" int sl3d_last_fused_kernel_name(sl3d_ctx *x, char *buf, size_t capacity)
 try {
     if (!x || !buf || capacity == 0) return fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: null argument");
-    const bool sub = subpixel_fused_route(x);  // (every launch of such a context is k_subpixel_fused)
-    if (sub ? !x->residual_ready : x->last_fused.nmax == 0) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
-    const int n = sub ? snprintf(buf, capacity, "%s", SL3D_SUBPIXEL_FUSED_NAME) : fused_key_name(x->last_fused, buf, capacity);
+    const bool own = own_kernel_route(x);  // (every launch of such a context is k_subpixel_fused / k_repair_fused)
+    if (own ? !x->own_kernel_ran : x->last_fused.nmax == 0) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
+    const int n = own ? snprintf(buf, capacity, "%s", own_kernel_name(x)) : fused_key_name(x->last_fused, buf, capacity);
     return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: buffer too small");
 }
 SL3D_CATCH(x)
@@ -248,9 +262,11 @@ extern "C" int sl3d_fused_kernel_name(sl3d_ctx *x, int n_views, int clouds, char
 try {
     if (!x || !buf || capacity == 0 || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: null argument");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called (the rig class is part of the name)");
-    if (subpixel_fused_route(x)) {
-        if (clouds) return fail(x, SL3D_E_UNSUPPORTED, "fused_kernel_name: a SL3D_FLAG_SUBPIXEL context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)");
-        const int n = snprintf(buf, capacity, "%s", SL3D_SUBPIXEL_FUSED_NAME);
+    if (own_kernel_route(x)) {
+        if (clouds)
+            return fail(x, SL3D_E_UNSUPPORTED, repair_fused_route(x) ? "fused_kernel_name: a SL3D_FLAG_REPAIR_PERIODS context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)"
+                                                                     : "fused_kernel_name: a SL3D_FLAG_SUBPIXEL context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)");
+        const int n = snprintf(buf, capacity, "%s", own_kernel_name(x));
         return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: buffer too small");
     }
     const bool fits = n_views <= x->cfg.max_views, gated = fits && sparse_views(x, 0, n_views);
@@ -263,7 +279,7 @@ extern "C" int sl3d_camera_table_bytes_per_pixel(sl3d_ctx *x, int n_views)
 try {
     if (!x || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "camera_table_bytes_per_pixel: null context or no views");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called");
-    if (!x->P.cam_tab || subpixel_fused_route(x)) return 0;  // (k_subpixel_fused iterates the camera's undistortion itself)
+    if (!x->P.cam_tab || own_kernel_route(x)) return 0;  // (k_subpixel_fused and k_repair_fused iterate the camera's undistortion themselves)
     if (x->P.cam_tab_kind == 2) return 16;
     (void)n_views;
     return 8;

@@ -47,7 +47,7 @@ try {
     if (rc) return rc;
     if (!out) return fail(x, SL3D_E_INVALID_ARG, "null output");
     if (!x->d_residual || !x->residual_ready)
-        return fail(x, SL3D_E_STATE, subpixel_fused_route(x) ? "no residuals: sl3d_run has not been called on this SL3D_FLAG_SUBPIXEL context"
+        return fail(x, SL3D_E_STATE, x->subpixel && !x->keep ? "no residuals: sl3d_run has not been called on this SL3D_FLAG_SUBPIXEL context"
                                      : x->subpixel         ? "no residuals: neither sl3d_run nor sl3d_triangulate_subpixel has been called"
                                                            : "no residuals: sl3d_triangulate_subpixel has not been called");
     return download_plane(x, x->d_residual + (size_t)view * x->P.px_view_stride, 1, out, stride);

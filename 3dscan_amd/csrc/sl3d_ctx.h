@@ -22,6 +22,10 @@ struct sl3d_ctx {
     bool keep = false;
     // SL3D_FLAG_SUBPIXEL: sl3d_run leaves the sub-pixel scan.  Which launch that takes is subpixel_fused_route (sl3d_capi_internal.h)
     bool subpixel = false;
+    // SL3D_FLAG_REPAIR_PERIODS: sl3d_run leaves the scan with the 2*Pi period jumps of both axes repaired (radius 4, one pass).  Which
+    // launches that takes is repair_fused_route (sl3d_capi_internal.h)
+    bool repair = false;
+    bool own_kernel_ran = false;  // own_kernel_route: a launch has gone out (sl3d_last_fused_kernel_name)
     bool own_stream = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -189,6 +189,10 @@ try {
     *out = nullptr;
     if (cfg->height < n) return gfail(nullptr, SL3D_E_INVALID_ARG, "group_create: more stripes than rows");
     if (cfg->stream) return gfail(nullptr, SL3D_E_INVALID_ARG, "group_create: every stripe creates its own stream (cfg->stream must be NULL)");
+    if (cfg->flags & SL3D_FLAG_REPAIR_PERIODS)
+        return gfail(nullptr, SL3D_E_UNSUPPORTED,
+                     "group_create: SL3D_FLAG_REPAIR_PERIODS has no group form: a repair neighbourhood is clipped to its context's window, so the "
+                     "horizontal axis of a row stripe would decide differently from the whole frame within 4 rows of every seam");
     sl3d_group *g = new sl3d_group();
     g->cfg = *cfg;
     if (g->cfg.full_width == 0) g->cfg.full_width = cfg->width;

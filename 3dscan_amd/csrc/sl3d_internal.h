@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -231,6 +231,14 @@ int launch_subpixel_coords(const KParams &P, int view, double *xy, void *stream)
 // launch_subpixel(+inf) leave there, in one launch.  SL3D_SUBPIXEL_FUSED_NAME: the kernel as rocprofv3 spells it
 #define SL3D_SUBPIXEL_FUSED_NAME "sl3d::k_subpixel_fused"
 int launch_subpixel_fused(const KParams &P, const DevCal *d_cal, int first_view, int n_views, float *residual, void *stream);
+// the period-repaired scan of a timed context (sl3d_repair_fused.hip, SL3D_FLAG_REPAIR_PERIODS): what launch_wrap / launch_unwrap of both
+// axes, launch_period_repair(radius SL3D_REPAIR_FUSED_RADIUS) of every axis that has Gray planes, launch_corr and launch_tri leave in
+// the views' points and valid planes, in one launch; residual != NULL: the sub-pixel ending instead (launch_subpixel(+inf)) and the
+// residual plane with it.  SL3D_REPAIR_FUSED_NAME / _SUB_NAME: the two instantiations as rocprofv3 spells them
+#define SL3D_REPAIR_FUSED_RADIUS 4
+#define SL3D_REPAIR_FUSED_NAME "sl3d::k_repair_fused<false>"
+#define SL3D_REPAIR_FUSED_SUB_NAME "sl3d::k_repair_fused<true>"
+int launch_repair_fused(const KParams &P, const DevCal *d_cal, int first_view, int n_views, float *residual, void *stream);
 // counts per block (or chunk) of a launch's views, their exclusive scan (k_compact_scan) and the views' totals: the scratch of every
 // consumer of a dense result.  Compaction (O1 / N2): cnt / off hold one slot per view OF A LAUNCH (slot k: view first_view + k), a slot =
 // the valid pixels of the view's 1024-pixel blocks; tot: [max_views], view v's at tot[v].  Mesh: cnt / off [max_views][2][mesh_chunks]

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.16.0"
+#define SL3D_VERSION_STRING "0.17.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -93,7 +93,27 @@ enum sl3d_flags {
      *   behind it; sl3d_compute_c_p_map + sl3d_triangulate restores the integer result.
      * Every consumer of the dense planes (getters, compactions, colour, registration, meshes) sees the sub-pixel scan.  sl3d_group_create
      * hands the flag to its stripes.  A context without the flag behaves exactly as before. */
-    SL3D_FLAG_SUBPIXEL = 128u
+    SL3D_FLAG_SUBPIXEL = 128u,
+    /* (0.17.0) sl3d_run() -- and with it sl3d_run_timed and sl3d_process_views -- leaves the scan with the 2*Pi period jumps of the
+     * absolute phase REPAIRED: after sl3d_run(ctx, first_view, n_views) the points and valid planes of those views hold, bit for bit on
+     * every pixel of the window (NaN patterns included), what this staged route leaves on a KEEP_STAGES context with the same
+     * configuration, calibration, masks and frames: sl3d_compute_wrapped_phase + sl3d_unwrap_phase of both axes; sl3d_repair_periods(
+     * view, axis, 4, NULL), one pass, for each axis that has Gray planes (an axis with n_gray == 0 is skipped: the staged call refuses
+     * it); sl3d_compute_c_p_map; sl3d_triangulate.  With SL3D_FLAG_SUBPIXEL also set the last step is sl3d_triangulate_subpixel(
+     * first_view, n_views, +infinity, NULL) instead, and the residual plane matches as well.
+     *   The radius is fixed at 4.  Other radii, several passes and the repaired / unrepairable counts stay with sl3d_repair_periods.
+     *   Without KEEP_STAGES: ONE launch of a kernel of its own (k_repair_fused: frames in; points, valid -- and residuals -- out; no
+     *   stage plane in between; the block decodes the halo of its tile itself) on the context's stream -- such a context has no launch
+     *   lanes, sl3d_launch_counts reports every launch as on-stream -- behind the preparation of whatever masks of the views are still
+     *   deferred.  sl3d_fused_kernel_name / sl3d_last_fused_kernel_name give that kernel, sl3d_camera_table_bytes_per_pixel is 0.
+     *   sl3d_run_clouds has no repaired form: SL3D_E_UNSUPPORTED (sl3d_run + sl3d_compact_views).  sl3d_repair_periods and the other
+     *   per-stage calls stay SL3D_E_STATE as on every timed context.
+     *   With KEEP_STAGES: sl3d_run() launches what it always does, then sl3d_repair_periods' launches for both axes at radius 4, then
+     *   stage 5, then stage 7 (or sl3d_triangulate_subpixel's kernel): the stage getters show the repaired code and phase.
+     * Every consumer of the dense planes sees the repaired scan.  sl3d_group_create refuses the flag (SL3D_E_UNSUPPORTED): a neighbourhood
+     * is clipped to the context's window, so the horizontal axis of a row stripe would decide differently from the whole frame within 4
+     * rows of every seam.  A context without the flag behaves exactly as before. */
+    SL3D_FLAG_REPAIR_PERIODS = 256u
     /* (8u was SL3D_FLAG_CLOUDS_LOOKBACK until 0.3: contiguous clouds in one pass by a decoupled look-back between tiles.  Removed
      * in 0.4 -- every tile waited for its predecessors, 0.53 of the roofline against 0.67 for the segmented clouds; a consumer
      * that wants one contiguous device array asks sl3d_get_cloud_counts for it.) */
@@ -324,13 +344,14 @@ int sl3d_get_correspondences_subpixel(sl3d_ctx *ctx, int view, double *xy, size_
  * float cast of 8/save_point_cloud.cpp:100-102, for views [first_view, first_view+n_views), as ONE
  * kernel launch that reads every frame byte once and writes xyz (f32) + valid (u8). Asynchronous.
  * On a SL3D_FLAG_SUBPIXEL context: the sub-pixel scan and its residual plane instead (see the flag) -- still one launch per call
- * without KEEP_STAGES, the parity launch + sl3d_triangulate_subpixel's with it. */
+ * without KEEP_STAGES, the parity launch + sl3d_triangulate_subpixel's with it.  On a SL3D_FLAG_REPAIR_PERIODS context: the scan with
+ * the period jumps of both axes repaired (see the flag), one launch per call without KEEP_STAGES as well. */
 int sl3d_run(sl3d_ctx *ctx, int first_view, int n_views);
 /* The same pass with the compaction of 8/save_point_cloud.cpp:33-37,85-104 INSIDE the kernel: instead of the dense xyz plane every
  * view's valid points are written once, compacted in the reference's row-major scan order, plus the valid map:
  * ~47 + 12*valid_fraction + 1 bytes per pixel instead of 60 for the dense pass + 25 for a separate compaction.  Timed mode only
- * (no SL3D_FLAG_KEEP_STAGES), and the integer scan only: SL3D_E_UNSUPPORTED on a SL3D_FLAG_SUBPIXEL context, nothing changed (sl3d_run +
- * sl3d_compact_views give its clouds).  Asynchronous.
+ * (no SL3D_FLAG_KEEP_STAGES), and the integer scan only: SL3D_E_UNSUPPORTED on a SL3D_FLAG_SUBPIXEL or SL3D_FLAG_REPAIR_PERIODS context, nothing
+ * changed (sl3d_run + sl3d_compact_views give its clouds).  Asynchronous.
  *   SEGMENTED clouds.  Every wave of the kernel compacts the 256 consecutive scan pixels it owns into its own fixed slot
  *   (points [256*s, 256*s + count_s) of the view's region) and stores count_s.  The counts become offsets by a small scan kernel
  *   right behind a launch of more than 4 views; a launch of up to 4 views -- the reference's one scan per call -- leaves the scan
@@ -375,7 +396,8 @@ int sl3d_register_clouds(sl3d_ctx *ctx, int first_view, int n_views, float tx, f
  * with this context's configuration and calibration, spelled as rocprofv3 --kernel-trace prints it: benchmarks name the kernel
  * their roofline figure is about without restating the library's dispatch rules.  On a SL3D_FLAG_SUBPIXEL context without KEEP_STAGES
  * this, and sl3d_last_fused_kernel_name after the first sl3d_run, is "sl3d::k_subpixel_fused" (clouds = 1: SL3D_E_UNSUPPORTED), and
- * sl3d_camera_table_bytes_per_pixel is 0: that kernel reads no table. */
+ * sl3d_camera_table_bytes_per_pixel is 0: that kernel reads no table.  On a SL3D_FLAG_REPAIR_PERIODS context without KEEP_STAGES the same
+ * holds with "sl3d::k_repair_fused<false>", or "sl3d::k_repair_fused<true>" if the context has SL3D_FLAG_SUBPIXEL too. */
 int sl3d_fused_kernel_name(sl3d_ctx *ctx, int n_views, int clouds, char *buf, size_t capacity);
 /* The instantiation the LAST fused launch of this context ran (sl3d_run, sl3d_run_clouds, sl3d_run_timed, sl3d_process_views): the
  * choice is recorded when the launch is made -- it depends on what was known about the views' masks at that moment (a small
