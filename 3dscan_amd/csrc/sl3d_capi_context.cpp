@@ -2,6 +2,7 @@
 // layout: frame stack, mask with halo, dense results, optional stage planes; the device-side proof of the lattice atan2), and the per-scan
 // constants of stage 7 (Rodrigues, A = K*[R|t]: 7/triangulation.cpp:1061-1126) with the per-calibration tables.  All compute happens in the
 // HIP kernels; there is no CPU implementation of the path in this library.
+#include "sl3d_anchor.h"
 #include "sl3d_capi_internal.h"
 
 static thread_local std::string g_create_err;
@@ -97,6 +98,9 @@ try {
     if (c.n_fringe < 3 || c.n_fringe > 5) return fail(nullptr, SL3D_E_UNSUPPORTED, "n_fringe must be 3, 4 or 5");
     if (c.n_gray_v < 0 || c.n_gray_v > SL3D_MAX_GRAY || c.n_gray_h < 0 || c.n_gray_h > SL3D_MAX_GRAY)
         return fail(nullptr, SL3D_E_UNSUPPORTED, "n_gray out of range");
+    // (decided before a device is touched, sl3d_anchor.h)
+    if (const char *why = anchor_refusal((c.flags & SL3D_FLAG_ANCHOR_PERIODS) != 0, (c.flags & SL3D_FLAG_SUBPIXEL) != 0, (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
+        return fail(nullptr, SL3D_E_UNSUPPORTED, why);
     if (c.n_codes_v <= 0) c.n_codes_v = (c.proj_width + c.fringe_width_v - 1) / c.fringe_width_v;
     if (c.n_codes_h <= 0) c.n_codes_h = (c.proj_height + c.fringe_width_h - 1) / c.fringe_width_h;
 
@@ -114,6 +118,7 @@ try {
     x->keep = (c.flags & SL3D_FLAG_KEEP_STAGES) != 0;
     x->subpixel = (c.flags & SL3D_FLAG_SUBPIXEL) != 0;
     x->repair = (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0;
+    x->anchor = (c.flags & SL3D_FLAG_ANCHOR_PERIODS) != 0;
 #define CREATE_CHK(call)                                                                 \
     do {                                                                                 \
         hipError_t e_ = (call);                                                          \

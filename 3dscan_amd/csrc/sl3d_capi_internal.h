@@ -125,7 +125,8 @@ inline bool repair_fused_route(const sl3d_ctx *x) { return x->repair && !x->keep
 inline bool own_kernel_route(const sl3d_ctx *x) { return subpixel_fused_route(x) || repair_fused_route(x); }
 inline const char *own_kernel_name(const sl3d_ctx *x)
 {
-    return !repair_fused_route(x) ? SL3D_SUBPIXEL_FUSED_NAME : x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;
+    if (!repair_fused_route(x)) return x->anchor ? SL3D_SUBPIXEL_FUSED_ANCHOR_NAME : SL3D_SUBPIXEL_FUSED_NAME;
+    return x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;
 }
 // the launches of sl3d_repair_periods (sl3d_capi_period.cpp): one pass over one axis of one view behind whatever the stream holds; the
 // counts are added to the view's and the axis's two words of d_period_counts, which the caller has cleared if it reads them

@@ -27,6 +27,10 @@ try {
         if (status == SL3D_E_UNSUPPORTED) return fail(x, status, "repair_periods: the axis has no Gray planes (n_gray == 0), there is no period to repair");
         return fail(x, status, axis != 0 && axis != 1 ? "axis must be 0 or 1" : "repair_periods: radius must be 1..8");
     }
+    if (x->anchor)  // (nothing has been touched)
+        return fail(x, SL3D_E_UNSUPPORTED,
+                    "repair_periods: not on a SL3D_FLAG_ANCHOR_PERIODS context: the repair turns code from the Gray cell into a fringe index, which leaves "
+                    "nothing to anchor to (create the context without SL3D_FLAG_ANCHOR_PERIODS to repair instead)");
     ON_DEVICE(x);
     int rc = ensure_plane(x, &x->d_period_counts, (size_t)x->cfg.max_views * 4);
     if (rc) return rc;

@@ -135,7 +135,8 @@ static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int 
 
 // every fused launch of the library goes through here.  A SL3D_FLAG_SUBPIXEL context (subpixel_fused_route): the timed one launches k_subpixel_fused on the context's stream, behind the
 // preparation of whatever masks of the views are still deferred; the parity one launches what it always does and k_subpixel
-// (+infinity, no counts) behind it.  Either way sl3d_run leaves the same scan.
+// (+infinity, no counts) behind it.  Either way sl3d_run leaves the same scan.  SL3D_FLAG_ANCHOR_PERIODS picks the anchored instantiation of
+// whichever of the two kernels goes out.
 // A SL3D_FLAG_REPAIR_PERIODS context (repair_fused_route) likewise: the timed one launches k_repair_fused -- with the sub-pixel ending
 // if it has SL3D_FLAG_SUBPIXEL too -- and the parity one launches what it always does, then one pass of the staged repair over every axis
 // that has Gray planes, then stage 5 again and stage 7 (or k_subpixel) over the repaired phases.
@@ -147,7 +148,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
         if ((rc = flush_masks(x, first_view, n_views))) return rc;
         x->launches_on_stream++;
         if (repair_fused_route(x)) rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream));
-        else rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->stream));
+        else rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->anchor, x->stream));
         if (!rc) x->own_kernel_ran = true;
     } else {
         if ((rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap))) return rc;
@@ -160,7 +161,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
             }
         }
         if (x->subpixel)
-            rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->stream));
+            rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->anchor, x->stream));
     }
     if (!rc && x->subpixel) x->residual_ready = true;
     return rc;

@@ -30,7 +30,7 @@ try {
         if (rc) return rc;
     }
     unsigned *cnt = x->d_subpixel_counts;
-    int rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, max_residual, x->d_residual, counts ? x->d_subpixel_partials : nullptr, cnt, x->stream));
+    int rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, max_residual, x->d_residual, counts ? x->d_subpixel_partials : nullptr, cnt, x->anchor, x->stream));
     if (rc) return rc;
     x->residual_ready = true;
     if (counts) {
@@ -62,7 +62,7 @@ try {
     if (stride < (size_t)x->P.W) return fail(x, SL3D_E_INVALID_ARG, "output stride too small");
     ON_DEVICE(x);
     if ((rc = ensure_plane(x, &x->d_subpixel_xy, 2 * x->P.px_view_stride))) return rc;
-    if ((rc = launched(x, launch_subpixel_coords(x->P, view, x->d_subpixel_xy, x->stream)))) return rc;
+    if ((rc = launched(x, launch_subpixel_coords(x->P, view, x->d_subpixel_xy, x->anchor, x->stream)))) return rc;
     return download_plane(x, x->d_subpixel_xy, 2, xy, 2 * stride);
 }
 SL3D_CATCH(x)

@@ -25,6 +25,9 @@ struct sl3d_ctx {
     // SL3D_FLAG_REPAIR_PERIODS: sl3d_run leaves the scan with the 2*Pi period jumps of both axes repaired (radius 4, one pass).  Which
     // launches that takes is repair_fused_route (sl3d_capi_internal.h)
     bool repair = false;
+    // SL3D_FLAG_ANCHOR_PERIODS (only with subpixel, never with repair: sl3d_create): the sub-pixel solve and
+    // sl3d_get_correspondences_subpixel take the anchored coordinates (sl3d_anchor.h)
+    bool anchor = false;
     bool own_kernel_ran = false;  // own_kernel_route: a launch has gone out (sl3d_last_fused_kernel_name)
     bool own_stream = false;
     hipStream_t stream = nullptr;

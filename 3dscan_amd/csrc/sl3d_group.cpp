@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "sl3d_anchor.h"
 #include "sl3d_ctx.h"
 
 namespace {
@@ -189,6 +190,9 @@ try {
     *out = nullptr;
     if (cfg->height < n) return gfail(nullptr, SL3D_E_INVALID_ARG, "group_create: more stripes than rows");
     if (cfg->stream) return gfail(nullptr, SL3D_E_INVALID_ARG, "group_create: every stripe creates its own stream (cfg->stream must be NULL)");
+    // (sl3d_create's own refusal, made here before a stripe is created)
+    if (const char *why = anchor_refusal((cfg->flags & SL3D_FLAG_ANCHOR_PERIODS) != 0, (cfg->flags & SL3D_FLAG_SUBPIXEL) != 0, (cfg->flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
+        return gfail(nullptr, SL3D_E_UNSUPPORTED, std::string("group_create: ") + why);
     if (cfg->flags & SL3D_FLAG_REPAIR_PERIODS)
         return gfail(nullptr, SL3D_E_UNSUPPORTED,
                      "group_create: SL3D_FLAG_REPAIR_PERIODS has no group form: a repair neighbourhood is clipped to its context's window, so the "
@@ -227,7 +231,8 @@ try {
         c.device = s.device;
         c.stream = nullptr;
         // (a stripe's launches stay on its one stream: the group orders its communication behind them by events on that stream)
-        c.flags = (cfg->flags & (SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL)) | SL3D_FLAG_SERIAL_LAUNCHES;
+        // (SL3D_FLAG_ANCHOR_PERIODS goes with SL3D_FLAG_SUBPIXEL: the rule is pointwise and works in frame coordinates, stripes agree with the whole frame)
+        c.flags = (cfg->flags & (SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS)) | SL3D_FLAG_SERIAL_LAUNCHES;
         const int rc = sl3d_create(&c, &s.ctx);
         if (rc != SL3D_OK) return bail(rc, "stripe " + std::to_string(i) + ": " + sl3d_last_error(nullptr));
         DeviceGuard dg(s.device);

@@ -221,16 +221,18 @@ int launch_tri(const KParams &P, const DevCal &C, int view, void *stream);
 // the sub-pixel triangulation of views [first_view, first_view + n_views) in one launch (sl3d_subpixel.hip, sl3d_subpixel.h): residual
 // [max_views][px_view_stride]; partials: NULL, or [n_views][subpixel_blocks(P)] words of scratch -- then a second launch sums them into
 // counts [n_views][2], the triangulated and the rejected pixels of view first_view + k.  launch_subpixel_coords: (xs, ys) of one view ->
-// xy [px_view_stride][2]
+// xy [px_view_stride][2].  anchor (SL3D_FLAG_ANCHOR_PERIODS, sl3d_anchor.h): the coordinates of both from the wrapped-phase and code planes
 unsigned subpixel_blocks(const KParams &P);
 int launch_subpixel(const KParams &P, const DevCal &C, int first_view, int n_views, double max_residual, float *residual, unsigned *partials,
-                    unsigned *counts, void *stream);
-int launch_subpixel_coords(const KParams &P, int view, double *xy, void *stream);
+                    unsigned *counts, bool anchor, void *stream);
+int launch_subpixel_coords(const KParams &P, int view, double *xy, bool anchor, void *stream);
 // the sub-pixel scan of a timed context (sl3d_subpixel_fused.hip, SL3D_FLAG_SUBPIXEL): frames and prepared valid bytes of views [first_view,
 // first_view + n_views) -> their points, valid and residual planes, what launch_wrap / launch_unwrap of both axes, launch_corr and
-// launch_subpixel(+inf) leave there, in one launch.  SL3D_SUBPIXEL_FUSED_NAME: the kernel as rocprofv3 spells it
-#define SL3D_SUBPIXEL_FUSED_NAME "sl3d::k_subpixel_fused"
-int launch_subpixel_fused(const KParams &P, const DevCal *d_cal, int first_view, int n_views, float *residual, void *stream);
+// launch_subpixel(+inf, anchor) leave there, in one launch.  SL3D_SUBPIXEL_FUSED_NAME / _ANCHOR_NAME: the two instantiations as rocprofv3
+// spells them
+#define SL3D_SUBPIXEL_FUSED_NAME "sl3d::k_subpixel_fused<false>"
+#define SL3D_SUBPIXEL_FUSED_ANCHOR_NAME "sl3d::k_subpixel_fused<true>"
+int launch_subpixel_fused(const KParams &P, const DevCal *d_cal, int first_view, int n_views, float *residual, bool anchor, void *stream);
 // the period-repaired scan of a timed context (sl3d_repair_fused.hip, SL3D_FLAG_REPAIR_PERIODS): what launch_wrap / launch_unwrap of both
 // axes, launch_period_repair(radius SL3D_REPAIR_FUSED_RADIUS) of every axis that has Gray planes, launch_corr and launch_tri leave in
 // the views' points and valid planes, in one launch; residual != NULL: the sub-pixel ending instead (launch_subpixel(+inf)) and the

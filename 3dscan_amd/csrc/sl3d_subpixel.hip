@@ -10,10 +10,14 @@
 //   k_subpixel_counts  a block per view: the sum of the view's partial words -> counts[view][2].  No atomic add anywhere: one per wave
 //                      and count on the views' two words cost more than the triangulation itself (measured)
 //   k_subpixel_coords  (xs, ys) of one view into a scratch plane of double pairs, NaN where either axis valid byte is not 1
+// k_subpixel and k_subpixel_coords have an ANCHOR instantiation each (SL3D_FLAG_ANCHOR_PERIODS): the coordinates come from
+// the wrapped-phase and code planes of both axes (sl3d_anchor.h: anchor_coordinate) where stage 4's loop ran on an axis with Gray planes,
+// from the absolute phase elsewhere -- about 25 B/px in instead of 9.
 // Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sl3d_anchor.h"
 #include "sl3d_block.h"
 #include "sl3d_device.h"
 #include "sl3d_internal.h"
@@ -21,7 +25,18 @@
 
 namespace sl3d {
 
+// the continuous projector coordinate of one axis of pixel px of the planes, at column gx and row gy of the frame
+template <bool ANCHOR>
+__device__ __forceinline__ double subpixel_coordinate(const KParams &P, int axis, size_t px, int gx, int gy)
+{
+    const int fw = axis == 0 ? P.fwv : P.fwh;
+    if (ANCHOR && (axis == 0 ? anchor_applies(P.Nv, gx, P.fullW) : anchor_applies(P.Nh, gy, P.fullH)))
+        return anchor_coordinate(P.wrapped[axis][px], P.code[axis][px], fw, P.F);
+    return correspond_arg(P.unwrapped[axis][px], fw);
+}
+
 // partials: NULL, or [gridDim.y][gridDim.x] words: triangulated pixels of the block | rejected ones << 16 (at most 256 of either)
+template <bool ANCHOR>
 __global__ __launch_bounds__(256) void k_subpixel(const KParams P, const DevCal C, int first_view, double max_residual, float *__restrict__ residual,
                                                   unsigned *__restrict__ partials)
 {
@@ -36,9 +51,10 @@ __global__ __launch_bounds__(256) void k_subpixel(const KParams P, const DevCal 
     bool rejected = false;
     if (valid) {
         const int row = (int)(t / (size_t)P.pitch), col = (int)(t - (size_t)row * P.pitch);
-        const double xs = correspond_arg(P.unwrapped[0][px], P.fwv), ys = correspond_arg(P.unwrapped[1][px], P.fwh);
+        const int gx = P.col0 + col, gy = P.row0 + row;
+        const double xs = subpixel_coordinate<ANCHOR>(P, 0, px, gx, gy), ys = subpixel_coordinate<ANCHOR>(P, 1, px, gx, gy);
         double u, v, up, vp;
-        undistort_reproject((double)(P.col0 + col), (double)(P.row0 + row), C.cam, u, v);
+        undistort_reproject((double)gx, (double)gy, C.cam, u, v);
         undistort_reproject(xs, ys, C.proj, up, vp);
         PinnedRows PR;
         for (int j = 0; j < 4; j++) { PR.c2[j] = C.Ac[8 + j]; PR.p2[j] = C.Ap[8 + j]; }
@@ -87,6 +103,7 @@ __global__ __launch_bounds__(256) void k_subpixel_counts(const unsigned *__restr
     }
 }
 
+template <bool ANCHOR>
 __global__ __launch_bounds__(256) void k_subpixel_coords(const KParams P, int view, double *__restrict__ xy)
 {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -95,8 +112,9 @@ __global__ __launch_bounds__(256) void k_subpixel_coords(const KParams P, int vi
     const double nand = __builtin_nan("");
     double xs = nand, ys = nand;
     if (P.valid_axis[0][px] == 1 && P.valid_axis[1][px] == 1) {  // merge_valid_maps: the pixels stage 5 forms the doubles of
-        xs = correspond_arg(P.unwrapped[0][px], P.fwv);
-        ys = correspond_arg(P.unwrapped[1][px], P.fwh);
+        const int row = (int)(t / (size_t)P.pitch), col = (int)(t - (size_t)row * P.pitch);
+        xs = subpixel_coordinate<ANCHOR>(P, 0, px, P.col0 + col, P.row0 + row);
+        ys = subpixel_coordinate<ANCHOR>(P, 1, px, P.col0 + col, P.row0 + row);
     }
     xy[2 * t + 0] = xs;
     xy[2 * t + 1] = ys;
@@ -105,21 +123,25 @@ __global__ __launch_bounds__(256) void k_subpixel_coords(const KParams P, int vi
 unsigned subpixel_blocks(const KParams &P) { return (unsigned)((P.px_view_stride + 255) / 256); }
 
 int launch_subpixel(const KParams &P, const DevCal &C, int first_view, int n_views, double max_residual, float *residual, unsigned *partials,
-                    unsigned *counts, void *stream)
+                    unsigned *counts, bool anchor, void *stream)
 {
     (void)hipGetLastError();
     const unsigned n_blocks = subpixel_blocks(P);
-    hipLaunchKernelGGL(k_subpixel, dim3(n_blocks, (unsigned)n_views), dim3(256), 0, (hipStream_t)stream, P, C, first_view, max_residual, residual, partials);
+    const dim3 grid(n_blocks, (unsigned)n_views);
+    if (anchor) hipLaunchKernelGGL(k_subpixel<true>, grid, dim3(256), 0, (hipStream_t)stream, P, C, first_view, max_residual, residual, partials);
+    else hipLaunchKernelGGL(k_subpixel<false>, grid, dim3(256), 0, (hipStream_t)stream, P, C, first_view, max_residual, residual, partials);
     int e = (int)hipGetLastError();
     if (e || !partials) return e;
     hipLaunchKernelGGL(k_subpixel_counts, dim3((unsigned)n_views), dim3(256), 0, (hipStream_t)stream, partials, n_blocks, counts);
     return (int)hipGetLastError();
 }
 
-int launch_subpixel_coords(const KParams &P, int view, double *xy, void *stream)
+int launch_subpixel_coords(const KParams &P, int view, double *xy, bool anchor, void *stream)
 {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_subpixel_coords, dim3((unsigned)((P.px_view_stride + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, view, xy);
+    const dim3 grid((unsigned)((P.px_view_stride + 255) / 256));
+    if (anchor) hipLaunchKernelGGL(k_subpixel_coords<true>, grid, dim3(256), 0, (hipStream_t)stream, P, view, xy);
+    else hipLaunchKernelGGL(k_subpixel_coords<false>, grid, dim3(256), 0, (hipStream_t)stream, P, view, xy);
     return (int)hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 // stage 5 (correspond: the merged valid byte; correspond_arg: the continuous projector coordinate) -> undistort_reproject of both
 // devices -> triangulate_px -> subpixel_reproj_err2 / subpixel_residual.  Every arithmetic step is the helper the staged kernels call
 // (sl3d_device.h, sl3d_subpixel.h), with the arguments they call it with; nothing is tabulated.
+//   ANCHOR  k_subpixel_fused<true> (SL3D_FLAG_ANCHOR_PERIODS): the solve takes the anchored coordinates (sl3d_anchor.h) from the
+//           shifted wrapped phase and the code where k_subpixel<true> takes them; the absolute phase still decides the valid byte.
 //   shape   a lane owns the 4 consecutive pixels of one dword of every u8 plane (the pitch is a multiple of 16: a quad never straddles
 //           a row) and walks the views of the launch itself: the camera side (u, v) of a pixel does not depend on the view and is
 //           formed once per pixel and launch, for the pixels some view of the launch selects.  The Gray planes are a run-time loop
@@ -15,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sl3d_anchor.h"
 #include "sl3d_device.h"
 #include "sl3d_internal.h"
 #include "sl3d_subpixel.h"
@@ -28,8 +31,12 @@ typedef float spf_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned spf_load(const uint8_t *p) { return __builtin_nontemporal_load((const unsigned *)p); }
 __device__ __forceinline__ unsigned spf_byte(unsigned w, int k) { return (w >> (8 * k)) & 0xffu; }
 
-// the absolute phase of one axis of the quad's pixels whose bit is set in `bits` (k_wrap + k_unwrap; 0 where stage 4's loop does not run)
-__device__ __forceinline__ void spf_axis(const KParams &P, const uint8_t *quad, int axis, unsigned bits, int gx0, int gy, const AtanK &K, float unw[4])
+// the absolute phase of one axis of the quad's pixels whose bit is set in `bits` (k_wrap + k_unwrap; 0 where stage 4's loop does not run),
+// and with ANCHOR beside it what stage 4 leaves in the wrapped-phase and code planes where its loop runs: w = shift_pi(phi), code_out.
+// (Without ANCHOR the text is the parent's, statement by statement: that instantiation keeps the parent's instruction stream.)
+template <bool ANCHOR>
+__device__ __forceinline__ void spf_axis(const KParams &P, const uint8_t *quad, int axis, unsigned bits, int gx0, int gy, const AtanK &K, float unw[4],
+                                         float w[4], int code_out[4])
 {
     const int N = axis == 0 ? P.Nv : P.Nh;
     const uint8_t *fr = quad + (size_t)(axis == 0 ? 0 : P.F + 2 * P.Nv) * P.plane_stride;
@@ -50,15 +57,21 @@ __device__ __forceinline__ void spf_axis(const KParams &P, const uint8_t *quad, 
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         unw[k] = 0.f;
+        if (ANCHOR) {
+            w[k] = 0.f;
+            code_out[k] = code[k];
+        }
         if (!(bits >> k & 1u)) continue;
         const float phi = wrapped_phase<false>(P.F, spf_byte(i0, k), spf_byte(i1, k), spf_byte(i2, k), spf_byte(i3, k), nullptr, K);
         const bool in_range = axis == 0 ? (gx0 + k >= 1 && gx0 + k <= P.fullW - 2) : (gy >= 1 && gy <= P.fullH - 2);  // :285 / :304
         if (in_range) unw[k] = unwrap_value(shift_pi(phi), code[k]);
+        if (ANCHOR && in_range) w[k] = shift_pi(phi);
     }
 }
 
 // Cp: the context's device copy of the calibration, read through scalar loads where a constant is used (as a kernel argument its 93
 // doubles were loaded up front: 180 VGPRs with 128 SGPRs spilled into them, 2 waves per SIMD; this way 117 VGPRs, 4 waves)
+template <bool ANCHOR>
 __global__ __launch_bounds__(SL3D_SPF_BLOCK) void k_subpixel_fused(const KParams P, const DevCal *__restrict__ Cp, int first_view, int n_views,
                                                                    float *__restrict__ residual)
 {
@@ -96,9 +109,10 @@ __global__ __launch_bounds__(SL3D_SPF_BLOCK) void k_subpixel_fused(const KParams
         unsigned valid = 0u;
         if (bits) {
             const uint8_t *quad = P.frames + (size_t)view * P.view_stride + px0;
-            float unw0[4], unw1[4];
-            spf_axis(P, quad, 0, bits, gx0, gy, K, unw0);
-            spf_axis(P, quad, 1, bits, gx0, gy, K, unw1);
+            float unw0[4], unw1[4], w0[4], w1[4];
+            int code0[4], code1[4];
+            spf_axis<ANCHOR>(P, quad, 0, bits, gx0, gy, K, unw0, w0, code0);
+            spf_axis<ANCHOR>(P, quad, 1, bits, gx0, gy, K, unw1, w1, code1);
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 if (!(bits >> k & 1u)) continue;  // merge_valid_maps: both axes carry the valid byte of the boundary removal
@@ -106,7 +120,9 @@ __global__ __launch_bounds__(SL3D_SPF_BLOCK) void k_subpixel_fused(const KParams
                 double dx, dy;
                 const bool okx = correspond(unw0[k], P.fwv, P.PW, cx, dx), oky = correspond(unw1[k], P.fwh, P.PH, cy, dy);
                 if (!(okx && oky)) continue;      // k_corr
-                const double xs = correspond_arg(unw0[k], P.fwv), ys = correspond_arg(unw1[k], P.fwh);
+                // (where the formula does not apply the coordinate stays as it is: k_subpixel<true>)
+                const double xs = ANCHOR && anchor_applies(P.Nv, gx0 + k, P.fullW) ? anchor_coordinate(w0[k], code0[k], P.fwv, P.F) : correspond_arg(unw0[k], P.fwv);
+                const double ys = ANCHOR && anchor_applies(P.Nh, gy, P.fullH) ? anchor_coordinate(w1[k], code1[k], P.fwh, P.F) : correspond_arg(unw1[k], P.fwh);
                 double up, vp, X[3];
                 undistort_reproject(xs, ys, C.proj, up, vp);
                 triangulate_px(C, PR, u[k], v[k], up, vp, X);
@@ -127,12 +143,13 @@ __global__ __launch_bounds__(SL3D_SPF_BLOCK) void k_subpixel_fused(const KParams
     }
 }
 
-int launch_subpixel_fused(const KParams &P, const DevCal *C, int first_view, int n_views, float *residual, void *stream)
+int launch_subpixel_fused(const KParams &P, const DevCal *C, int first_view, int n_views, float *residual, bool anchor, void *stream)
 {
     (void)hipGetLastError();
     const size_t quads = P.px_view_stride / 4;
-    hipLaunchKernelGGL(k_subpixel_fused, dim3((unsigned)((quads + SL3D_SPF_BLOCK - 1) / SL3D_SPF_BLOCK)), dim3(SL3D_SPF_BLOCK), 0, (hipStream_t)stream, P, C,
-                       first_view, n_views, residual);
+    const dim3 grid((unsigned)((quads + SL3D_SPF_BLOCK - 1) / SL3D_SPF_BLOCK));
+    if (anchor) hipLaunchKernelGGL(k_subpixel_fused<true>, grid, dim3(SL3D_SPF_BLOCK), 0, (hipStream_t)stream, P, C, first_view, n_views, residual);
+    else hipLaunchKernelGGL(k_subpixel_fused<false>, grid, dim3(SL3D_SPF_BLOCK), 0, (hipStream_t)stream, P, C, first_view, n_views, residual);
     return (int)hipGetLastError();
 }
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.17.0"
+#define SL3D_VERSION_STRING "0.18.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -113,7 +113,38 @@ enum sl3d_flags {
      * Every consumer of the dense planes sees the repaired scan.  sl3d_group_create refuses the flag (SL3D_E_UNSUPPORTED): a neighbourhood
      * is clipped to the context's window, so the horizontal axis of a row stripe would decide differently from the whole frame within 4
      * rows of every seam.  A context without the flag behaves exactly as before. */
-    SL3D_FLAG_REPAIR_PERIODS = 256u
+    SL3D_FLAG_REPAIR_PERIODS = 256u,
+    /* (0.18.0) The sub-pixel scan of a SL3D_FLAG_SUBPIXEL context takes ANCHORED projector coordinates: the period index of an axis is not
+     * the Gray code itself but the fringe period nearest the centre of the pixel's Gray cell, and the fringe period is measured with pi,
+     * not with the reference's Pi = 22/7 (its generator and decoder write 22/7 around a real cos / atan2: the Gray cell is fringe_width
+     * projector pixels wide, the projected fringe has the period fringe_width * pi / (22/7)).  That takes out a scale error of
+     * p * (22/7 - pi) / (22/7) = 4.0e-4 p pixels at projector coordinate p, and the period jumps in the band behind every Gray edge that
+     * the drift of the phase's wrap against the edge leaves.  The definition, in IEEE double without contraction, in this order, so that
+     * every route agrees bit for bit:
+     *     P2 = (2.0 * 22.0) / 7.0    TWOPI = 2.0 * 3.141592653589793    INV = 0.15915494309189535
+     *     c  = 0.0 for n_fringe == 3,  0.75 * (3.141592653589793 - 22.0 / 7.0) for n_fringe == 4
+     *     w, code: what stage 4 leaves in the wrapped-phase plane (the float, Pi already added) and in the code plane
+     *     a  = (double)w + c
+     *     m  = rint((((double)code + 0.5) * P2 - a) * INV)            (round half to even)
+     *     xs = (double)fringe_width * ((a + TWOPI * m) / P2)
+     * on an axis of a pixel where stage 4's loop runs (frame columns 1..full_width-2 on the vertical axis, frame rows 1..full_height-2 on
+     * the horizontal one) and only if that axis has n_gray > 0; everywhere else the coordinate stays the double stage 5 hands to lrint,
+     * as without the flag.  The rule is pointwise: no neighbourhood, so windows and the stripes of a group agree with the whole frame.
+     *   What changes: the (xs, ys) that the sub-pixel solve and sl3d_get_correspondences_subpixel use -- sl3d_run (the anchored
+     *   instantiation of k_subpixel_fused on a timed context, of sl3d_triangulate_subpixel's kernel behind the parity launch with
+     *   KEEP_STAGES) and sl3d_triangulate_subpixel itself, max_residual and counts as before; sl3d_fused_kernel_name /
+     *   sl3d_last_fused_kernel_name report "sl3d::k_subpixel_fused<true>".  An anchored coordinate may lie a fraction of a pixel outside
+     *   [0, proj_width - 1].
+     *   What does not: the validity of a pixel -- the merged valid byte stays stage 5's, its range test on the integer c_p_map included --
+     *   c_p_map, the wrapped and unwrapped phase planes, code and every other stage getter.
+     *   Refused with SL3D_E_UNSUPPORTED by sl3d_create and sl3d_group_create before a device is touched: the flag without
+     *   SL3D_FLAG_SUBPIXEL (the integer scan has no use for the coordinate), and together with SL3D_FLAG_REPAIR_PERIODS; and by
+     *   sl3d_repair_periods on an anchored KEEP_STAGES context, which leaves every plane as it was.  The repair turns code from "Gray
+     *   cell" into "fringe index": the pixel then sits at the edge of that cell, where anchoring to its centre is a coin flip.
+     *   sl3d_run_clouds stays refused as on every SL3D_FLAG_SUBPIXEL context.  sl3d_group_create hands the flag to its stripes.
+     * What remains: a tie band of relative width 4e-4 per cell in which two positions share one phase, and pixels whose Gray code itself
+     * is wrong at an edge.  A context without the flag behaves exactly as before. */
+    SL3D_FLAG_ANCHOR_PERIODS = 512u
     /* (8u was SL3D_FLAG_CLOUDS_LOOKBACK until 0.3: contiguous clouds in one pass by a decoupled look-back between tiles.  Removed
      * in 0.4 -- every tile waited for its predecessors, 0.53 of the roofline against 0.67 for the segmented clouds; a consumer
      * that wants one contiguous device array asks sl3d_get_cloud_counts for it.) */
@@ -299,7 +330,8 @@ int sl3d_triangulate(sl3d_ctx *ctx, int view);
  * KEEP_STAGES context the same planes exist, so sl3d_repair_periods + sl3d_compute_c_p_map + sl3d_triangulate works there too.
  * counts[0] = repaired, counts[1] = unrepairable pixels of this pass; counts may be NULL (then the call stays asynchronous), otherwise the
  * call synchronises.  SL3D_E_INVALID_ARG for a bad view, an axis outside {0, 1} or a radius outside 1..8; SL3D_E_STATE without
- * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes.  A refused call changes nothing. */
+ * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes, or on a SL3D_FLAG_ANCHOR_PERIODS context (see the flag).  A
+ * refused call changes nothing. */
 int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t counts[2]);
 
 /* ---- sub-pixel triangulation with a reprojection residual (0.15.0; needs SL3D_FLAG_KEEP_STAGES -- the timed mode has it as SL3D_FLAG_SUBPIXEL) --
@@ -327,7 +359,8 @@ int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t 
  * counts: NULL (the call stays asynchronous) or n_views pairs; counts[2k] = pixels of view first_view + k triangulated (merged valid 1 on
  * entry), counts[2k + 1] = those of them rejected; then a second small launch adds them up and the call synchronises.
  * SL3D_E_INVALID_ARG for bad views or a max_residual that is NaN or <= 0 (+infinity: no pixel is rejected); SL3D_E_STATE without
- * SL3D_FLAG_KEEP_STAGES or before sl3d_set_calibration.  A refused call changes nothing. */
+ * SL3D_FLAG_KEEP_STAGES or before sl3d_set_calibration.  A refused call changes nothing.
+ * On a SL3D_FLAG_ANCHOR_PERIODS context (xs, ys) of step 1 are the anchored coordinates (see the flag); everything else is as above. */
 int sl3d_triangulate_subpixel(sl3d_ctx *ctx, int first_view, int n_views, double max_residual, uint32_t *counts);
 /* The residual plane of a view, out[row * stride_elems + col]: NaN on every pixel the last sl3d_triangulate_subpixel over the view did
  * not triangulate (and on a view none has run over).  SL3D_E_STATE before the context's first sl3d_triangulate_subpixel.
@@ -336,7 +369,8 @@ int sl3d_triangulate_subpixel(sl3d_ctx *ctx, int first_view, int n_views, double
 int sl3d_get_residuals(sl3d_ctx *ctx, int view, float *out, size_t stride_elems);
 /* (xs, ys) of step 1 for every window pixel, xy[(row * stride_elems + col) * 2 + {0, 1}], bit for bit those expressions; NaN where
  * either per-axis valid byte is not 1 (the pixels stage 5 does not form them for).  Computed from the stage-4 planes as they are: no
- * sl3d_compute_c_p_map is needed, a rejection does not show.  SL3D_E_STATE without SL3D_FLAG_KEEP_STAGES. */
+ * sl3d_compute_c_p_map is needed, a rejection does not show.  SL3D_E_STATE without SL3D_FLAG_KEEP_STAGES.  On a
+ * SL3D_FLAG_ANCHOR_PERIODS context: the anchored coordinates, bit for bit the flag's definition (same NaN pattern). */
 int sl3d_get_correspondences_subpixel(sl3d_ctx *ctx, int view, double *xy, size_t stride_elems);
 
 /* ---- the fused hot path ------------------------------------------------------------------- */
@@ -395,8 +429,8 @@ int sl3d_register_clouds(sl3d_ctx *ctx, int first_view, int n_views, float tx, f
 /* Name of the fused-kernel instantiation sl3d_run (clouds = 0) / sl3d_run_clouds (clouds = 1) launches for a batch of n_views views
  * with this context's configuration and calibration, spelled as rocprofv3 --kernel-trace prints it: benchmarks name the kernel
  * their roofline figure is about without restating the library's dispatch rules.  On a SL3D_FLAG_SUBPIXEL context without KEEP_STAGES
- * this, and sl3d_last_fused_kernel_name after the first sl3d_run, is "sl3d::k_subpixel_fused" (clouds = 1: SL3D_E_UNSUPPORTED), and
- * sl3d_camera_table_bytes_per_pixel is 0: that kernel reads no table.  On a SL3D_FLAG_REPAIR_PERIODS context without KEEP_STAGES the same
+ * this, and sl3d_last_fused_kernel_name after the first sl3d_run, is "sl3d::k_subpixel_fused<false>" -- "sl3d::k_subpixel_fused<true>" with
+ * SL3D_FLAG_ANCHOR_PERIODS -- (clouds = 1: SL3D_E_UNSUPPORTED), and sl3d_camera_table_bytes_per_pixel is 0: that kernel reads no table.  On a SL3D_FLAG_REPAIR_PERIODS context without KEEP_STAGES the same
  * holds with "sl3d::k_repair_fused<false>", or "sl3d::k_repair_fused<true>" if the context has SL3D_FLAG_SUBPIXEL too. */
 int sl3d_fused_kernel_name(sl3d_ctx *ctx, int n_views, int clouds, char *buf, size_t capacity);
 /* The instantiation the LAST fused launch of this context ran (sl3d_run, sl3d_run_clouds, sl3d_run_timed, sl3d_process_views): the
