@@ -3,6 +3,7 @@
 // constants of stage 7 (Rodrigues, A = K*[R|t]: 7/triangulation.cpp:1061-1126) with the per-calibration tables.  All compute happens in the
 // HIP kernels; there is no CPU implementation of the path in this library.
 #include "sl3d_anchor.h"
+#include "sl3d_one_axis.h"
 #include "sl3d_capi_internal.h"
 
 static thread_local std::string g_create_err;
@@ -80,6 +81,8 @@ static void build_atan_tables(std::vector<float> &tab)
         }
 }
 
+static_assert(SL3D_FLAG_ONLY_VERTICAL == SL3D_ONE_AXIS_VERTICAL_BIT && SL3D_FLAG_ONLY_HORIZONTAL == SL3D_ONE_AXIS_HORIZONTAL_BIT, "one_axis_of_flags reads these bits");
+
 extern "C" int sl3d_create(const sl3d_config *cfg, sl3d_ctx **out)
 try {
     if (!cfg || !out) return fail(nullptr, SL3D_E_INVALID_ARG, "null argument");
@@ -101,6 +104,10 @@ try {
     // (decided before a device is touched, sl3d_anchor.h)
     if (const char *why = anchor_refusal((c.flags & SL3D_FLAG_ANCHOR_PERIODS) != 0, (c.flags & SL3D_FLAG_SUBPIXEL) != 0, (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
         return fail(nullptr, SL3D_E_UNSUPPORTED, why);
+    // (likewise, sl3d_one_axis.h)
+    if (const char *why = one_axis_refusal((c.flags & SL3D_FLAG_ONLY_VERTICAL) != 0, (c.flags & SL3D_FLAG_ONLY_HORIZONTAL) != 0, (c.flags & SL3D_FLAG_SUBPIXEL) != 0,
+                                           (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
+        return fail(nullptr, SL3D_E_UNSUPPORTED, why);
     if (c.n_codes_v <= 0) c.n_codes_v = (c.proj_width + c.fringe_width_v - 1) / c.fringe_width_v;
     if (c.n_codes_h <= 0) c.n_codes_h = (c.proj_height + c.fringe_width_h - 1) / c.fringe_width_h;
 
@@ -119,6 +126,7 @@ try {
     x->subpixel = (c.flags & SL3D_FLAG_SUBPIXEL) != 0;
     x->repair = (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0;
     x->anchor = (c.flags & SL3D_FLAG_ANCHOR_PERIODS) != 0;
+    x->one_axis = one_axis_of_flags(c.flags);
 #define CREATE_CHK(call)                                                                 \
     do {                                                                                 \
         hipError_t e_ = (call);                                                          \
@@ -212,7 +220,8 @@ try {
     CREATE_CHK(hipMemsetAsync(x->d_points, 0, V * P.px_view_stride * 3 * sizeof(float), x->stream));
     CREATE_CHK(hipMemsetAsync(x->d_band, 0, V * P.px_view_stride, x->stream));
     P.frames = x->d_frames; P.mask = x->d_mask; P.points = x->d_points; P.valid = x->d_valid; P.band = x->d_band;
-    if (x->subpixel) {  // the residual plane of sl3d_run, NaN everywhere: the views no call has run over yet (as sl3d_triangulate_subpixel leaves them)
+    if (x->subpixel && x->one_axis < 0) {  // (an exactly determined solve has no residual: a one-axis context has no such plane)
+        // the residual plane of sl3d_run, NaN everywhere: the views no call has run over yet (as sl3d_triangulate_subpixel leaves them)
         ALLOC(x->d_residual, V * P.px_view_stride);
         CREATE_CHK(hipMemsetAsync(x->d_residual, 0xff, V * P.px_view_stride * sizeof(float), x->stream));
     }
@@ -357,6 +366,8 @@ extern "C" int sl3d_set_calibration(sl3d_ctx *x, const double Kc[9], const doubl
 try {
     if (!x || !Kc || !dc || !rc || !tc || !Kp || !dp || !rp || !tp) return fail(x, SL3D_E_INVALID_ARG, "null argument");
     if (Kc[0] == 0 || Kc[4] == 0 || Kp[0] == 0 || Kp[4] == 0) return fail(x, SL3D_E_INVALID_ARG, "zero focal length");
+    // (a one-axis context: before anything of the previous calibration is touched)
+    if (const char *why = one_axis_calibration_refusal(x->one_axis, Kp, dp)) return fail(x, SL3D_E_UNSUPPORTED, why);
     projection_matrix(Kc, rc, tc, x->C.Ac);
     projection_matrix(Kp, rp, tp, x->C.Ap);
     fill_intr(x->C.cam, Kc, dc);

@@ -290,7 +290,9 @@ try {
         HIPCHK_DRAIN(x, hipMemcpy2DAsync(dst, P.mpitch, m + (size_t)k * view_stride + (size_t)g.gy0 * stride + g.gx0, stride, (size_t)(g.gx1 - g.gx0),
                                          (size_t)(g.gy1 - g.gy0), hipMemcpyDefault, x->stream));
     }
-    rc = launched(x, launch_modulation_select(P, first_view, n_views, x->d_mask_raw, m != nullptr, min_modulation, x->stream));
+    // (a one-axis context tests the modulation of its coded axis alone: the frames of the other axis may be absent)
+    if (x->one_axis >= 0) rc = launched(x, launch_modulation_select_one(P, first_view, n_views, x->d_mask_raw, m != nullptr, min_modulation, x->one_axis, x->stream));
+    else rc = launched(x, launch_modulation_select(P, first_view, n_views, x->d_mask_raw, m != nullptr, min_modulation, x->stream));
     if (rc) {
         (void)hipStreamSynchronize(x->stream);  // (no copy from the caller's memory still runs when the error is returned)
         return rc;

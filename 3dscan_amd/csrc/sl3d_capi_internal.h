@@ -74,6 +74,8 @@ inline int grow_plane(sl3d_ctx *c, T **p, size_t *cap, size_t count)
 SL3D_INTERNAL int launched(sl3d_ctx *x, int hip_err);   // a launch's hipError_t -> status (+ the context's error text)
 SL3D_INTERNAL int need_keep(sl3d_ctx *x);               // SL3D_E_STATE unless the context keeps the stage planes
 SL3D_INTERNAL int check_view(sl3d_ctx *x, int view, int n = 1);
+// a per-stage call `call` on `axis`: SL3D_E_UNSUPPORTED on the axis a one-axis context does not code (sl3d_capi_run.cpp)
+SL3D_INTERNAL int one_axis_serves(sl3d_ctx *x, int axis, const char *call);
 // what kind of memory `p` is: 0 = pageable host, 1 = pinned host, 2 = device (*device = its ordinal)
 SL3D_INTERNAL int memory_kind(const void *p, int *device = nullptr);
 SL3D_INTERNAL bool is_pinned_host(const void *p);
@@ -123,8 +125,12 @@ inline bool subpixel_fused_route(const sl3d_ctx *x) { return x->subpixel && !x->
 // report by it; own_kernel_route: either of the two -- one launch per call on the context's stream, no k_fused instantiation, no camera table
 inline bool repair_fused_route(const sl3d_ctx *x) { return x->repair && !x->keep; }
 inline bool own_kernel_route(const sl3d_ctx *x) { return subpixel_fused_route(x) || repair_fused_route(x); }
+// ... and of a one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL; always with SL3D_FLAG_SUBPIXEL, never with the repair: it is a
+// subpixel_fused_route whose kernel is k_one_axis.  With SL3D_FLAG_KEEP_STAGES: stages 3 and 4 of the coded axis, the one-axis stage 5 and 7)
+inline bool one_axis_route(const sl3d_ctx *x) { return x->one_axis >= 0 && subpixel_fused_route(x); }
 inline const char *own_kernel_name(const sl3d_ctx *x)
 {
+    if (one_axis_route(x)) return SL3D_ONE_AXIS_NAME(x->one_axis, x->anchor);
     if (!repair_fused_route(x)) return x->anchor ? SL3D_SUBPIXEL_FUSED_ANCHOR_NAME : SL3D_SUBPIXEL_FUSED_NAME;
     return x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;
 }

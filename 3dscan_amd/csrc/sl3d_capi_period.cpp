@@ -31,9 +31,10 @@ try {
         return fail(x, SL3D_E_UNSUPPORTED,
                     "repair_periods: not on a SL3D_FLAG_ANCHOR_PERIODS context: the repair turns code from the Gray cell into a fringe index, which leaves "
                     "nothing to anchor to (create the context without SL3D_FLAG_ANCHOR_PERIODS to repair instead)");
-    ON_DEVICE(x);
-    int rc = ensure_plane(x, &x->d_period_counts, (size_t)x->cfg.max_views * 4);
+    int rc = one_axis_serves(x, axis, "repair_periods");  // (nothing has been touched)
     if (rc) return rc;
+    ON_DEVICE(x);
+    if ((rc = ensure_plane(x, &x->d_period_counts, (size_t)x->cfg.max_views * 4))) return rc;
     unsigned *cnt = x->d_period_counts + 4 * (size_t)view + 2 * (size_t)axis;
     HIPCHK(x, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned), x->stream));
     if ((rc = period_repair_enqueue(x, view, axis, radius))) return rc;

@@ -15,11 +15,20 @@ int launched(sl3d_ctx *x, int hip_err)
     return SL3D_OK;
 }
 
+// a per-stage call on one axis of a one-axis context: only the coded axis exists (nothing has been touched)
+int one_axis_serves(sl3d_ctx *x, int axis, const char *call)
+{
+    if (x->one_axis < 0 || axis == x->one_axis) return SL3D_OK;
+    return fail(x, SL3D_E_UNSUPPORTED, std::string(call) + (x->one_axis == 0 ? ": a SL3D_FLAG_ONLY_VERTICAL context has no horizontal axis (axis 1)"
+                                                                            : ": a SL3D_FLAG_ONLY_HORIZONTAL context has no vertical axis (axis 0)"));
+}
+
 extern "C" int sl3d_compute_wrapped_phase(sl3d_ctx *x, int view, int axis)
 try {
     int rc = check_view(x, view);
     if (rc || (rc = need_keep(x))) return rc;
     if (axis != 0 && axis != 1) return fail(x, SL3D_E_INVALID_ARG, "axis must be 0 or 1");
+    if ((rc = one_axis_serves(x, axis, "compute_wrapped_phase"))) return rc;
     ON_DEVICE(x);
     return launched(x, launch_wrap(x->P, view, axis, x->stream));
 }
@@ -30,6 +39,7 @@ try {
     int rc = check_view(x, view);
     if (rc || (rc = need_keep(x))) return rc;
     if (axis != 0 && axis != 1) return fail(x, SL3D_E_INVALID_ARG, "axis must be 0 or 1");
+    if ((rc = one_axis_serves(x, axis, "unwrap_phase"))) return rc;
     ON_DEVICE(x);
     return launched(x, launch_unwrap(x->P, view, axis, x->stream));
 }
@@ -40,6 +50,7 @@ try {
     int rc = check_view(x, view);
     if (rc || (rc = need_keep(x))) return rc;
     ON_DEVICE(x);
+    if (x->one_axis >= 0) return launched(x, launch_corr_one(x->P, view, x->one_axis, x->stream));
     return launched(x, launch_corr(x->P, view, x->stream));
 }
 SL3D_CATCH(x)
@@ -49,6 +60,9 @@ try {
     int rc = check_view(x, view);
     if (rc || (rc = need_keep(x))) return rc;
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called");
+    if (x->one_axis >= 0)  // (nothing has been touched)
+        return fail(x, SL3D_E_UNSUPPORTED, "triangulate: the integer solve needs both axes; a SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL context "
+                                           "triangulates with sl3d_triangulate_subpixel");
     ON_DEVICE(x);
     return launched(x, launch_tri(x->P, x->C, view, x->stream));
 }
@@ -140,6 +154,9 @@ static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int 
 // A SL3D_FLAG_REPAIR_PERIODS context (repair_fused_route) likewise: the timed one launches k_repair_fused -- with the sub-pixel ending
 // if it has SL3D_FLAG_SUBPIXEL too -- and the parity one launches what it always does, then one pass of the staged repair over every axis
 // that has Gray planes, then stage 5 again and stage 7 (or k_subpixel) over the repaired phases.
+// A one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL, one_axis_route): the timed one launches k_one_axis, the parity one the staged
+// one-axis route -- k_wrap, k_unwrap of the coded axis and k_corr_one per view, then k_subpixel_one over the views; never the parity k_fused,
+// which reads both axes.
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
     if (!x->subpixel && !x->repair) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
@@ -147,9 +164,19 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
     if (own_kernel_route(x)) {
         if ((rc = flush_masks(x, first_view, n_views))) return rc;
         x->launches_on_stream++;
-        if (repair_fused_route(x)) rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream));
+        if (one_axis_route(x)) rc = launched(x, launch_one_axis(x->P, x->d_cal, x->one_axis, first_view, n_views, x->anchor, x->stream));
+        else if (repair_fused_route(x)) rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream));
         else rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->anchor, x->stream));
         if (!rc) x->own_kernel_ran = true;
+    } else if (x->one_axis >= 0) {  // the staged one-axis route: not the parity kernel, which reads both axes
+        if ((rc = flush_masks(x, first_view, n_views))) return rc;
+        x->launches_on_stream++;  // (one per call, as the parity launch counts)
+        for (int view = first_view; view < first_view + n_views; view++) {
+            if ((rc = launched(x, launch_wrap(x->P, view, x->one_axis, x->stream)))) return rc;
+            if ((rc = launched(x, launch_unwrap(x->P, view, x->one_axis, x->stream)))) return rc;
+            if ((rc = launched(x, launch_corr_one(x->P, view, x->one_axis, x->stream)))) return rc;
+        }
+        return launched(x, launch_subpixel_one(x->P, x->C, x->one_axis, first_view, n_views, nullptr, nullptr, x->anchor, x->stream));
     } else {
         if ((rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap))) return rc;
         if (x->repair) {
@@ -163,7 +190,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
         if (x->subpixel)
             rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->anchor, x->stream));
     }
-    if (!rc && x->subpixel) x->residual_ready = true;
+    if (!rc && x->subpixel && x->one_axis < 0) x->residual_ready = true;
     return rc;
 }
 
@@ -459,8 +486,12 @@ int sl3d_process_views_enqueue(sl3d_ctx *x, int n_views, const uint8_t *const *p
     const int ppv = P.planes_per_view;
     // every pointer is checked BEFORE anything is enqueued: an error return must never leave copies running against
     // buffers the caller is about to free
-    for (size_t i = 0; i < (size_t)n_views * (size_t)ppv; i++)
-        if (!planes[i]) return fail(x, SL3D_E_INVALID_ARG, "process_views: null plane");
+    // (a one-axis context uploads the planes of its coded axis alone: the pointers of the other axis are not looked at, they may be NULL)
+    int p_first, p_count;
+    frame_plane_range(x, &p_first, &p_count);
+    for (int v = 0; v < n_views; v++)
+        for (int p = p_first; p < p_first + p_count; p++)
+            if (!planes[(size_t)v * ppv + p]) return fail(x, SL3D_E_INVALID_ARG, "process_views: null plane");
     for (int v = 0; v < n_views; v++) {
         const int slot = v % S;
         // the slot's previous occupant must have been computed (frames free) and downloaded (results free)
@@ -470,12 +501,13 @@ int sl3d_process_views_enqueue(sl3d_ctx *x, int n_views, const uint8_t *const *p
         }
         // a view whose planes are back to back in host memory, in the device's own pitch, goes up as ONE copy
         bool contiguous = stride == (size_t)P.pitch && (size_t)P.W == (size_t)P.pitch;
-        for (int p = 1; p < ppv; p++)
+        for (int p = p_first + 1; p < p_first + p_count; p++)
             if (planes[(size_t)v * ppv + p] != planes[(size_t)v * ppv + p - 1] + P.plane_stride) contiguous = false;
         if (contiguous) {
-            HIPCHK(x, hipMemcpyAsync(x->d_frames + (size_t)slot * P.view_stride, planes[(size_t)v * ppv], P.view_stride, hipMemcpyHostToDevice, x->s_h2d));
+            HIPCHK(x, hipMemcpyAsync(x->d_frames + (size_t)slot * P.view_stride + (size_t)p_first * P.plane_stride, planes[(size_t)v * ppv + p_first],
+                                     (size_t)p_count * P.plane_stride, hipMemcpyHostToDevice, x->s_h2d));
         } else {
-            for (int p = 0; p < ppv; p++)
+            for (int p = p_first; p < p_first + p_count; p++)
                 HIPCHK(x, hipMemcpy2DAsync(x->d_frames + (size_t)slot * P.view_stride + (size_t)p * P.plane_stride, P.pitch,
                                            planes[(size_t)v * ppv + p], stride, P.W, P.H, hipMemcpyHostToDevice, x->s_h2d));
         }

@@ -28,6 +28,9 @@ struct sl3d_ctx {
     // SL3D_FLAG_ANCHOR_PERIODS (only with subpixel, never with repair: sl3d_create): the sub-pixel solve and
     // sl3d_get_correspondences_subpixel take the anchored coordinates (sl3d_anchor.h)
     bool anchor = false;
+    // SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL (only with subpixel, never with repair: sl3d_create): the coded axis, 0 or 1, of a
+    // one-axis context (sl3d_one_axis.h) -- no frame and no stage plane of the other axis is read, there is no residual plane; -1 otherwise
+    int one_axis = -1;
     bool own_kernel_ran = false;  // own_kernel_route: a launch has gone out (sl3d_last_fused_kernel_name)
     bool own_stream = false;
     hipStream_t stream = nullptr;
@@ -248,3 +251,10 @@ __attribute__((visibility("hidden"))) int sl3d_lanes_join(sl3d_ctx *x);
         if (join_rc_) return join_rc_;                \
     } while (0)
 
+// the planes of a view a context reads, [first, first + count) of planes_per_view: all of them, or those of a one-axis context's coded axis
+inline void frame_plane_range(const sl3d_ctx *x, int *first, int *count)
+{
+    const sl3d::KParams &P = x->P;
+    *first = x->one_axis == 1 ? P.F + 2 * P.Nv : 0;
+    *count = x->one_axis == 0 ? P.F + 2 * P.Nv : x->one_axis == 1 ? P.F + 2 * P.Nh : P.planes_per_view;
+}

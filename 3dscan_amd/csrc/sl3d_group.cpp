@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "sl3d_anchor.h"
+#include "sl3d_one_axis.h"
 #include "sl3d_ctx.h"
 
 namespace {
@@ -193,6 +194,9 @@ try {
     // (sl3d_create's own refusal, made here before a stripe is created)
     if (const char *why = anchor_refusal((cfg->flags & SL3D_FLAG_ANCHOR_PERIODS) != 0, (cfg->flags & SL3D_FLAG_SUBPIXEL) != 0, (cfg->flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
         return gfail(nullptr, SL3D_E_UNSUPPORTED, std::string("group_create: ") + why);
+    if (const char *why = one_axis_refusal((cfg->flags & SL3D_FLAG_ONLY_VERTICAL) != 0, (cfg->flags & SL3D_FLAG_ONLY_HORIZONTAL) != 0, (cfg->flags & SL3D_FLAG_SUBPIXEL) != 0,
+                                           (cfg->flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
+        return gfail(nullptr, SL3D_E_UNSUPPORTED, std::string("group_create: ") + why);
     if (cfg->flags & SL3D_FLAG_REPAIR_PERIODS)
         return gfail(nullptr, SL3D_E_UNSUPPORTED,
                      "group_create: SL3D_FLAG_REPAIR_PERIODS has no group form: a repair neighbourhood is clipped to its context's window, so the "
@@ -232,7 +236,9 @@ try {
         c.stream = nullptr;
         // (a stripe's launches stay on its one stream: the group orders its communication behind them by events on that stream)
         // (SL3D_FLAG_ANCHOR_PERIODS goes with SL3D_FLAG_SUBPIXEL: the rule is pointwise and works in frame coordinates, stripes agree with the whole frame)
-        c.flags = (cfg->flags & (SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS)) | SL3D_FLAG_SERIAL_LAUNCHES;
+        // (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL likewise: pointwise, in frame coordinates)
+        c.flags = (cfg->flags & (SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS | SL3D_FLAG_ONLY_VERTICAL | SL3D_FLAG_ONLY_HORIZONTAL)) |
+                  SL3D_FLAG_SERIAL_LAUNCHES;
         const int rc = sl3d_create(&c, &s.ctx);
         if (rc != SL3D_OK) return bail(rc, "stripe " + std::to_string(i) + ": " + sl3d_last_error(nullptr));
         DeviceGuard dg(s.device);
@@ -548,8 +554,11 @@ try {
     if (!g || n_views < 1 || !planes) return gfail(g, SL3D_E_INVALID_ARG, "group_process_views: null argument");
     const size_t W = (size_t)g->cfg.width, H = (size_t)g->cfg.height;
     const size_t ppv = (size_t)g->st[0].ctx->P.planes_per_view, np = (size_t)n_views * ppv;
+    // (the stripes of a one-axis group upload the planes of the coded axis alone: the pointers of the other axis may be NULL)
+    int p_first, p_count;
+    frame_plane_range(g->st[0].ctx, &p_first, &p_count);
     for (size_t i = 0; i < np; i++)
-        if (!planes[i]) return gfail(g, SL3D_E_INVALID_ARG, "group_process_views: null plane");
+        if (!planes[i] && (int)(i % ppv) >= p_first && (int)(i % ppv) < p_first + p_count) return gfail(g, SL3D_E_INVALID_ARG, "group_process_views: null plane");
     // the pipelines overwrite result slots [0, min(n_views, max_views)) of every stripe: an asynchronous gather may still be
     // reading them (sl3d_group_gather / _gather_clouds only mark the views busy) -- an RCCL send on the communication stream of the
     // stripe's own GPU, a (peer) copy on the root's.  The stripe's stream waits for both, as group_launch does; the enqueue below
@@ -569,7 +578,7 @@ try {
     size_t enq = 0;
     for (; enq < g->st.size(); enq++) {
         const Stripe &S = g->st[enq];
-        for (size_t i = 0; i < np; i++) sub[i] = planes[i] + (size_t)S.row0 * stride;
+        for (size_t i = 0; i < np; i++) sub[i] = planes[i] ? planes[i] + (size_t)S.row0 * stride : nullptr;
         const int rc = sl3d_process_views_enqueue(S.ctx, n_views, sub.data(), stride, xyz ? xyz + (size_t)S.row0 * W * 3 : nullptr, W * H * 3,
                                                   valid ? valid + (size_t)S.row0 * W : nullptr, W * H, W);
         if (rc != SL3D_OK) {

@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -233,6 +233,20 @@ int launch_subpixel_coords(const KParams &P, int view, double *xy, bool anchor, 
 #define SL3D_SUBPIXEL_FUSED_NAME "sl3d::k_subpixel_fused<false>"
 #define SL3D_SUBPIXEL_FUSED_ANCHOR_NAME "sl3d::k_subpixel_fused<true>"
 int launch_subpixel_fused(const KParams &P, const DevCal *d_cal, int first_view, int n_views, float *residual, bool anchor, void *stream);
+// the one-axis scan (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL, sl3d_one_axis.h; axis: the coded one).  Staged: launch_corr_one (sl3d_kernels.hip)
+// is stage 5 of that axis alone, launch_subpixel_one / launch_subpixel_coords_one (sl3d_subpixel.hip) the one-axis forms of launch_subpixel
+// (no residual, nothing rejected: counts [n_views][2] = triangulated, 0) and launch_subpixel_coords.  Timed: launch_one_axis
+// (sl3d_one_axis.hip) leaves in the views' points and valid planes what launch_wrap / launch_unwrap of that axis, launch_corr_one and
+// launch_subpixel_one leave there, in one launch.  SL3D_ONE_AXIS_NAME: its four instantiations as rocprofv3 spells them
+int launch_corr_one(const KParams &P, int view, int axis, void *stream);
+int launch_subpixel_one(const KParams &P, const DevCal &C, int axis, int first_view, int n_views, unsigned *partials, unsigned *counts, bool anchor,
+                        void *stream);
+int launch_subpixel_coords_one(const KParams &P, int axis, int view, double *xy, bool anchor, void *stream);
+#define SL3D_ONE_AXIS_NAME(axis, anchor) \
+    ((axis) == 0 ? ((anchor) ? "sl3d::k_one_axis<0, true>" : "sl3d::k_one_axis<0, false>") : ((anchor) ? "sl3d::k_one_axis<1, true>" : "sl3d::k_one_axis<1, false>"))
+int launch_one_axis(const KParams &P, const DevCal *d_cal, int axis, int first_view, int n_views, bool anchor, void *stream);
+// the fringe-modulation test of a one-axis context: gamma of the coded axis alone, no plane of the other axis read
+int launch_modulation_select_one(const KParams &P, int first_view, int n_views, uint8_t *staging, bool has_mask, double thr, int axis, void *stream);
 // the period-repaired scan of a timed context (sl3d_repair_fused.hip, SL3D_FLAG_REPAIR_PERIODS): what launch_wrap / launch_unwrap of both
 // axes, launch_period_repair(radius SL3D_REPAIR_FUSED_RADIUS) of every axis that has Gray planes, launch_corr and launch_tri leave in
 // the views' points and valid planes, in one launch; residual != NULL: the sub-pixel ending instead (launch_subpixel(+inf)) and the

@@ -259,6 +259,24 @@ __global__ __launch_bounds__(256) void k_corr(const KParams P, int view)
     P.cpmap[2 * px + 1] = v ? cy : 0;
 }
 
+// stage 5 of a one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL): the valid byte of stage 3's boundary removal and the
+// correspondence of the coded axis alone; the other column of c_p_map holds -1 where the pixel is valid.  No plane of the other axis is read.
+__global__ __launch_bounds__(256) void k_corr_one(const KParams P, int view, int axis)
+{
+    int col, row;
+    if (!px_coords(P, col, row)) return;
+    const size_t px = (size_t)view * P.px_view_stride + (size_t)row * P.pitch + col;
+    bool v = P.valid_axis[axis][px] == 1;
+    long c = 0;
+    if (v) {
+        double d;
+        v = correspond(P.unwrapped[axis][px], axis == 0 ? P.fwv : P.fwh, axis == 0 ? P.PW : P.PH, c, d);
+    }
+    P.valid[px] = v ? 1 : 0;
+    P.cpmap[2 * px + axis] = v ? c : 0;
+    P.cpmap[2 * px + (1 - axis)] = v ? -1 : 0;
+}
+
 // stage 7: triangulate  7/triangulation.cpp:1444-1561 (method 3 only; the dead precomputations are not reproduced)
 __global__ __launch_bounds__(256) void k_tri(const KParams P, const DevCal C, int view)
 {
@@ -755,6 +773,11 @@ int launch_unwrap(const KParams &P, int view, int axis, void *stream)
 int launch_corr(const KParams &P, int view, void *stream)
 {
     hipLaunchKernelGGL(k_corr, px_grid(P), dim3(256), 0, (hipStream_t)stream, P, view);
+    return (int)hipGetLastError();
+}
+int launch_corr_one(const KParams &P, int view, int axis, void *stream)
+{
+    hipLaunchKernelGGL(k_corr_one, px_grid(P), dim3(256), 0, (hipStream_t)stream, P, view, axis);
     return (int)hipGetLastError();
 }
 int launch_tri(const KParams &P, const DevCal &C, int view, void *stream)

@@ -46,6 +46,31 @@ __global__ __launch_bounds__(256) void k_modulation_select(const KParams P, int 
     *dst = out;
 }
 
+// the same for a one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL): the test of the coded axis alone -- mod_select with that axis's
+// gamma in both places -- and no plane of the other axis read
+__global__ __launch_bounds__(256) void k_modulation_select_one(const KParams P, int first_view, uint8_t *__restrict__ staging, int has_mask, double thr,
+                                                               int axis)
+{
+    const int qpr = (P.W + 3) >> 2;
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    const int row = (int)(t / (unsigned)qpr), q = (int)(t - (unsigned)row * (unsigned)qpr);
+    if (row >= P.H) return;
+    const int view = first_view + (int)blockIdx.y;
+    const uint8_t *f = P.frames + (size_t)view * P.view_stride + (size_t)(axis == 0 ? 0 : P.F + 2 * P.Nv) * P.plane_stride + (size_t)row * P.pitch + 4 * q;
+    const unsigned f0 = *(const unsigned *)f, f1 = *(const unsigned *)(f + P.plane_stride), f2 = *(const unsigned *)(f + 2 * P.plane_stride);
+    unsigned *dst = (unsigned *)(staging + (size_t)blockIdx.y * P.mask_view_stride + (size_t)(row + SL3D_MASK_HALO) * P.mpitch + SL3D_MASK_LPAD + 4 * q);
+    const unsigned m = has_mask ? *dst : 0x01010101u;
+    const int in_window = P.W - 4 * q;  // pixels of the quad inside the window (>= 1)
+    unsigned out = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float g = quad_gamma(f0, f1, f2, k);
+        const int sel = mod_select(((m >> (8 * k)) & 0xffu) == 1u, g, g, thr);
+        out |= (unsigned)(sel & (k < in_window)) << (8 * k);
+    }
+    *dst = out;
+}
+
 // gamma of axis `axis` of `view`: out[row * pitch + col] (the pitch's padding columns hold gamma of whatever the padding bytes are)
 __global__ __launch_bounds__(256) void k_modulation_gamma(const KParams P, int view, int axis, float *__restrict__ out)
 {
@@ -71,6 +96,14 @@ int launch_modulation_select(const KParams &P, int first_view, int n_views, uint
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_modulation_select, dim3(modulation_blocks(P), (unsigned)n_views), dim3(256), 0, (hipStream_t)stream, P, first_view, staging,
                        has_mask ? 1 : 0, thr);
+    return (int)hipGetLastError();
+}
+
+int launch_modulation_select_one(const KParams &P, int first_view, int n_views, uint8_t *staging, bool has_mask, double thr, int axis, void *stream)
+{
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_modulation_select_one, dim3(modulation_blocks(P), (unsigned)n_views), dim3(256), 0, (hipStream_t)stream, P, first_view, staging,
+                       has_mask ? 1 : 0, thr, axis);
     return (int)hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 #include "sl3d_block.h"
 #include "sl3d_device.h"
 #include "sl3d_internal.h"
+#include "sl3d_one_axis.h"
 #include "sl3d_subpixel.h"
 
 namespace sl3d {
@@ -120,6 +121,63 @@ __global__ __launch_bounds__(256) void k_subpixel_coords(const KParams P, int vi
     xy[2 * t + 1] = ys;
 }
 
+// The one-axis forms (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL; sl3d_one_axis.h): k_subpixel_one triangulates from the continuous
+// coordinate of axis AXIS alone -- the exactly determined ray-plane solve, no residual, nothing to reject -- and reads no plane of the other
+// axis; k_subpixel_coords_one leaves NaN in the other component.
+template <int AXIS, bool ANCHOR>
+__global__ __launch_bounds__(256) void k_subpixel_one(const KParams P, const DevCal C, int first_view, unsigned *__restrict__ partials)
+{
+    __shared__ unsigned s_cnt[4];
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;  // pixel of the view, padding columns included
+    const bool in_view = t < P.px_view_stride;
+    const size_t px = (size_t)(first_view + (int)blockIdx.y) * P.px_view_stride + (in_view ? t : 0);
+    const bool valid = in_view && P.valid[px] == 1;
+    const float nanv = __builtin_nanf("");
+    float x = nanv, y = nanv, z = nanv;
+    double X[3] = {0, 0, 0};
+    if (valid) {
+        const int row = (int)(t / (size_t)P.pitch), col = (int)(t - (size_t)row * P.pitch);
+        const int gx = P.col0 + col, gy = P.row0 + row;
+        const double s = subpixel_coordinate<ANCHOR>(P, AXIS, px, gx, gy);
+        double u, v;
+        undistort_reproject((double)gx, (double)gy, C.cam, u, v);
+        const double tp = one_axis_project(s, C.proj.K[AXIS == 0 ? 0 : 4], AXIS == 0 ? C.proj.ifx : C.proj.ify, AXIS == 0 ? C.proj.cx : C.proj.cy);
+        one_axis_solve(C.Ac, C.Ap, AXIS, u, v, tp, X);
+        x = (float)X[0];
+        y = (float)X[1];
+        z = (float)X[2];
+    }
+    if (in_view) {
+        P.ipoints[3 * px + 0] = X[0];
+        P.ipoints[3 * px + 1] = X[1];
+        P.ipoints[3 * px + 2] = X[2];
+        P.points[3 * px + 0] = x;
+        P.points[3 * px + 1] = y;
+        P.points[3 * px + 2] = z;
+    }
+    if (partials) {  // (a kernel argument: the whole block takes the branch or none of it)
+        unsigned c = valid ? 1u : 0u;
+        BLOCK_SUM(c, s_cnt);
+        if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = BLOCK_SUM_TOTAL(s_cnt);
+    }
+}
+
+template <int AXIS, bool ANCHOR>
+__global__ __launch_bounds__(256) void k_subpixel_coords_one(const KParams P, int view, double *__restrict__ xy)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= P.px_view_stride) return;
+    const size_t px = (size_t)view * P.px_view_stride + t;
+    const double nand = __builtin_nan("");
+    double s = nand;
+    if (P.valid_axis[AXIS][px] == 1) {
+        const int row = (int)(t / (size_t)P.pitch), col = (int)(t - (size_t)row * P.pitch);
+        s = subpixel_coordinate<ANCHOR>(P, AXIS, px, P.col0 + col, P.row0 + row);
+    }
+    xy[2 * t + AXIS] = s;
+    xy[2 * t + (1 - AXIS)] = nand;
+}
+
 unsigned subpixel_blocks(const KParams &P) { return (unsigned)((P.px_view_stride + 255) / 256); }
 
 int launch_subpixel(const KParams &P, const DevCal &C, int first_view, int n_views, double max_residual, float *residual, unsigned *partials,
@@ -142,6 +200,33 @@ int launch_subpixel_coords(const KParams &P, int view, double *xy, bool anchor, 
     const dim3 grid((unsigned)((P.px_view_stride + 255) / 256));
     if (anchor) hipLaunchKernelGGL(k_subpixel_coords<true>, grid, dim3(256), 0, (hipStream_t)stream, P, view, xy);
     else hipLaunchKernelGGL(k_subpixel_coords<false>, grid, dim3(256), 0, (hipStream_t)stream, P, view, xy);
+    return (int)hipGetLastError();
+}
+
+int launch_subpixel_one(const KParams &P, const DevCal &C, int axis, int first_view, int n_views, unsigned *partials, unsigned *counts, bool anchor,
+                        void *stream)
+{
+    (void)hipGetLastError();
+    const unsigned n_blocks = subpixel_blocks(P);
+    const dim3 grid(n_blocks, (unsigned)n_views);
+#define SL3D_ONE(AXIS, ANCHOR) hipLaunchKernelGGL((k_subpixel_one<AXIS, ANCHOR>), grid, dim3(256), 0, (hipStream_t)stream, P, C, first_view, partials)
+    if (axis == 0) { if (anchor) SL3D_ONE(0, true); else SL3D_ONE(0, false); }
+    else { if (anchor) SL3D_ONE(1, true); else SL3D_ONE(1, false); }
+#undef SL3D_ONE
+    int e = (int)hipGetLastError();
+    if (e || !partials) return e;
+    hipLaunchKernelGGL(k_subpixel_counts, dim3((unsigned)n_views), dim3(256), 0, (hipStream_t)stream, partials, n_blocks, counts);
+    return (int)hipGetLastError();
+}
+
+int launch_subpixel_coords_one(const KParams &P, int axis, int view, double *xy, bool anchor, void *stream)
+{
+    (void)hipGetLastError();
+    const dim3 grid((unsigned)((P.px_view_stride + 255) / 256));
+#define SL3D_ONE(AXIS, ANCHOR) hipLaunchKernelGGL((k_subpixel_coords_one<AXIS, ANCHOR>), grid, dim3(256), 0, (hipStream_t)stream, P, view, xy)
+    if (axis == 0) { if (anchor) SL3D_ONE(0, true); else SL3D_ONE(0, false); }
+    else { if (anchor) SL3D_ONE(1, true); else SL3D_ONE(1, false); }
+#undef SL3D_ONE
     return (int)hipGetLastError();
 }
 

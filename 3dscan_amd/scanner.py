@@ -18,6 +18,7 @@ SL3D_FLAG_SERIAL_LAUNCHES = 64
 SL3D_FLAG_SUBPIXEL = 128
 SL3D_FLAG_REPAIR_PERIODS = 256
 SL3D_FLAG_ANCHOR_PERIODS = 512
+SL3D_FLAG_ONLY_VERTICAL, SL3D_FLAG_ONLY_HORIZONTAL = 1024, 2048
 AXIS_VERTICAL, AXIS_HORIZONTAL = 0, 1
 PATTERN_FRINGE, PATTERN_GRAY, PATTERN_INVERSE_GRAY, PATTERN_BINARY = 0, 1, 2, 3
 VALID_VERTICAL, VALID_HORIZONTAL, VALID_MERGED = 0, 1, 2
@@ -372,7 +373,7 @@ class Scanner(_Handle):
     def __init__(self, width, height, proj_width, proj_height, n_gray_v, n_gray_h, fringe_width_v, fringe_width_h,
                  n_fringe=3, n_codes_v=0, n_codes_h=0, max_views=1, device=0, keep_stages=False,
                  full_size=None, origin=(0, 0), stream=None, eager_mask=False, serial_launches=False, subpixel=False, repaired=False,
-                 anchored=False):
+                 anchored=False, only_axis=None):
         """eager_mask: SL3D_FLAG_EAGER_MASK -- every mask is prepared by k_mask_prepare when it is set; by default a timed context
         defers masks of up to 4 views to the next launch over them (the fused kernel evaluates the selection itself).
         subpixel: SL3D_FLAG_SUBPIXEL -- run() (and process_views) leaves the sub-pixel scan and its residual plane: what the per-stage
@@ -384,14 +385,22 @@ class Scanner(_Handle):
         anchored: SL3D_FLAG_ANCHOR_PERIODS -- the sub-pixel scan (run(), triangulate_subpixel(), correspondences_subpixel()) takes the
         projector coordinates from the fringe period nearest the centre of the pixel's Gray cell, measured with pi instead of 22/7;
         validity, c_p_map and the stage planes stay as they are.  Needs subpixel=True and excludes repaired=True (and repair_periods()):
-        the library refuses the other combinations.  Groups: flags=SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS."""
+        the library refuses the other combinations.  Groups: flags=SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS.
+        only_axis: None, or the one pattern direction the scan is made from -- 0: SL3D_FLAG_ONLY_VERTICAL (the projector column), 1:
+        SL3D_FLAG_ONLY_HORIZONTAL (the row).  The frames of the other axis are never read (they need not be set, process_views does not
+        upload them), a pixel is the intersection of its camera ray with the plane of the decoded coordinate, and there are no
+        residuals.  Needs subpixel=True, an undistorted projector with a plain matrix, and excludes repaired=True; may be combined with
+        anchored=True.  Groups: flags=SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ONLY_VERTICAL."""
+        if only_axis not in (None, 0, 1):
+            raise ValueError("only_axis must be None, 0 or 1")
         self.L = load_library()
         fw, fh = full_size if full_size else (width, height)
         self.cfg = Config(width, height, fw, fh, origin[0], origin[1], proj_width, proj_height, n_fringe,
                           n_gray_v, n_gray_h, fringe_width_v, fringe_width_h, n_codes_v, n_codes_h,
                           max_views, device, (SL3D_FLAG_KEEP_STAGES if keep_stages else 0) | (SL3D_FLAG_EAGER_MASK if eager_mask else 0) |
                           (SL3D_FLAG_SERIAL_LAUNCHES if serial_launches else 0) | (SL3D_FLAG_SUBPIXEL if subpixel else 0) |
-                          (SL3D_FLAG_REPAIR_PERIODS if repaired else 0) | (SL3D_FLAG_ANCHOR_PERIODS if anchored else 0), stream)
+                          (SL3D_FLAG_REPAIR_PERIODS if repaired else 0) | (SL3D_FLAG_ANCHOR_PERIODS if anchored else 0) |
+                          {None: 0, 0: SL3D_FLAG_ONLY_VERTICAL, 1: SL3D_FLAG_ONLY_HORIZONTAL}[only_axis], stream)
         self.W, self.H = width, height
         self._h = C.c_void_p()
         rc = self.L.sl3d_create(C.byref(self.cfg), C.byref(self._h))

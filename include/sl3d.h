@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.18.0"
+#define SL3D_VERSION_STRING "0.19.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -144,7 +144,53 @@ enum sl3d_flags {
      *   sl3d_run_clouds stays refused as on every SL3D_FLAG_SUBPIXEL context.  sl3d_group_create hands the flag to its stripes.
      * What remains: a tie band of relative width 4e-4 per cell in which two positions share one phase, and pixels whose Gray code itself
      * is wrong at an edge.  A context without the flag behaves exactly as before. */
-    SL3D_FLAG_ANCHOR_PERIODS = 512u
+    SL3D_FLAG_ANCHOR_PERIODS = 512u,
+    /* (0.19.0) A ONE-AXIS scan: the sub-pixel scan of a SL3D_FLAG_SUBPIXEL context from ONE pattern direction.  A decoded projector column
+     * (or row) is a plane in space and a camera pixel is a ray: three equations, three unknowns.  SL3D_FLAG_ONLY_VERTICAL codes axis a = 0
+     * (the vertical-stripe patterns: the projector COLUMN), SL3D_FLAG_ONLY_HORIZONTAL axis a = 1 (the ROW); b is the other axis.  The
+     * frame layout, planes_per_view and the setters do not change; planes of axis b may be set, but no frame of the other axis is read by
+     * anything (sl3d_process_views and sl3d_group_process_views upload the planes of axis a alone, their contiguity test runs over those,
+     * and the pointers of axis b may be NULL).  Per pixel of a view, in IEEE double, fma where written, nothing else contracted:
+     *   1. sel = the valid byte of stage 3's boundary removal (the same byte for both axes).
+     *   2. stages 3 and 4 of axis a as always: w_a, code_a, unw_a.
+     *   3. stage 5: ok = the correspondence of axis a alone (the same lrint argument, FE_INVALID rule and range test); merged valid byte
+     *      = sel && ok.  c_p_map[.][a] = the integer, c_p_map[.][b] = -1 where the pixel is valid; both 0 elsewhere.
+     *   4. s = fringe_width_a * (unw_a / ((2.0 * 22.0) / 7.0)), the double stage 5 hands to lrint -- with SL3D_FLAG_ANCHOR_PERIODS the
+     *      anchored coordinate of axis a where that flag's rule applies.
+     *   5. f = Kp[0], c = Kp[2] (a = 0) or Kp[4], Kp[5] (a = 1):  t = fma(f, (s - c) * (1.0 / f), c)
+     *   6. (u, v) = the undistorted camera point as in stage 7; Ac, Ap the 3 x 4 projection matrices:
+     *        r0[j] = fma(-u, Ac[2][j], Ac[0][j])   f0 = fma(Ac[2][3], u, -Ac[0][3])        j = 0..2
+     *        r1[j] = fma(-v, Ac[2][j], Ac[1][j])   f1 = fma(Ac[2][3], v, -Ac[1][3])
+     *        r2[j] = fma(-t, Ap[2][j], Ap[a][j])   f2 = fma(Ap[2][3], t, -Ap[a][3])
+     *        c0 = r1 x r2, c1 = r2 x r0, c2 = r0 x r1, where (p x q)[0] = fma(p[1], q[2], -(p[2] * q[1])), [1] = fma(p[2], q[0],
+     *        -(p[0] * q[2])), [2] = fma(p[0], q[1], -(p[1] * q[0]))
+     *        det = fma(r0[0], c0[0], fma(r0[1], c0[1], r0[2] * c0[2]))
+     *        X[j] = fma(f0, c0[j], fma(f1, c1[j], f2 * c2[j])) * (1.0 / det);  det == 0: X = 0 and the valid byte stays, as in stage 7
+     *      (X = adj(P) F / det(P) of the 3 x 3 system whose rows are r0, r1, r2)
+     *   7. points = (float)X where valid, NaN and valid 0 elsewhere; intersection_points (KEEP_STAGES) = X where valid, 0 elsewhere.
+     * An exactly determined solve has no residual: such a context has no residual plane, sl3d_get_residuals returns SL3D_E_UNSUPPORTED,
+     * and so does sl3d_triangulate_subpixel with a finite max_residual (nothing changes); with +infinity it works, counts = (triangulated,
+     * 0).  sl3d_get_correspondences_subpixel returns s in component a and NaN in component b, both NaN where the valid byte of axis a is
+     * not 1.  sl3d_set_masks_modulated tests the modulation of axis a alone.
+     *   Without KEEP_STAGES: ONE launch of a kernel of its own (k_one_axis<a, anchored>: the frames of axis a in; points and valid out) on
+     *   the context's stream, behind the preparation of whatever masks are still deferred -- no launch lanes, every launch counts as
+     *   on-stream, sl3d_camera_table_bytes_per_pixel is 0, sl3d_fused_kernel_name / sl3d_last_fused_kernel_name report
+     *   "sl3d::k_one_axis<0, false>", "<0, true>", "<1, false>" or "<1, true>".  The result is bit for bit the staged route's.
+     *   With KEEP_STAGES: sl3d_run() enqueues stages 3 and 4 of axis a, the one-axis stage 5 and the one-axis stage 7 per view (not the
+     *   parity kernel, which reads both axes); sl3d_compute_c_p_map, sl3d_triangulate_subpixel and sl3d_get_correspondences_subpixel
+     *   take their one-axis forms.  SL3D_E_UNSUPPORTED, nothing touched: sl3d_compute_wrapped_phase, sl3d_unwrap_phase and
+     *   sl3d_repair_periods on axis b, and sl3d_triangulate (the integer solve).  The stage getters of axis b hand out planes that
+     *   were never written.
+     *   Refused with SL3D_E_UNSUPPORTED by sl3d_create and sl3d_group_create before a device is touched: both flags together; either
+     *   without SL3D_FLAG_SUBPIXEL; either with SL3D_FLAG_REPAIR_PERIODS (the fused repair has no one-axis form).  By
+     *   sl3d_set_calibration on such a context: a projector with any distortion coefficient != 0, or a Kp that is not plain (Kp[1],
+     *   Kp[3], Kp[6], Kp[7] != 0 or Kp[8] != 1) -- with the other coordinate unknown a column is then a curve and not a line; the
+     *   previous calibration stays in force.  sl3d_run_clouds stays refused as on every SL3D_FLAG_SUBPIXEL context.
+     * sl3d_group_create hands the flag to its stripes; the rule is pointwise in frame coordinates, so stripes agree with the whole frame.
+     * Where the baseline between camera and projector is horizontal the row carries almost no depth: SL3D_FLAG_ONLY_HORIZONTAL is for
+     * rigs with a vertical baseline.  A context without these flags behaves exactly as before. */
+    SL3D_FLAG_ONLY_VERTICAL = 1024u,
+    SL3D_FLAG_ONLY_HORIZONTAL = 2048u
     /* (8u was SL3D_FLAG_CLOUDS_LOOKBACK until 0.3: contiguous clouds in one pass by a decoupled look-back between tiles.  Removed
      * in 0.4 -- every tile waited for its predecessors, 0.53 of the roofline against 0.67 for the segmented clouds; a consumer
      * that wants one contiguous device array asks sl3d_get_cloud_counts for it.) */
@@ -330,8 +376,8 @@ int sl3d_triangulate(sl3d_ctx *ctx, int view);
  * KEEP_STAGES context the same planes exist, so sl3d_repair_periods + sl3d_compute_c_p_map + sl3d_triangulate works there too.
  * counts[0] = repaired, counts[1] = unrepairable pixels of this pass; counts may be NULL (then the call stays asynchronous), otherwise the
  * call synchronises.  SL3D_E_INVALID_ARG for a bad view, an axis outside {0, 1} or a radius outside 1..8; SL3D_E_STATE without
- * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes, or on a SL3D_FLAG_ANCHOR_PERIODS context (see the flag).  A
- * refused call changes nothing. */
+ * SL3D_FLAG_KEEP_STAGES; SL3D_E_UNSUPPORTED if the axis has no Gray planes, on a SL3D_FLAG_ANCHOR_PERIODS context (see the flag), or on
+ * the axis a SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL context does not code.  A refused call changes nothing. */
 int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t counts[2]);
 
 /* ---- sub-pixel triangulation with a reprojection residual (0.15.0; needs SL3D_FLAG_KEEP_STAGES -- the timed mode has it as SL3D_FLAG_SUBPIXEL) --
@@ -360,7 +406,9 @@ int sl3d_repair_periods(sl3d_ctx *ctx, int view, int axis, int radius, uint32_t 
  * entry), counts[2k + 1] = those of them rejected; then a second small launch adds them up and the call synchronises.
  * SL3D_E_INVALID_ARG for bad views or a max_residual that is NaN or <= 0 (+infinity: no pixel is rejected); SL3D_E_STATE without
  * SL3D_FLAG_KEEP_STAGES or before sl3d_set_calibration.  A refused call changes nothing.
- * On a SL3D_FLAG_ANCHOR_PERIODS context (xs, ys) of step 1 are the anchored coordinates (see the flag); everything else is as above. */
+ * On a SL3D_FLAG_ANCHOR_PERIODS context (xs, ys) of step 1 are the anchored coordinates (see the flag); everything else is as above.
+ * On a SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL context: the exactly determined one-axis solve instead (see the flags) -- no
+ * residual plane; a finite max_residual is SL3D_E_UNSUPPORTED and changes nothing; counts = (triangulated, 0). */
 int sl3d_triangulate_subpixel(sl3d_ctx *ctx, int first_view, int n_views, double max_residual, uint32_t *counts);
 /* The residual plane of a view, out[row * stride_elems + col]: NaN on every pixel the last sl3d_triangulate_subpixel over the view did
  * not triangulate (and on a view none has run over).  SL3D_E_STATE before the context's first sl3d_triangulate_subpixel.
@@ -370,7 +418,9 @@ int sl3d_get_residuals(sl3d_ctx *ctx, int view, float *out, size_t stride_elems)
 /* (xs, ys) of step 1 for every window pixel, xy[(row * stride_elems + col) * 2 + {0, 1}], bit for bit those expressions; NaN where
  * either per-axis valid byte is not 1 (the pixels stage 5 does not form them for).  Computed from the stage-4 planes as they are: no
  * sl3d_compute_c_p_map is needed, a rejection does not show.  SL3D_E_STATE without SL3D_FLAG_KEEP_STAGES.  On a
- * SL3D_FLAG_ANCHOR_PERIODS context: the anchored coordinates, bit for bit the flag's definition (same NaN pattern). */
+ * SL3D_FLAG_ANCHOR_PERIODS context: the anchored coordinates, bit for bit the flag's definition (same NaN pattern).  On a one-axis
+ * context (SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL): the coordinate of the coded axis, NaN in the other component.
+ * sl3d_get_residuals on such a context: SL3D_E_UNSUPPORTED, there are none. */
 int sl3d_get_correspondences_subpixel(sl3d_ctx *ctx, int view, double *xy, size_t stride_elems);
 
 /* ---- the fused hot path ------------------------------------------------------------------- */
