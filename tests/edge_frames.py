@@ -1,0 +1,186 @@
+"""The inputs of the edge-frame tests of the sub-pixel launches (tests/test_edge_frames.py on the CPU, tests/test_gpu_subpixel_edges.py on
+the device).  Inputs only: this module imports no scanner (oracle_scan runs the CPU oracle on them, once per case).
+
+FRAMES   `random` (uniform random bytes on both axes: every code, Gray ties, correspondences outside the projector), `flat_17`, `flat_0`,
+         `flat_255` (every plane one value: pos == inv on every Gray plane, atan2(0, 0)), `noise3` (make_capture(..., noise=3) of a
+         plane that leaves part of the frame unlit).
+SHAPES   `base`: the 101 x 37 full frame; the ragged full frames 64 x 5, 19 x 64 and 130 x 3 of
+         test_gpu_stage_parity.py::test_ragged_sizes_random_masks; `window`: 70 x 9 at (37, 5) of a 320 x 240 frame.
+         The projector is 300 x 200 with N = (7, 6) Gray planes and fringe widths (4, 6): both extents are smaller than fw * 2^N (512 and
+         384), so decoded coordinates outside the projector occur and are rejected.
+RIGS     rig(0, ...): synth_rig (a horizontal baseline); rig(1, ...): the vertical-baseline variant of tests/one_axis_cases.py.  The
+         two-axis scans use the rig of axis 0.
+MASKS    random_mask(rng, p), full-frame; the 0.9 mask holds the value 2 on 5 % of its pixels (only the value 1 selects).
+         view_masks(): three masks of the base shape whose selections differ per quad and lane (see there).
+
+`selected(mask)` is stage 3's boundary removal in closed form (tests/test_oracle.py::closed_form_valid): the valid byte every sub-pixel
+kernel masks with.  tests/test_edge_frames.py holds it against the oracle on these masks."""
+import functools
+import importlib
+import zlib
+
+import numpy as np
+
+PW, PH = 300, 200
+N = (7, 6)
+FW = (4, 6)
+EXTENT = (PW, PH)
+NOISE_PLANE = (40.0, 0.05, 0.05)   # of `noise3`: a fifth of the frame sees no projector pixel (random decodes, rejected correspondences)
+VIEW_PLANES = ((0.0, 0.05, 0.05), (4.0, 0.02, -0.04), (-6.0, -0.03, 0.06))
+# name -> ((W, H) of the window, (col0, row0), (W, H) of the frame)
+SHAPES = {
+    "base": ((101, 37), (0, 0), (101, 37)),
+    "64x5": ((64, 5), (0, 0), (64, 5)),
+    "19x64": ((19, 64), (0, 0), (19, 64)),
+    "130x3": ((130, 3), (0, 0), (130, 3)),
+    "window": ((70, 9), (37, 5), (320, 240)),
+}
+FRAMES = ("random", "flat_17", "flat_0", "flat_255", "noise3")
+# (frames, shape, p of the random mask): every frame set on the base shape with every pixel selected, the frame's border lines included;
+# `random` on the base shape under the mask that holds the value 2, on the ragged shapes and on the window, each under one random mask
+BASE_CASES = tuple((f, "base", 1.0) for f in ("random", "flat_17", "noise3"))
+RAGGED_CASES = (("random", "base", 0.9), ("random", "64x5", 0.5), ("random", "19x64", 0.9), ("random", "130x3", 1.0), ("random", "window", 0.9))
+CASES = BASE_CASES + RAGGED_CASES
+
+
+def _syn():
+    return importlib.import_module("3dscan_amd.synth")
+
+
+def _seed(*what):
+    return zlib.crc32(repr(what).encode())
+
+
+def rig(axis, W, H, PW=PW, PH=PH):
+    """The calibration dict of a W x H frame for one coded axis."""
+    syn = _syn()
+    cal = {k: np.array(v, dtype=np.float64).copy() for k, v in syn.synth_rig(W, H, PW, PH).items()}
+    if axis == 1:
+        cal["rp"] = np.array([0.42, 0.027, -0.016])
+        cal["tp"] = np.array([0.0, 0.0, 220.0]) - syn.rodrigues(cal["rp"]) @ np.array([58.0, 36.0, 0.0])
+    return cal
+
+
+def random_mask(rng, p, shape):
+    """A full-frame mask (H, W): 1 with probability p; the 0.9 mask holds the value 2 on 5 % of its pixels."""
+    mask = (rng.random(shape) < p).astype(np.uint8)
+    if p == 0.9:
+        mask[rng.random(shape) < 0.05] = 2
+    return mask
+
+
+def selected(mask):
+    """The valid byte stage 3 leaves for a full-frame mask (uint8 0 / 1): the scan-order dependent boundary removal in the closed form the
+    kernels implement -- the frame's border lines keep their selection; it is not an erosion."""
+    from test_oracle import closed_form_valid
+    return closed_form_valid(mask).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def frames(name, shape, rig_axis=0, plane=None, noise=3, view=0):
+    """(planes_v, planes_h): lists of uint8 planes of the window, fringe + Gray + inverse Gray per axis."""
+    (W, H), (col0, row0), full = SHAPES[shape]
+    counts = [3 + 2 * n for n in N]
+    if name == "random":
+        rng = np.random.default_rng(_seed(name, shape))
+        return tuple([rng.integers(0, 256, (H, W), dtype=np.uint8) for _ in range(c)] for c in counts)
+    if name.startswith("flat_"):
+        return tuple([np.full((H, W), int(name[5:]), np.uint8) for _ in range(c)] for c in counts)
+    assert name == "noise3"
+    cap = _syn().make_capture(W, H, PW, PH, N[0], N[1], FW[0], FW[1], cal=rig(rig_axis, *full), plane=NOISE_PLANE if plane is None else plane, noise=noise, view=view,
+                              col0=col0, row0=row0, full=full)
+    return cap["planes_v"], cap["planes_h"]
+
+
+@functools.lru_cache(maxsize=None)
+def case(name, shape, p, rig_axis=0):
+    """dict(W, H, origin, full, planes (v, h), mask (full frame), cal (tuple)) of one case.  Nothing in it is ever written to."""
+    (W, H), origin, full = SHAPES[shape]
+    mask = random_mask(np.random.default_rng(_seed("mask", shape, p)), p, (full[1], full[0]))
+    return dict(W=W, H=H, origin=origin, full=full, planes=frames(name, shape, rig_axis), mask=mask, cal=_syn().cal_tuple(rig(rig_axis, *full)))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_scan(name, shape, p, rig_axis=0):
+    """The oracle's planes of a case, both axes decoded, computed once: dict(w, code, unw, valid_axis (pairs v, h), valid, c_p_map, ipoints,
+    A_cam, A_proj).  A window is run as the oracle's own image at its origin, under the window of the mask: compare on inner(shape)."""
+    from oracle.oracle import Oracle
+    c = case(name, shape, p, rig_axis)
+    o = Oracle(c["W"], c["H"], PW, PH, N[0], N[1], FW[0], FW[1], col0=c["origin"][0], row0=c["origin"][1])
+    o.set_mask(window(c["mask"], shape))
+    o.set_calibration(*c["cal"])
+    o.run_scan(*c["planes"])
+    A, B = o.projection_matrices()
+    out = dict(w=(o.wrapped_phi(0), o.wrapped_phi(1)), code=(o.code(0), o.code(1)), unw=(o.unwrapped_phi(0), o.unwrapped_phi(1)),
+               valid_axis=(o.valid_map(0), o.valid_map(1)), valid=o.valid_map(2), c_p_map=o.c_p_map(), ipoints=o.intersection_points(), A_cam=A, A_proj=B)
+    o.close()
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def restated_one_axis(name, shape, p, axis, anchored):
+    """tests/one_axis_reference.py::scan on the oracle's planes of the coded axis (the rig of that axis)."""
+    import one_axis_reference as OR
+    c, o = case(name, shape, p, axis), oracle_scan(name, shape, p, axis)
+    return OR.scan(o["w"][axis], o["code"][axis], o["unw"][axis], o["valid_axis"][axis], c["cal"], o["A_cam"], o["A_proj"], axis, FW[axis], EXTENT[axis], N[axis], 3,
+                   c["origin"], c["full"], anchored)
+
+
+@functools.lru_cache(maxsize=None)
+def restated_two_axis(name, shape, p, anchored):
+    """tests/subpixel_reference.py::triangulate at the plain or the anchored coordinates of the oracle's planes (the rig of axis 0):
+    its dict, with xy (the coordinates) added."""
+    import anchor_reference as AR
+    import subpixel_reference as SR
+    c, o = case(name, shape, p), oracle_scan(name, shape, p)
+    xy = AR.correspondences(o["w"], o["code"], o["unw"], o["valid_axis"], FW, 3, N, c["origin"], c["full"]) if anchored else \
+        SR.correspondences(*o["unw"], *o["valid_axis"], *FW)
+    return dict(SR.triangulate(xy, o["valid"], c["cal"], o["A_cam"], o["A_proj"], c["origin"]), xy=xy)
+
+
+def window(a, shape):
+    """A full-frame array cut to the window of a shape."""
+    (W, H), (col0, row0), _ = SHAPES[shape]
+    return np.ascontiguousarray(a[row0:row0 + H, col0:col0 + W])
+
+
+def inner(shape):
+    """(H, W) bool: the window without the 3 pixels inside each edge that is not an edge of the frame (tests/fuzz_parity.py): there the
+    oracle, which sees the window as its own image, leaves what the device leaves."""
+    (W, H), (col0, row0), (fullW, fullH) = SHAPES[shape]
+    out = np.zeros((H, W), bool)
+    lo_r, hi_r = (0 if row0 == 0 else 3), (H if row0 + H == fullH else H - 3)
+    lo_c, hi_c = (0 if col0 == 0 else 3), (W if col0 + W == fullW else W - 3)
+    out[lo_r:hi_r, lo_c:hi_c] = True
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def view_captures(rig_axis):
+    """Three captures of the base shape that differ (VIEW_PLANES, noise 2 so that the modulation spreads): [(planes_v, planes_h)]."""
+    return [frames("noise3", "base", rig_axis, plane, 2, v) for v, plane in enumerate(VIEW_PLANES)]
+
+
+C_ROWS = (3, 9, 15, 21, 27, 33)
+C_QUADS = (1, 5, 9, 13, 16, 20, 23)
+
+
+@functools.lru_cache(maxsize=None)
+def view_masks():
+    """(A, B, C), masks of the base shape (101 x 37), for three views of one launch.
+    A: the left two thirds of the columns [0, 67) on rows [0, 26);  B: the right two thirds [34, 101) on rows [11, 37): no edge on a
+    multiple of 4, and two corners of the frame that neither selects.
+    C: 40 blocks of 2 x 3 ones whose upper middle pixels lie in 40 different quads, at lane positions 0, 1, 2, 3 in turn: after stage 3's
+    boundary removal exactly that pixel of each block is selected -- one pixel in each of 40 quads.
+    By construction (tests/test_edge_frames.py asserts it on selected()): some quads are selected by exactly one view, in the corners by
+    C alone -- the LAST view of a launch over A, B, C, and after swapping A and C it is A alone in the left third; at A's right edge a
+    quad holds lanes of A and another lane of C."""
+    W, H = SHAPES["base"][0]
+    A, B, C = (np.zeros((H, W), np.uint8) for _ in range(3))
+    A[0:26, 0:67] = 1
+    B[11:37, 34:101] = 1
+    centres = [(r, 4 * q) for r in C_ROWS for q in C_QUADS][:40]
+    for i, (r, c0) in enumerate(centres):
+        c = c0 + i % 4
+        C[r:r + 2, c - 1:c + 2] = 1
+    return A, B, C
