@@ -4,6 +4,7 @@
 // HIP kernels; there is no CPU implementation of the path in this library.
 #include "sl3d_anchor.h"
 #include "sl3d_one_axis.h"
+#include "sl3d_direct_gray.h"
 #include "sl3d_capi_internal.h"
 
 static thread_local std::string g_create_err;
@@ -82,6 +83,7 @@ static void build_atan_tables(std::vector<float> &tab)
 }
 
 static_assert(SL3D_FLAG_ONLY_VERTICAL == SL3D_ONE_AXIS_VERTICAL_BIT && SL3D_FLAG_ONLY_HORIZONTAL == SL3D_ONE_AXIS_HORIZONTAL_BIT, "one_axis_of_flags reads these bits");
+static_assert(SL3D_FLAG_DIRECT_GRAY == SL3D_DIRECT_GRAY_BIT, "sl3d_direct_gray.h names this bit");
 
 extern "C" int sl3d_create(const sl3d_config *cfg, sl3d_ctx **out)
 try {
@@ -108,6 +110,9 @@ try {
     if (const char *why = one_axis_refusal((c.flags & SL3D_FLAG_ONLY_VERTICAL) != 0, (c.flags & SL3D_FLAG_ONLY_HORIZONTAL) != 0, (c.flags & SL3D_FLAG_SUBPIXEL) != 0,
                                            (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
         return fail(nullptr, SL3D_E_UNSUPPORTED, why);
+    // (likewise, sl3d_direct_gray.h)
+    if (const char *why = direct_gray_refusal((c.flags & SL3D_FLAG_DIRECT_GRAY) != 0, (c.flags & SL3D_FLAG_SUBPIXEL) != 0, (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
+        return fail(nullptr, SL3D_E_UNSUPPORTED, why);
     if (c.n_codes_v <= 0) c.n_codes_v = (c.proj_width + c.fringe_width_v - 1) / c.fringe_width_v;
     if (c.n_codes_h <= 0) c.n_codes_h = (c.proj_height + c.fringe_width_h - 1) / c.fringe_width_h;
 
@@ -127,6 +132,7 @@ try {
     x->repair = (c.flags & SL3D_FLAG_REPAIR_PERIODS) != 0;
     x->anchor = (c.flags & SL3D_FLAG_ANCHOR_PERIODS) != 0;
     x->one_axis = one_axis_of_flags(c.flags);
+    x->direct_gray = (c.flags & SL3D_FLAG_DIRECT_GRAY) != 0;
 #define CREATE_CHK(call)                                                                 \
     do {                                                                                 \
         hipError_t e_ = (call);                                                          \

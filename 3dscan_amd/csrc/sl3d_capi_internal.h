@@ -128,8 +128,18 @@ inline bool own_kernel_route(const sl3d_ctx *x) { return subpixel_fused_route(x)
 // ... and of a one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL; always with SL3D_FLAG_SUBPIXEL, never with the repair: it is a
 // subpixel_fused_route whose kernel is k_one_axis.  With SL3D_FLAG_KEEP_STAGES: stages 3 and 4 of the coded axis, the one-axis stage 5 and 7)
 inline bool one_axis_route(const sl3d_ctx *x) { return x->one_axis >= 0 && subpixel_fused_route(x); }
+// ... and of a SL3D_FLAG_DIRECT_GRAY context (always with SL3D_FLAG_SUBPIXEL, never with the repair; with or without a one-axis flag): it is
+// a subpixel_fused_route whose kernel is k_direct_gray.  With SL3D_FLAG_KEEP_STAGES: stage 3, the direct stage 4 (launch_stage4), stage 5 and
+// the sub-pixel launch of the coded axes
+inline bool direct_gray_route(const sl3d_ctx *x) { return x->direct_gray && subpixel_fused_route(x); }
+// stage 4 of one axis of a view on the context's stream: by the direct rule on a SL3D_FLAG_DIRECT_GRAY context (k_unwrap itself is untouched)
+inline int launch_stage4(const sl3d_ctx *x, int view, int axis)
+{
+    return x->direct_gray ? launch_unwrap_direct(x->P, view, axis, x->stream) : launch_unwrap(x->P, view, axis, x->stream);
+}
 inline const char *own_kernel_name(const sl3d_ctx *x)
 {
+    if (direct_gray_route(x)) return SL3D_DIRECT_GRAY_NAME(x->one_axis >= 0 ? x->one_axis : 2, x->anchor);
     if (one_axis_route(x)) return SL3D_ONE_AXIS_NAME(x->one_axis, x->anchor);
     if (!repair_fused_route(x)) return x->anchor ? SL3D_SUBPIXEL_FUSED_ANCHOR_NAME : SL3D_SUBPIXEL_FUSED_NAME;
     return x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;

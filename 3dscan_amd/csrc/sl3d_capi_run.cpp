@@ -41,7 +41,7 @@ try {
     if (axis != 0 && axis != 1) return fail(x, SL3D_E_INVALID_ARG, "axis must be 0 or 1");
     if ((rc = one_axis_serves(x, axis, "unwrap_phase"))) return rc;
     ON_DEVICE(x);
-    return launched(x, launch_unwrap(x->P, view, axis, x->stream));
+    return launched(x, launch_stage4(x, view, axis));  // (a SL3D_FLAG_DIRECT_GRAY context: the direct rule)
 }
 SL3D_CATCH(x)
 
@@ -157,6 +157,9 @@ static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int 
 // A one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL, one_axis_route): the timed one launches k_one_axis, the parity one the staged
 // one-axis route -- k_wrap, k_unwrap of the coded axis and k_corr_one per view, then k_subpixel_one over the views; never the parity k_fused,
 // which reads both axes.
+// A SL3D_FLAG_DIRECT_GRAY context (direct_gray_route): the timed one launches k_direct_gray -- its one-axis or its two-axis form --, the parity
+// one k_wrap, k_unwrap_direct and stage 5 per view and then the sub-pixel launch over the views; never the parity k_fused, which reads the
+// inverse planes.
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
     if (!x->subpixel && !x->repair) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
@@ -164,7 +167,9 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
     if (own_kernel_route(x)) {
         if ((rc = flush_masks(x, first_view, n_views))) return rc;
         x->launches_on_stream++;
-        if (one_axis_route(x)) rc = launched(x, launch_one_axis(x->P, x->d_cal, x->one_axis, first_view, n_views, x->anchor, x->stream));
+        if (direct_gray_route(x))
+            rc = launched(x, launch_direct_gray(x->P, x->d_cal, x->one_axis >= 0 ? x->one_axis : 2, first_view, n_views, x->d_residual, x->anchor, x->stream));
+        else if (one_axis_route(x)) rc = launched(x, launch_one_axis(x->P, x->d_cal, x->one_axis, first_view, n_views, x->anchor, x->stream));
         else if (repair_fused_route(x)) rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream));
         else rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->anchor, x->stream));
         if (!rc) x->own_kernel_ran = true;
@@ -173,10 +178,21 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
         x->launches_on_stream++;  // (one per call, as the parity launch counts)
         for (int view = first_view; view < first_view + n_views; view++) {
             if ((rc = launched(x, launch_wrap(x->P, view, x->one_axis, x->stream)))) return rc;
-            if ((rc = launched(x, launch_unwrap(x->P, view, x->one_axis, x->stream)))) return rc;
+            if ((rc = launched(x, launch_stage4(x, view, x->one_axis)))) return rc;
             if ((rc = launched(x, launch_corr_one(x->P, view, x->one_axis, x->stream)))) return rc;
         }
         return launched(x, launch_subpixel_one(x->P, x->C, x->one_axis, first_view, n_views, nullptr, nullptr, x->anchor, x->stream));
+    } else if (x->direct_gray) {  // the staged two-axis route of a SL3D_FLAG_DIRECT_GRAY context: not the parity kernel, which reads the inverse planes
+        if ((rc = flush_masks(x, first_view, n_views))) return rc;
+        x->launches_on_stream++;  // (one per call, as the parity launch counts)
+        for (int view = first_view; view < first_view + n_views; view++) {
+            for (int axis = 0; axis < 2; axis++) {
+                if ((rc = launched(x, launch_wrap(x->P, view, axis, x->stream)))) return rc;
+                if ((rc = launched(x, launch_stage4(x, view, axis)))) return rc;
+            }
+            if ((rc = launched(x, launch_corr(x->P, view, x->stream)))) return rc;
+        }
+        rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->anchor, x->stream));
     } else {
         if ((rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap))) return rc;
         if (x->repair) {
@@ -487,11 +503,12 @@ int sl3d_process_views_enqueue(sl3d_ctx *x, int n_views, const uint8_t *const *p
     // every pointer is checked BEFORE anything is enqueued: an error return must never leave copies running against
     // buffers the caller is about to free
     // (a one-axis context uploads the planes of its coded axis alone: the pointers of the other axis are not looked at, they may be NULL)
-    int p_first, p_count;
-    frame_plane_range(x, &p_first, &p_count);
+    // (a SL3D_FLAG_DIRECT_GRAY context uploads the F fringe and N Gray planes of each coded axis: the pointers of the inverse planes likewise)
+    int p_first[2], p_count[2];
+    const int n_runs = frame_plane_runs(x, p_first, p_count);
     for (int v = 0; v < n_views; v++)
-        for (int p = p_first; p < p_first + p_count; p++)
-            if (!planes[(size_t)v * ppv + p]) return fail(x, SL3D_E_INVALID_ARG, "process_views: null plane");
+        for (int p = 0; p < ppv; p++)
+            if (!planes[(size_t)v * ppv + p] && frame_plane_read(x, p)) return fail(x, SL3D_E_INVALID_ARG, "process_views: null plane");
     for (int v = 0; v < n_views; v++) {
         const int slot = v % S;
         // the slot's previous occupant must have been computed (frames free) and downloaded (results free)
@@ -499,17 +516,20 @@ int sl3d_process_views_enqueue(sl3d_ctx *x, int n_views, const uint8_t *const *p
             HIPCHK(x, hipStreamWaitEvent(x->s_h2d, x->ev_done[(size_t)slot], 0));
             HIPCHK(x, hipStreamWaitEvent(x->stream, x->ev_down[(size_t)slot], 0));
         }
-        // a view whose planes are back to back in host memory, in the device's own pitch, goes up as ONE copy
-        bool contiguous = stride == (size_t)P.pitch && (size_t)P.W == (size_t)P.pitch;
-        for (int p = p_first + 1; p < p_first + p_count; p++)
-            if (planes[(size_t)v * ppv + p] != planes[(size_t)v * ppv + p - 1] + P.plane_stride) contiguous = false;
-        if (contiguous) {
-            HIPCHK(x, hipMemcpyAsync(x->d_frames + (size_t)slot * P.view_stride + (size_t)p_first * P.plane_stride, planes[(size_t)v * ppv + p_first],
-                                     (size_t)p_count * P.plane_stride, hipMemcpyHostToDevice, x->s_h2d));
-        } else {
-            for (int p = p_first; p < p_first + p_count; p++)
-                HIPCHK(x, hipMemcpy2DAsync(x->d_frames + (size_t)slot * P.view_stride + (size_t)p * P.plane_stride, P.pitch,
-                                           planes[(size_t)v * ppv + p], stride, P.W, P.H, hipMemcpyHostToDevice, x->s_h2d));
+        // a view whose planes are back to back in host memory, in the device's own pitch, goes up as ONE copy (per run of planes read)
+        for (int r = 0; r < n_runs; r++) {
+            const int first = p_first[r], count = p_count[r];
+            bool contiguous = stride == (size_t)P.pitch && (size_t)P.W == (size_t)P.pitch;
+            for (int p = first + 1; p < first + count; p++)
+                if (planes[(size_t)v * ppv + p] != planes[(size_t)v * ppv + p - 1] + P.plane_stride) contiguous = false;
+            if (contiguous) {
+                HIPCHK(x, hipMemcpyAsync(x->d_frames + (size_t)slot * P.view_stride + (size_t)first * P.plane_stride, planes[(size_t)v * ppv + first],
+                                         (size_t)count * P.plane_stride, hipMemcpyHostToDevice, x->s_h2d));
+            } else {
+                for (int p = first; p < first + count; p++)
+                    HIPCHK(x, hipMemcpy2DAsync(x->d_frames + (size_t)slot * P.view_stride + (size_t)p * P.plane_stride, P.pitch,
+                                               planes[(size_t)v * ppv + p], stride, P.W, P.H, hipMemcpyHostToDevice, x->s_h2d));
+            }
         }
         HIPCHK(x, hipEventRecord(x->ev_up[(size_t)slot], x->s_h2d));
         HIPCHK(x, hipStreamWaitEvent(x->stream, x->ev_up[(size_t)slot], 0));

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/sl3d.h"
+#include "sl3d_direct_gray.h"
 #include "sl3d_internal.h"
 #include "sl3d_lanes.h"
 
@@ -31,6 +32,9 @@ struct sl3d_ctx {
     // SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL (only with subpixel, never with repair: sl3d_create): the coded axis, 0 or 1, of a
     // one-axis context (sl3d_one_axis.h) -- no frame and no stage plane of the other axis is read, there is no residual plane; -1 otherwise
     int one_axis = -1;
+    // SL3D_FLAG_DIRECT_GRAY (only with subpixel, never with repair: sl3d_create): stage 4 thresholds a Gray frame against the fringe mean
+    // (sl3d_direct_gray.h) -- no inverse Gray plane is read or uploaded
+    bool direct_gray = false;
     bool own_kernel_ran = false;  // own_kernel_route: a launch has gone out (sl3d_last_fused_kernel_name)
     bool own_stream = false;
     hipStream_t stream = nullptr;
@@ -251,10 +255,31 @@ __attribute__((visibility("hidden"))) int sl3d_lanes_join(sl3d_ctx *x);
         if (join_rc_) return join_rc_;                \
     } while (0)
 
-// the planes of a view a context reads, [first, first + count) of planes_per_view: all of them, or those of a one-axis context's coded axis
-inline void frame_plane_range(const sl3d_ctx *x, int *first, int *count)
+// the planes of a view a context reads, as runs [first[i], first[i] + count[i]) of planes_per_view; returns their number, 1 or 2.  All planes
+// in one run, or those of a one-axis context's coded axis; on a SL3D_FLAG_DIRECT_GRAY context one run per coded axis, its F fringe and N Gray
+// planes without the N inverse planes behind them
+inline int frame_plane_runs(const sl3d_ctx *x, int first[2], int count[2])
 {
     const sl3d::KParams &P = x->P;
-    *first = x->one_axis == 1 ? P.F + 2 * P.Nv : 0;
-    *count = x->one_axis == 0 ? P.F + 2 * P.Nv : x->one_axis == 1 ? P.F + 2 * P.Nh : P.planes_per_view;
+    if (!x->direct_gray) {
+        first[0] = x->one_axis == 1 ? P.F + 2 * P.Nv : 0;
+        count[0] = x->one_axis == 0 ? P.F + 2 * P.Nv : x->one_axis == 1 ? P.F + 2 * P.Nh : P.planes_per_view;
+        return 1;
+    }
+    int n = 0;
+    for (int axis = 0; axis < 2; axis++) {
+        if (x->one_axis >= 0 && x->one_axis != axis) continue;
+        first[n] = axis == 0 ? 0 : P.F + 2 * P.Nv;
+        count[n++] = direct_gray_planes(P.F, axis == 0 ? P.Nv : P.Nh);
+    }
+    return n;
+}
+// is plane p of planes_per_view one of them?
+inline bool frame_plane_read(const sl3d_ctx *x, int p)
+{
+    int first[2], count[2];
+    const int n = frame_plane_runs(x, first, count);
+    for (int i = 0; i < n; i++)
+        if (p >= first[i] && p < first[i] + count[i]) return true;
+    return false;
 }

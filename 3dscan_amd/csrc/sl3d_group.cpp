@@ -26,6 +26,7 @@
 
 #include "sl3d_anchor.h"
 #include "sl3d_one_axis.h"
+#include "sl3d_direct_gray.h"
 #include "sl3d_ctx.h"
 
 namespace {
@@ -197,6 +198,8 @@ try {
     if (const char *why = one_axis_refusal((cfg->flags & SL3D_FLAG_ONLY_VERTICAL) != 0, (cfg->flags & SL3D_FLAG_ONLY_HORIZONTAL) != 0, (cfg->flags & SL3D_FLAG_SUBPIXEL) != 0,
                                            (cfg->flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
         return gfail(nullptr, SL3D_E_UNSUPPORTED, std::string("group_create: ") + why);
+    if (const char *why = direct_gray_refusal((cfg->flags & SL3D_FLAG_DIRECT_GRAY) != 0, (cfg->flags & SL3D_FLAG_SUBPIXEL) != 0, (cfg->flags & SL3D_FLAG_REPAIR_PERIODS) != 0))
+        return gfail(nullptr, SL3D_E_UNSUPPORTED, std::string("group_create: ") + why);
     if (cfg->flags & SL3D_FLAG_REPAIR_PERIODS)
         return gfail(nullptr, SL3D_E_UNSUPPORTED,
                      "group_create: SL3D_FLAG_REPAIR_PERIODS has no group form: a repair neighbourhood is clipped to its context's window, so the "
@@ -236,8 +239,9 @@ try {
         c.stream = nullptr;
         // (a stripe's launches stay on its one stream: the group orders its communication behind them by events on that stream)
         // (SL3D_FLAG_ANCHOR_PERIODS goes with SL3D_FLAG_SUBPIXEL: the rule is pointwise and works in frame coordinates, stripes agree with the whole frame)
-        // (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL likewise: pointwise, in frame coordinates)
-        c.flags = (cfg->flags & (SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS | SL3D_FLAG_ONLY_VERTICAL | SL3D_FLAG_ONLY_HORIZONTAL)) |
+        // (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL and SL3D_FLAG_DIRECT_GRAY likewise: pointwise, in frame coordinates)
+        c.flags = (cfg->flags & (SL3D_FLAG_KEEP_STAGES | SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ANCHOR_PERIODS | SL3D_FLAG_ONLY_VERTICAL | SL3D_FLAG_ONLY_HORIZONTAL |
+                                 SL3D_FLAG_DIRECT_GRAY)) |
                   SL3D_FLAG_SERIAL_LAUNCHES;
         const int rc = sl3d_create(&c, &s.ctx);
         if (rc != SL3D_OK) return bail(rc, "stripe " + std::to_string(i) + ": " + sl3d_last_error(nullptr));
@@ -554,11 +558,10 @@ try {
     if (!g || n_views < 1 || !planes) return gfail(g, SL3D_E_INVALID_ARG, "group_process_views: null argument");
     const size_t W = (size_t)g->cfg.width, H = (size_t)g->cfg.height;
     const size_t ppv = (size_t)g->st[0].ctx->P.planes_per_view, np = (size_t)n_views * ppv;
-    // (the stripes of a one-axis group upload the planes of the coded axis alone: the pointers of the other axis may be NULL)
-    int p_first, p_count;
-    frame_plane_range(g->st[0].ctx, &p_first, &p_count);
+    // (the stripes of a one-axis group upload the planes of the coded axis alone: the pointers of the other axis may be NULL; those of a
+    // SL3D_FLAG_DIRECT_GRAY group no inverse plane: those pointers likewise)
     for (size_t i = 0; i < np; i++)
-        if (!planes[i] && (int)(i % ppv) >= p_first && (int)(i % ppv) < p_first + p_count) return gfail(g, SL3D_E_INVALID_ARG, "group_process_views: null plane");
+        if (!planes[i] && frame_plane_read(g->st[0].ctx, (int)(i % ppv))) return gfail(g, SL3D_E_INVALID_ARG, "group_process_views: null plane");
     // the pipelines overwrite result slots [0, min(n_views, max_views)) of every stripe: an asynchronous gather may still be
     // reading them (sl3d_group_gather / _gather_clouds only mark the views busy) -- an RCCL send on the communication stream of the
     // stripe's own GPU, a (peer) copy on the root's.  The stripe's stream waits for both, as group_launch does; the enqueue below

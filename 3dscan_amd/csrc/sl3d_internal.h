@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -245,6 +245,16 @@ int launch_subpixel_coords_one(const KParams &P, int axis, int view, double *xy,
 #define SL3D_ONE_AXIS_NAME(axis, anchor) \
     ((axis) == 0 ? ((anchor) ? "sl3d::k_one_axis<0, true>" : "sl3d::k_one_axis<0, false>") : ((anchor) ? "sl3d::k_one_axis<1, true>" : "sl3d::k_one_axis<1, false>"))
 int launch_one_axis(const KParams &P, const DevCal *d_cal, int axis, int first_view, int n_views, bool anchor, void *stream);
+// the scans of a SL3D_FLAG_DIRECT_GRAY context (sl3d_direct_gray.h / .hip): stage 4's Gray bit against the fringe mean, no inverse plane read.
+// Staged: launch_unwrap_direct is launch_unwrap with that bit.  Timed: launch_direct_gray leaves in the views' points and valid planes (axes
+// == 2: and in `residual`) what launch_wrap / launch_unwrap_direct, launch_corr / launch_corr_one and launch_subpixel(+inf) / launch_subpixel_one
+// leave there, in one launch; axes: 0 / 1 the one coded axis, 2 both.  SL3D_DIRECT_GRAY_NAME: its six instantiations as rocprofv3 spells them
+int launch_unwrap_direct(const KParams &P, int view, int axis, void *stream);
+#define SL3D_DIRECT_GRAY_NAME(axes, anchor)                                                                  \
+    ((axes) == 0   ? ((anchor) ? "sl3d::k_direct_gray<0, true>" : "sl3d::k_direct_gray<0, false>")          \
+     : (axes) == 1 ? ((anchor) ? "sl3d::k_direct_gray<1, true>" : "sl3d::k_direct_gray<1, false>")          \
+                   : ((anchor) ? "sl3d::k_direct_gray<2, true>" : "sl3d::k_direct_gray<2, false>"))
+int launch_direct_gray(const KParams &P, const DevCal *d_cal, int axes, int first_view, int n_views, float *residual, bool anchor, void *stream);
 // the fringe-modulation test of a one-axis context: gamma of the coded axis alone, no plane of the other axis read
 int launch_modulation_select_one(const KParams &P, int first_view, int n_views, uint8_t *staging, bool has_mask, double thr, int axis, void *stream);
 // the period-repaired scan of a timed context (sl3d_repair_fused.hip, SL3D_FLAG_REPAIR_PERIODS): what launch_wrap / launch_unwrap of both

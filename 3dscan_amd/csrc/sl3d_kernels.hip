@@ -203,6 +203,7 @@ __global__ __launch_bounds__(256) void k_wrap(const KParams P, int view, int axi
 }
 
 // stage 4: unwrap_phase  4/phase_unwrap.cpp:367-393 (Gray-code mode, count == 1)
+// (k_unwrap_direct, sl3d_direct_gray.hip, is this text with the bit of SL3D_FLAG_DIRECT_GRAY: a change here goes there too)
 __global__ __launch_bounds__(256) void k_unwrap(const KParams P, int view, int axis)
 {
     int col, row;

@@ -19,6 +19,7 @@ SL3D_FLAG_SUBPIXEL = 128
 SL3D_FLAG_REPAIR_PERIODS = 256
 SL3D_FLAG_ANCHOR_PERIODS = 512
 SL3D_FLAG_ONLY_VERTICAL, SL3D_FLAG_ONLY_HORIZONTAL = 1024, 2048
+SL3D_FLAG_DIRECT_GRAY = 4096
 AXIS_VERTICAL, AXIS_HORIZONTAL = 0, 1
 PATTERN_FRINGE, PATTERN_GRAY, PATTERN_INVERSE_GRAY, PATTERN_BINARY = 0, 1, 2, 3
 VALID_VERTICAL, VALID_HORIZONTAL, VALID_MERGED = 0, 1, 2
@@ -356,14 +357,24 @@ class _Handle:
         return self._fill(self._prefix + "get_cloud", (view,), _XYZ)[0]
 
     def _process_views(self, frames, xyz, valid):
-        n, ppv, H, W = frames.shape
-        assert (H, W) == (self.H, self.W) and frames.dtype == np.uint8 and frames.strides[3] == 1 and frames.strides[2] >= W
+        """frames: the 4-D array, or per view a sequence of planes_per_view planes in which a plane the context does not read (the other
+        axis of a one-axis scan, the inverse Gray planes under SL3D_FLAG_DIRECT_GRAY) may be None: its pointer goes down as NULL."""
+        H, W = self.H, self.W
+        if isinstance(frames, np.ndarray):
+            n, ppv = frames.shape[:2]
+            assert frames.shape[2:] == (H, W) and frames.dtype == np.uint8 and frames.strides[3] == 1 and frames.strides[2] >= W
+            planes, stride = [frames[v, p] for v in range(n) for p in range(ppv)], frames.strides[2]
+        else:
+            n, stride = len(frames), W
+            assert n >= 1 and len({len(v) for v in frames}) == 1, "every view lists planes_per_view planes (None for one that is not read)"
+            planes = [None if p is None else np.ascontiguousarray(p, dtype=np.uint8) for v in frames for p in v]
+            assert all(p is None or p.shape == (H, W) for p in planes)
         if xyz is None:
             xyz = np.empty((n, H, W, 3), dtype=np.float32)
         if valid is None:
             valid = np.empty((n, H, W), dtype=np.uint8)
-        ptrs = _ptrs([frames[v, p] for v in range(n) for p in range(ppv)])
-        self._call("process_views", n, ptrs, frames.strides[2], xyz.ctypes.data, valid.ctypes.data)
+        ptrs = (C.c_void_p * len(planes))(*[None if p is None else p.ctypes.data for p in planes])
+        self._call("process_views", n, ptrs, stride, xyz.ctypes.data, valid.ctypes.data)
         return xyz, valid
 
 
@@ -373,7 +384,7 @@ class Scanner(_Handle):
     def __init__(self, width, height, proj_width, proj_height, n_gray_v, n_gray_h, fringe_width_v, fringe_width_h,
                  n_fringe=3, n_codes_v=0, n_codes_h=0, max_views=1, device=0, keep_stages=False,
                  full_size=None, origin=(0, 0), stream=None, eager_mask=False, serial_launches=False, subpixel=False, repaired=False,
-                 anchored=False, only_axis=None):
+                 anchored=False, only_axis=None, direct_gray=False):
         """eager_mask: SL3D_FLAG_EAGER_MASK -- every mask is prepared by k_mask_prepare when it is set; by default a timed context
         defers masks of up to 4 views to the next launch over them (the fused kernel evaluates the selection itself).
         subpixel: SL3D_FLAG_SUBPIXEL -- run() (and process_views) leaves the sub-pixel scan and its residual plane: what the per-stage
@@ -390,7 +401,13 @@ class Scanner(_Handle):
         SL3D_FLAG_ONLY_HORIZONTAL (the row).  The frames of the other axis are never read (they need not be set, process_views does not
         upload them), a pixel is the intersection of its camera ray with the plane of the decoded coordinate, and there are no
         residuals.  Needs subpixel=True, an undistorted projector with a plain matrix, and excludes repaired=True; may be combined with
-        anchored=True.  Groups: flags=SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ONLY_VERTICAL."""
+        anchored=True.  Groups: flags=SL3D_FLAG_SUBPIXEL | SL3D_FLAG_ONLY_VERTICAL.
+        direct_gray: SL3D_FLAG_DIRECT_GRAY -- stage 4 thresholds a Gray frame against the mean of the pixel's fringe frames, (2 * gray -
+        (I0 + I2) >= 0), instead of against its inverse frame: no inverse Gray frame is read, so a coded axis needs F + N frames instead
+        of F + 2 N.  set_frames() then also takes those F + N planes alone, and process_views() a per-view list of planes with None for
+        the inverse ones.  Needs subpixel=True and excludes repaired=True (repair_periods() on a keep_stages scanner works); may be
+        combined with keep_stages, anchored, only_axis, eager_mask and serial_launches.  Groups: flags=SL3D_FLAG_SUBPIXEL |
+        SL3D_FLAG_DIRECT_GRAY."""
         if only_axis not in (None, 0, 1):
             raise ValueError("only_axis must be None, 0 or 1")
         self.L = load_library()
@@ -400,7 +417,8 @@ class Scanner(_Handle):
                           max_views, device, (SL3D_FLAG_KEEP_STAGES if keep_stages else 0) | (SL3D_FLAG_EAGER_MASK if eager_mask else 0) |
                           (SL3D_FLAG_SERIAL_LAUNCHES if serial_launches else 0) | (SL3D_FLAG_SUBPIXEL if subpixel else 0) |
                           (SL3D_FLAG_REPAIR_PERIODS if repaired else 0) | (SL3D_FLAG_ANCHOR_PERIODS if anchored else 0) |
-                          {None: 0, 0: SL3D_FLAG_ONLY_VERTICAL, 1: SL3D_FLAG_ONLY_HORIZONTAL}[only_axis], stream)
+                          {None: 0, 0: SL3D_FLAG_ONLY_VERTICAL, 1: SL3D_FLAG_ONLY_HORIZONTAL}[only_axis] |
+                          (SL3D_FLAG_DIRECT_GRAY if direct_gray else 0), stream)
         self.W, self.H = width, height
         self._h = C.c_void_p()
         rc = self.L.sl3d_create(C.byref(self.cfg), C.byref(self._h))
@@ -463,6 +481,14 @@ class Scanner(_Handle):
         m = np.ascontiguousarray(selected_region, dtype=np.int32)
         assert m.shape == (self.cfg.full_width, self.cfg.full_height), m.shape
         self._chk(self.L.sl3d_set_mask_colrow(self._h, view, m.ctypes.data), "sl3d_set_mask_colrow")
+
+    def set_frames(self, axis, planes, view=0):
+        """The F + 2 N planes of one axis; a direct_gray scanner also takes the F + N fringe and Gray planes alone (it reads no inverse
+        plane): they go through sl3d_set_frames_range."""
+        n_read = self.cfg.n_fringe + (self.cfg.n_gray_v if axis == 0 else self.cfg.n_gray_h)
+        if self.cfg.flags & SL3D_FLAG_DIRECT_GRAY and len(planes) == n_read:
+            return self.set_frames_range(axis, 0, planes, view=view)
+        return super().set_frames(axis, planes, view=view)
 
     def set_frames_range(self, axis, first_plane, planes, view=0):
         arrs, ptrs = self._planes(planes)
@@ -880,7 +906,8 @@ class Scanner(_Handle):
         return np.frombuffer((C.c_char * n).from_address(p), dtype=dtype).reshape(shape)
 
     def process_views(self, frames, xyz=None, valid=None):
-        """frames: (n_views, planes_per_view, H, W) uint8 host array (pinned for full overlap); returns (xyz, valid)."""
+        """frames: (n_views, planes_per_view, H, W) uint8 host array (pinned for full overlap), or per view a list of planes_per_view
+        planes with None for a plane the context does not read (direct_gray: the inverse Gray planes); returns (xyz, valid)."""
         return self._process_views(frames, xyz, valid)
 
     def undistort(self, image, K, dist):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.19.0"
+#define SL3D_VERSION_STRING "0.20.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -190,7 +190,41 @@ enum sl3d_flags {
      * Where the baseline between camera and projector is horizontal the row carries almost no depth: SL3D_FLAG_ONLY_HORIZONTAL is for
      * rigs with a vertical baseline.  A context without these flags behaves exactly as before. */
     SL3D_FLAG_ONLY_VERTICAL = 1024u,
-    SL3D_FLAG_ONLY_HORIZONTAL = 2048u
+    SL3D_FLAG_ONLY_HORIZONTAL = 2048u,
+    /* (0.20.0) The Gray decode against the FRINGE MEAN: a scan without the inverse Gray frames -- F + N frames per coded axis instead of
+     * F + 2 N ("3 phase-shift + 10 Gray-code frames": 13 instead of 23 for one axis, 26 instead of 46 for two).  An extension: the
+     * reference has no such mode.  Its fringe steps are Pi/2 apart (1/pattern_generator.cpp:302,342), so fringe frames 0 and 2 are half a
+     * period apart and I0 + I2 is twice the pixel's mean intensity, the level halfway between a lit and a dark Gray stripe.  On such a
+     * context bit i of stage 4's Gray decode of an axis is
+     *   G_i = (2 * (int)gray_i - ((int)I0 + (int)I2) >= 0)        ties -> 1, as pos - inv >= 0 in 4/phase_unwrap.cpp:183
+     * with gray_i the byte of Gray plane i and I0, I2 fringe bytes 0 and 2 of the same axis of the same view, as they sit in the frame
+     * stack; the same rule for n_fringe 3 and 4 (with 5 nothing is valid, as always).  Everything after the bit is unchanged: the XOR
+     * chain and code, the shifted wrapped phase, the absolute phase, stage 5, the anchored coordinate, the sub-pixel solves and the
+     * residual.  The rule is pointwise: windows and the stripes of a group agree with the whole frame.
+     *   The frame layout, planes_per_view, sl3d_device_buffers and the setters do not change: the inverse-Gray slots exist and nothing
+     *   reads them.  sl3d_set_frames still takes F + 2 N planes; a caller without inverse frames uses sl3d_set_frames_range(view, axis,
+     *   0, planes, F + N, stride).  sl3d_process_views and sl3d_group_process_views upload only the F + N planes of each coded axis,
+     *   their contiguity test runs over those, and the pointers of the inverse planes may be NULL (with SL3D_FLAG_ONLY_VERTICAL /
+     *   _HORIZONTAL so may all pointers of the other axis).  sl3d_synth_view, sl3d_get_frames, sl3d_copy_view, sl3d_set_masks_modulated
+     *   and sl3d_get_modulation are unchanged.
+     *   Without KEEP_STAGES: ONE launch of a kernel of its own (k_direct_gray<axes, anchored>, axes = 0: vertical only, 1: horizontal only,
+     *   2: both axes) on the context's stream, behind the preparation of whatever masks are still deferred -- no launch lanes, every
+     *   launch counts as on-stream, sl3d_camera_table_bytes_per_pixel is 0, sl3d_fused_kernel_name / sl3d_last_fused_kernel_name report
+     *   "sl3d::k_direct_gray<0, false>" ... "sl3d::k_direct_gray<2, true>".  Per pixel, view and coded axis it reads F + N frame bytes.
+     *   With both axes the residual plane is written as on any SL3D_FLAG_SUBPIXEL context; with one axis there is none.  Points, valid
+     *   (and residuals) are bit for bit the staged route's.
+     *   With KEEP_STAGES: sl3d_unwrap_phase decodes by the direct rule, the stage getters show the direct code, and sl3d_run() enqueues
+     *   per view stage 3 and the direct stage 4 of each coded axis and stage 5, then one sub-pixel launch over the views (not the parity
+     *   kernel, which reads the inverse planes).  sl3d_repair_periods works there as on any context: it touches the code and phase
+     *   planes only.
+     *   Refused with SL3D_E_UNSUPPORTED by sl3d_create and sl3d_group_create before a device is touched: the flag without
+     *   SL3D_FLAG_SUBPIXEL (the integer scan's kernel reads the inverse frames: add SL3D_FLAG_SUBPIXEL); the flag with
+     *   SL3D_FLAG_REPAIR_PERIODS (the fused repair has no direct form).  May be combined with SL3D_FLAG_KEEP_STAGES,
+     *   SL3D_FLAG_ANCHOR_PERIODS, SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL, SL3D_FLAG_EAGER_MASK and SL3D_FLAG_SERIAL_LAUNCHES.
+     *   sl3d_run_clouds stays refused as on every SL3D_FLAG_SUBPIXEL context.  sl3d_group_create hands the flag to its stripes.
+     * On a lit pixel the two decodes agree (the mean sits between the stripe levels as the inverse frame does); on an unlit pixel under
+     * noise both are noise and differ.  A context without the flag behaves exactly as before. */
+    SL3D_FLAG_DIRECT_GRAY = 4096u
     /* (8u was SL3D_FLAG_CLOUDS_LOOKBACK until 0.3: contiguous clouds in one pass by a decoupled look-back between tiles.  Removed
      * in 0.4 -- every tile waited for its predecessors, 0.53 of the roofline against 0.67 for the segmented clouds; a consumer
      * that wants one contiguous device array asks sl3d_get_cloud_counts for it.) */
@@ -329,7 +363,8 @@ int sl3d_set_mask_colrow(sl3d_ctx *ctx, int view, const int32_t *selected_region
 
 /* n_planes planes of one axis starting at plane index first_plane of sl3d_set_frames' order (fringe[0..F), gray[0..N),
  * inverse_gray[0..N)): stage 3 loads only the F fringe frames (read_image, 3/wrapped_phase.cpp:29-58), stage 4 only the Gray /
- * inverse frames (read_captured_images, 4/phase_unwrap.cpp:51-131). */
+ * inverse frames (read_captured_images, 4/phase_unwrap.cpp:51-131).  A SL3D_FLAG_DIRECT_GRAY context reads no inverse plane: first_plane 0
+ * and n_planes F + N set all it needs. */
 int sl3d_set_frames_range(sl3d_ctx *ctx, int view, int axis, int first_plane, const uint8_t *const *planes, int n_planes, size_t stride);
 
 /* Device-to-device duplicate of one resident view (frame stack + mask) into another slot of the batch. */
@@ -347,7 +382,7 @@ int sl3d_get_frames(sl3d_ctx *ctx, int view, int axis, uint8_t *const *planes, i
 /* ---- the reference's four stage entry points (need SL3D_FLAG_KEEP_STAGES) ------------------- */
 /* void compute_wrapped_phase(int pattern_type)   3/wrapped_phase.cpp:402   */
 int sl3d_compute_wrapped_phase(sl3d_ctx *ctx, int view, int axis);
-/* void unwrap_phase(int pattern_type)            4/phase_unwrap.cpp:367    */
+/* void unwrap_phase(int pattern_type)            4/phase_unwrap.cpp:367    (a SL3D_FLAG_DIRECT_GRAY context: the flag's Gray bit) */
 int sl3d_unwrap_phase(sl3d_ctx *ctx, int view, int axis);
 /* void compute_c_p_map()                         5/compute_correspondance.cpp:630 */
 int sl3d_compute_c_p_map(sl3d_ctx *ctx, int view);
@@ -429,7 +464,8 @@ int sl3d_get_correspondences_subpixel(sl3d_ctx *ctx, int view, double *xy, size_
  * kernel launch that reads every frame byte once and writes xyz (f32) + valid (u8). Asynchronous.
  * On a SL3D_FLAG_SUBPIXEL context: the sub-pixel scan and its residual plane instead (see the flag) -- still one launch per call
  * without KEEP_STAGES, the parity launch + sl3d_triangulate_subpixel's with it.  On a SL3D_FLAG_REPAIR_PERIODS context: the scan with
- * the period jumps of both axes repaired (see the flag), one launch per call without KEEP_STAGES as well. */
+ * the period jumps of both axes repaired (see the flag), one launch per call without KEEP_STAGES as well.  On a SL3D_FLAG_DIRECT_GRAY
+ * context: the Gray frames against the fringe mean, no inverse frame read (see the flag), one launch per call without KEEP_STAGES. */
 int sl3d_run(sl3d_ctx *ctx, int first_view, int n_views);
 /* The same pass with the compaction of 8/save_point_cloud.cpp:33-37,85-104 INSIDE the kernel: instead of the dense xyz plane every
  * view's valid points are written once, compacted in the reference's row-major scan order, plus the valid map:
@@ -863,7 +899,9 @@ int sl3d_register_views(sl3d_ctx *ctx, int first_view, int n_views, float tx, fl
  * upload), not the sum.  planes: n_views * planes_per_view pointers, view-major, plane order of sl3d_device_buffers;
  * xyz: n_views dense [height][width][3] float images, NaN where invalid (may be NULL); valid: n_views [height][width]
  * byte images (may be NULL).  Masks and calibration must be set (sl3d_set_mask for every slot < max_views).
- * sl3d_host_alloc returns pinned memory: with it the copies are asynchronous DMA (pageable memory works, serialised). */
+ * sl3d_host_alloc returns pinned memory: with it the copies are asynchronous DMA (pageable memory works, serialised).
+ * A SL3D_FLAG_DIRECT_GRAY context uploads the F + N fringe and Gray planes of each coded axis alone: the pointers of the inverse planes
+ * may be NULL. */
 void *sl3d_host_alloc(size_t bytes);
 void sl3d_host_free(void *p);
 int sl3d_process_views(sl3d_ctx *ctx, int n_views, const uint8_t *const *planes, size_t stride, float *xyz, uint8_t *valid);
