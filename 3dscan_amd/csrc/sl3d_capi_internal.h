@@ -1,7 +1,7 @@
 // sl3d_capi_internal.h -- what the translation units behind include/sl3d.h share (not part of the ABI; every symbol is hidden):
 //   sl3d_capi_context.cpp  errors, sl3d_create / sl3d_destroy, calibration (T0 and the per-calibration tables), stream helpers
 //   sl3d_capi_inputs.cpp   selection masks (prepared now or deferred to the launch: H0 / S3b / S3d) and frames in, [col][row] layouts
-//   sl3d_capi_run.cpp      the per-stage entry points, every fused launch (run_fused), getters, the host-buffer pipeline
+//   sl3d_capi_run.cpp      the per-stage entry points, every fused launch (run_fused, by fused_route below), getters, the host-buffer pipeline
 //   sl3d_capi_clouds.cpp   O1 / N2 / N3: ordered clouds, their consumers, colour, registration
 //   sl3d_capi_next.cpp     N1 / N4: patterns, synthetic captures, cvUndistort2, plain device copies
 //   sl3d_capi_period.cpp   the period repair between stage 4 and stage 5 (sl3d_repair_periods)
@@ -115,34 +115,48 @@ inline int download_plane(sl3d_ctx *x, const T *src, int comps, T *out, size_t o
     return SL3D_OK;
 }
 
-// every fused launch of the library (sl3d_capi_run.cpp)
-// THE routing decision of a SL3D_FLAG_SUBPIXEL context: does a dense launch of this context go out as k_subpixel_fused instead of a
-// k_fused instantiation?  (With SL3D_FLAG_KEEP_STAGES it stays the parity kernel, and k_subpixel follows it.)  run_fused launches by it,
-// sl3d_fused_kernel_name, sl3d_last_fused_kernel_name and sl3d_camera_table_bytes_per_pixel report by it
-inline bool subpixel_fused_route(const sl3d_ctx *x) { return x->subpixel && !x->keep && !x->repair; }
-// ... and of a SL3D_FLAG_REPAIR_PERIODS context: k_repair_fused, with the sub-pixel ending if the context has SL3D_FLAG_SUBPIXEL too.  (With
-// SL3D_FLAG_KEEP_STAGES: the parity kernel, the staged repair of both axes, stage 5 and stage 7 or k_subpixel behind it.)  The same four
-// report by it; own_kernel_route: either of the two -- one launch per call on the context's stream, no k_fused instantiation, no camera table
-inline bool repair_fused_route(const sl3d_ctx *x) { return x->repair && !x->keep; }
-inline bool own_kernel_route(const sl3d_ctx *x) { return subpixel_fused_route(x) || repair_fused_route(x); }
-// ... and of a one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL; always with SL3D_FLAG_SUBPIXEL, never with the repair: it is a
-// subpixel_fused_route whose kernel is k_one_axis.  With SL3D_FLAG_KEEP_STAGES: stages 3 and 4 of the coded axis, the one-axis stage 5 and 7)
-inline bool one_axis_route(const sl3d_ctx *x) { return x->one_axis >= 0 && subpixel_fused_route(x); }
-// ... and of a SL3D_FLAG_DIRECT_GRAY context (always with SL3D_FLAG_SUBPIXEL, never with the repair; with or without a one-axis flag): it is
-// a subpixel_fused_route whose kernel is k_direct_gray.  With SL3D_FLAG_KEEP_STAGES: stage 3, the direct stage 4 (launch_stage4), stage 5 and
-// the sub-pixel launch of the coded axes
-inline bool direct_gray_route(const sl3d_ctx *x) { return x->direct_gray && subpixel_fused_route(x); }
+// THE routing decision of a context: what a fused launch of it -- every one goes through run_fused (sl3d_capi_run.cpp) -- puts on the device.
+// run_fused launches by it; own_kernel_name, sl3d_fused_kernel_name, sl3d_last_fused_kernel_name and sl3d_camera_table_bytes_per_pixel report
+// by it.  Whichever route a flag set takes, sl3d_run leaves the same scan with and without SL3D_FLAG_KEEP_STAGES.
+enum FusedRoute {
+    ROUTE_K_FUSED,  // neither SL3D_FLAG_SUBPIXEL nor SL3D_FLAG_REPAIR_PERIODS: a k_fused instantiation alone (run_k_fused: on the stream or a lane)
+    // SL3D_FLAG_KEEP_STAGES with one of the two, both axes against the inverse planes: the parity k_fused; with the repair one pass of the
+    // staged repair over every axis that has Gray planes, stage 5 again and stage 7 over the repaired phases; with SL3D_FLAG_SUBPIXEL k_subpixel
+    // (+infinity, no counts) last, in place of stage 7
+    ROUTE_K_FUSED_THEN_STAGES,
+    // SL3D_FLAG_KEEP_STAGES on a one-axis (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL) or a SL3D_FLAG_DIRECT_GRAY context: never the parity k_fused,
+    // which reads both axes and the inverse planes.  Per view k_wrap and stage 4 (launch_stage4) of every coded axis and stage 5 (k_corr, or
+    // k_corr_one), then the sub-pixel launch over the views (k_subpixel, or k_subpixel_one)
+    ROUTE_STAGED,
+    // no SL3D_FLAG_KEEP_STAGES: ONE launch of the context's own kernel (sl3d_quad.h) per call, on the context's stream behind the preparation of
+    // the views' deferred masks -- no k_fused instantiation, no lanes, no camera table.  SL3D_FLAG_ANCHOR_PERIODS: the first three's anchored form
+    ROUTE_SUBPIXEL_FUSED,  // SL3D_FLAG_SUBPIXEL: k_subpixel_fused
+    ROUTE_ONE_AXIS,        // ... with a one-axis flag: k_one_axis
+    ROUTE_DIRECT_GRAY,     // ... with SL3D_FLAG_DIRECT_GRAY, with or without a one-axis flag: k_direct_gray, its one-axis or its two-axis form
+    ROUTE_REPAIR_FUSED     // SL3D_FLAG_REPAIR_PERIODS: k_repair_fused, with the sub-pixel ending if the context has SL3D_FLAG_SUBPIXEL too
+};
+inline FusedRoute fused_route(const sl3d_ctx *x)
+{
+    if (!x->subpixel && !x->repair) return ROUTE_K_FUSED;
+    if (x->keep) return x->one_axis >= 0 || x->direct_gray ? ROUTE_STAGED : ROUTE_K_FUSED_THEN_STAGES;
+    if (x->repair) return ROUTE_REPAIR_FUSED;  // (never with a one-axis flag or SL3D_FLAG_DIRECT_GRAY: sl3d_create refuses)
+    if (x->direct_gray) return ROUTE_DIRECT_GRAY;
+    return x->one_axis >= 0 ? ROUTE_ONE_AXIS : ROUTE_SUBPIXEL_FUSED;
+}
+inline bool own_kernel(FusedRoute r) { return r == ROUTE_SUBPIXEL_FUSED || r == ROUTE_ONE_AXIS || r == ROUTE_DIRECT_GRAY || r == ROUTE_REPAIR_FUSED; }
 // stage 4 of one axis of a view on the context's stream: by the direct rule on a SL3D_FLAG_DIRECT_GRAY context (k_unwrap itself is untouched)
 inline int launch_stage4(const sl3d_ctx *x, int view, int axis)
 {
     return x->direct_gray ? launch_unwrap_direct(x->P, view, axis, x->stream) : launch_unwrap(x->P, view, axis, x->stream);
 }
-inline const char *own_kernel_name(const sl3d_ctx *x)
+inline const char *own_kernel_name(const sl3d_ctx *x)  // (of a context whose route is an own_kernel)
 {
-    if (direct_gray_route(x)) return SL3D_DIRECT_GRAY_NAME(x->one_axis >= 0 ? x->one_axis : 2, x->anchor);
-    if (one_axis_route(x)) return SL3D_ONE_AXIS_NAME(x->one_axis, x->anchor);
-    if (!repair_fused_route(x)) return x->anchor ? SL3D_SUBPIXEL_FUSED_ANCHOR_NAME : SL3D_SUBPIXEL_FUSED_NAME;
-    return x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;
+    switch (fused_route(x)) {
+    case ROUTE_DIRECT_GRAY: return SL3D_DIRECT_GRAY_NAME(x->one_axis >= 0 ? x->one_axis : 2, x->anchor);
+    case ROUTE_ONE_AXIS: return SL3D_ONE_AXIS_NAME(x->one_axis, x->anchor);
+    case ROUTE_REPAIR_FUSED: return x->subpixel ? SL3D_REPAIR_FUSED_SUB_NAME : SL3D_REPAIR_FUSED_NAME;
+    default: return x->anchor ? SL3D_SUBPIXEL_FUSED_ANCHOR_NAME : SL3D_SUBPIXEL_FUSED_NAME;
+    }
 }
 // the launches of sl3d_repair_periods (sl3d_capi_period.cpp): one pass over one axis of one view behind whatever the stream holds; the
 // counts are added to the view's and the axis's two words of d_period_counts, which the caller has cleared if it reads them

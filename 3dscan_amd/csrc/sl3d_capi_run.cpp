@@ -147,53 +147,35 @@ int small_launch_overlaps(sl3d_ctx *x, int first_view, int n_views, bool *overla
 
 static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap);
 
-// every fused launch of the library goes through here.  A SL3D_FLAG_SUBPIXEL context (subpixel_fused_route): the timed one launches k_subpixel_fused on the context's stream, behind the
-// preparation of whatever masks of the views are still deferred; the parity one launches what it always does and k_subpixel
-// (+infinity, no counts) behind it.  Either way sl3d_run leaves the same scan.  SL3D_FLAG_ANCHOR_PERIODS picks the anchored instantiation of
-// whichever of the two kernels goes out.
-// A SL3D_FLAG_REPAIR_PERIODS context (repair_fused_route) likewise: the timed one launches k_repair_fused -- with the sub-pixel ending
-// if it has SL3D_FLAG_SUBPIXEL too -- and the parity one launches what it always does, then one pass of the staged repair over every axis
-// that has Gray planes, then stage 5 again and stage 7 (or k_subpixel) over the repaired phases.
-// A one-axis context (SL3D_FLAG_ONLY_VERTICAL / _HORIZONTAL, one_axis_route): the timed one launches k_one_axis, the parity one the staged
-// one-axis route -- k_wrap, k_unwrap of the coded axis and k_corr_one per view, then k_subpixel_one over the views; never the parity k_fused,
-// which reads both axes.
-// A SL3D_FLAG_DIRECT_GRAY context (direct_gray_route): the timed one launches k_direct_gray -- its one-axis or its two-axis form --, the parity
-// one k_wrap, k_unwrap_direct and stage 5 per view and then the sub-pixel launch over the views; never the parity k_fused, which reads the
-// inverse planes.
+// every fused launch of the library goes through here: by the context's route (fused_route, sl3d_capi_internal.h, where the routes are described)
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
-    if (!x->subpixel && !x->repair) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
+    const FusedRoute route = fused_route(x);
+    if (route == ROUTE_K_FUSED) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
     int rc;
-    if (own_kernel_route(x)) {
-        if ((rc = flush_masks(x, first_view, n_views))) return rc;
-        x->launches_on_stream++;
-        if (direct_gray_route(x))
-            rc = launched(x, launch_direct_gray(x->P, x->d_cal, x->one_axis >= 0 ? x->one_axis : 2, first_view, n_views, x->d_residual, x->anchor, x->stream));
-        else if (one_axis_route(x)) rc = launched(x, launch_one_axis(x->P, x->d_cal, x->one_axis, first_view, n_views, x->anchor, x->stream));
-        else if (repair_fused_route(x)) rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream));
-        else rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->anchor, x->stream));
-        if (!rc) x->own_kernel_ran = true;
-    } else if (x->one_axis >= 0) {  // the staged one-axis route: not the parity kernel, which reads both axes
+    if (route != ROUTE_K_FUSED_THEN_STAGES) {  // (run_k_fused prepares the masks and counts its launch itself)
         if ((rc = flush_masks(x, first_view, n_views))) return rc;
         x->launches_on_stream++;  // (one per call, as the parity launch counts)
+    }
+    switch (route) {
+    case ROUTE_DIRECT_GRAY: rc = launched(x, launch_direct_gray(x->P, x->d_cal, x->one_axis >= 0 ? x->one_axis : 2, first_view, n_views, x->d_residual, x->anchor, x->stream)); break;
+    case ROUTE_ONE_AXIS: rc = launched(x, launch_one_axis(x->P, x->d_cal, x->one_axis, first_view, n_views, x->anchor, x->stream)); break;
+    case ROUTE_REPAIR_FUSED: rc = launched(x, launch_repair_fused(x->P, x->d_cal, first_view, n_views, x->subpixel ? x->d_residual : nullptr, x->stream)); break;
+    case ROUTE_SUBPIXEL_FUSED: rc = launched(x, launch_subpixel_fused(x->P, x->d_cal, first_view, n_views, x->d_residual, x->anchor, x->stream)); break;
+    case ROUTE_STAGED: {
+        const bool one = x->one_axis >= 0;
         for (int view = first_view; view < first_view + n_views; view++) {
-            if ((rc = launched(x, launch_wrap(x->P, view, x->one_axis, x->stream)))) return rc;
-            if ((rc = launched(x, launch_stage4(x, view, x->one_axis)))) return rc;
-            if ((rc = launched(x, launch_corr_one(x->P, view, x->one_axis, x->stream)))) return rc;
-        }
-        return launched(x, launch_subpixel_one(x->P, x->C, x->one_axis, first_view, n_views, nullptr, nullptr, x->anchor, x->stream));
-    } else if (x->direct_gray) {  // the staged two-axis route of a SL3D_FLAG_DIRECT_GRAY context: not the parity kernel, which reads the inverse planes
-        if ((rc = flush_masks(x, first_view, n_views))) return rc;
-        x->launches_on_stream++;  // (one per call, as the parity launch counts)
-        for (int view = first_view; view < first_view + n_views; view++) {
-            for (int axis = 0; axis < 2; axis++) {
+            for (int axis = one ? x->one_axis : 0; axis <= (one ? x->one_axis : 1); axis++) {  // the context's coded axes
                 if ((rc = launched(x, launch_wrap(x->P, view, axis, x->stream)))) return rc;
                 if ((rc = launched(x, launch_stage4(x, view, axis)))) return rc;
             }
-            if ((rc = launched(x, launch_corr(x->P, view, x->stream)))) return rc;
+            if ((rc = launched(x, one ? launch_corr_one(x->P, view, x->one_axis, x->stream) : launch_corr(x->P, view, x->stream)))) return rc;
         }
-        rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->anchor, x->stream));
-    } else {
+        rc = launched(x, one ? launch_subpixel_one(x->P, x->C, x->one_axis, first_view, n_views, nullptr, nullptr, x->anchor, x->stream)
+                             : launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->anchor, x->stream));
+        break;
+    }
+    default:  // ROUTE_K_FUSED_THEN_STAGES
         if ((rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap))) return rc;
         if (x->repair) {
             for (int view = first_view; view < first_view + n_views; view++) {
@@ -206,6 +188,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
         if (x->subpixel)
             rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, (double)__builtin_inff(), x->d_residual, nullptr, nullptr, x->anchor, x->stream));
     }
+    if (!rc && own_kernel(route)) x->own_kernel_ran = true;
     if (!rc && x->subpixel && x->one_axis < 0) x->residual_ready = true;
     return rc;
 }
@@ -279,7 +262,7 @@ extern "C" int sl3d_launch_counts(sl3d_ctx *x, int64_t *on_stream, int64_t *on_l
 extern "C" int sl3d_last_fused_kernel_name(sl3d_ctx *x, char *buf, size_t capacity)
 try {
     if (!x || !buf || capacity == 0) return fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: null argument");
-    const bool own = own_kernel_route(x);  // (every launch of such a context is k_subpixel_fused / k_repair_fused)
+    const bool own = own_kernel(fused_route(x));  // (every launch of such a context is that kernel)
     if (own ? !x->own_kernel_ran : x->last_fused.nmax == 0) return fail(x, SL3D_E_STATE, "no fused launch has been made on this context");
     const int n = own ? snprintf(buf, capacity, "%s", own_kernel_name(x)) : fused_key_name(x->last_fused, buf, capacity);
     return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "last_fused_kernel_name: buffer too small");
@@ -306,9 +289,9 @@ extern "C" int sl3d_fused_kernel_name(sl3d_ctx *x, int n_views, int clouds, char
 try {
     if (!x || !buf || capacity == 0 || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: null argument");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called (the rig class is part of the name)");
-    if (own_kernel_route(x)) {
+    if (const FusedRoute route = fused_route(x); own_kernel(route)) {
         if (clouds)
-            return fail(x, SL3D_E_UNSUPPORTED, repair_fused_route(x) ? "fused_kernel_name: a SL3D_FLAG_REPAIR_PERIODS context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)"
+            return fail(x, SL3D_E_UNSUPPORTED, route == ROUTE_REPAIR_FUSED ? "fused_kernel_name: a SL3D_FLAG_REPAIR_PERIODS context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)"
                                                                      : "fused_kernel_name: a SL3D_FLAG_SUBPIXEL context has no sl3d_run_clouds (sl3d_run + sl3d_compact_views)");
         const int n = snprintf(buf, capacity, "%s", own_kernel_name(x));
         return n > 0 && (size_t)n < capacity ? SL3D_OK : fail(x, SL3D_E_INVALID_ARG, "fused_kernel_name: buffer too small");
@@ -323,7 +306,7 @@ extern "C" int sl3d_camera_table_bytes_per_pixel(sl3d_ctx *x, int n_views)
 try {
     if (!x || n_views < 1) return fail(x, SL3D_E_INVALID_ARG, "camera_table_bytes_per_pixel: null context or no views");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "sl3d_set_calibration has not been called");
-    if (!x->P.cam_tab || own_kernel_route(x)) return 0;  // (k_subpixel_fused and k_repair_fused iterate the camera's undistortion themselves)
+    if (!x->P.cam_tab || own_kernel(fused_route(x))) return 0;  // (the own kernels iterate the camera's undistortion themselves)
     if (x->P.cam_tab_kind == 2) return 16;
     (void)n_views;
     return 8;

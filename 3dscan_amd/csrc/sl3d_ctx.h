@@ -21,10 +21,10 @@ struct sl3d_ctx {
     bool have_cal = false;
     int rig = 0;
     bool keep = false;
-    // SL3D_FLAG_SUBPIXEL: sl3d_run leaves the sub-pixel scan.  Which launch that takes is subpixel_fused_route (sl3d_capi_internal.h)
+    // SL3D_FLAG_SUBPIXEL: sl3d_run leaves the sub-pixel scan.  Which launch that takes is fused_route (sl3d_capi_internal.h)
     bool subpixel = false;
     // SL3D_FLAG_REPAIR_PERIODS: sl3d_run leaves the scan with the 2*Pi period jumps of both axes repaired (radius 4, one pass).  Which
-    // launches that takes is repair_fused_route (sl3d_capi_internal.h)
+    // launches that takes is fused_route (sl3d_capi_internal.h)
     bool repair = false;
     // SL3D_FLAG_ANCHOR_PERIODS (only with subpixel, never with repair: sl3d_create): the sub-pixel solve and
     // sl3d_get_correspondences_subpixel take the anchored coordinates (sl3d_anchor.h)
@@ -35,7 +35,7 @@ struct sl3d_ctx {
     // SL3D_FLAG_DIRECT_GRAY (only with subpixel, never with repair: sl3d_create): stage 4 thresholds a Gray frame against the fringe mean
     // (sl3d_direct_gray.h) -- no inverse Gray plane is read or uploaded
     bool direct_gray = false;
-    bool own_kernel_ran = false;  // own_kernel_route: a launch has gone out (sl3d_last_fused_kernel_name)
+    bool own_kernel_ran = false;  // an own_kernel route (fused_route): a launch has gone out (sl3d_last_fused_kernel_name)
     bool own_stream = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

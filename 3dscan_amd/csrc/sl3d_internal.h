@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip -- these four share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once

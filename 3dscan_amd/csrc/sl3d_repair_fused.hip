@@ -3,7 +3,10 @@
 // the launch's views, bit for bit, what k_wrap, k_unwrap (both axes), one pass of k_period_jumps<AXIS, 4> + k_period_apply over every
 // axis that has Gray planes, k_corr and k_tri (SUB: k_subpixel(+inf)) leave there on a SL3D_FLAG_KEEP_STAGES context -- without any of
 // the stage planes between them.  Every arithmetic step is the helper the staged kernels call (sl3d_device.h, sl3d_period.h,
-// sl3d_subpixel.h), with the arguments they call it with; the per-pixel chain and the quad-per-lane shape are k_subpixel_fused's.
+// sl3d_subpixel.h), with the arguments they call it with; the per-pixel chain and the quad-per-lane shape are sl3d_quad.h's.  From that header:
+// the types and loads, quad_need, quad_correspond, quad_store, the launch.  As this unit's own statements, because the header's helper in their
+// place moves vector instructions of an instantiation (profiles/quad_kernels_isa.txt: which, and by what): the decode and phase step of an axis
+// (rpf_axis), a view's NaN fill, and the solve with its residual -- a change to those goes into sl3d_quad.h AND here.
 //   tile    256 lanes own 64 columns x 16 rows (the origin a multiple of 4: the radius of 4 is exactly one quad of columns each side), a
 //           lane the 4 consecutive pixels of one dword of every u8 plane.  The repair is a Jacobi pass over stage 4's output: a pixel
 //           needs the absolute phase and the sample-ness of up to 4 neighbours each side, along its row for the vertical axis and down
@@ -20,14 +23,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sl3d_device.h"
-#include "sl3d_internal.h"
 #include "sl3d_period.h"
-#include "sl3d_subpixel.h"
+#include "sl3d_quad.h"
 
 namespace sl3d {
 
-#define SL3D_RPF_BLOCK 256  // lanes per block
+#define SL3D_RPF_BLOCK SL3D_QUAD_BLOCK  // lanes per block
 #define SL3D_RPF_RADIUS SL3D_REPAIR_FUSED_RADIUS  // the radius of the flag's repair: Scanner.repair_periods' default
 constexpr int RPF_COLS = 64, RPF_ROWS = 16;              // the pixels a block owns
 constexpr int RPF_QUADS = RPF_COLS / 4;                  // lanes per tile row
@@ -39,12 +40,7 @@ static_assert(SL3D_RPF_RADIUS == 4, "the halo of a row is one quad each side");
 static_assert(RPF_QUADS * RPF_ROWS == SL3D_RPF_BLOCK && RPF_HALO_H + RPF_HALO_V <= SL3D_RPF_BLOCK, "a lane owns one quad and decodes at most one halo quad");
 static_assert(RPF_HALO_H % 64 == 0, "the two halo axes do not share a wave");
 
-typedef float rpf_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned rpf_load(const uint8_t *p) { return __builtin_nontemporal_load((const unsigned *)p); }
-__device__ __forceinline__ unsigned rpf_byte(unsigned w, int k) { return (w >> (8 * k)) & 0xffu; }
-
-// one axis of a quad as stages 3 and 4 leave it (k_wrap + k_unwrap), for the pixels whose bit is set in `bits`: the wrapped phase after
+// (quad_axis's statements) one axis of a quad as stages 3 and 4 leave it (k_wrap + k_unwrap), for the pixels whose bit is set in `bits`: the wrapped phase after
 // stage 4's += Pi, the Gray code and the absolute phase (0 where stage 4's loop does not run)
 struct RpfAxis {
     float w[4], unw[4];
@@ -54,18 +50,18 @@ __device__ __forceinline__ void rpf_axis(const KParams &P, const uint8_t *quad, 
 {
     const int N = axis == 0 ? P.Nv : P.Nh;
     const uint8_t *fr = quad + (size_t)(axis == 0 ? 0 : P.F + 2 * P.Nv) * P.plane_stride;
-    const unsigned i0 = rpf_load(fr), i1 = rpf_load(fr + P.plane_stride), i2 = rpf_load(fr + 2 * P.plane_stride);
-    const unsigned i3 = P.F == 4 ? rpf_load(fr + 3 * P.plane_stride) : 0u;
+    const unsigned i0 = quad_load(fr), i1 = quad_load(fr + P.plane_stride), i2 = quad_load(fr + 2 * P.plane_stride);
+    const unsigned i3 = P.F == 4 ? quad_load(fr + 3 * P.plane_stride) : 0u;
     const uint8_t *gr = fr + (size_t)P.F * P.plane_stride;
     unsigned b[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 4; k++) a.code[k] = 0;
 #pragma unroll 2
     for (int i = 0; i < N; i++) {
-        const unsigned pos = rpf_load(gr + (size_t)i * P.plane_stride), inv = rpf_load(gr + (size_t)(N + i) * P.plane_stride);
+        const unsigned pos = quad_load(gr + (size_t)i * P.plane_stride), inv = quad_load(gr + (size_t)(N + i) * P.plane_stride);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            b[k] ^= rpf_byte(pos, k) >= rpf_byte(inv, k) ? 1u : 0u;  // 4/phase_unwrap.cpp:183, :187-191
+            b[k] ^= quad_byte(pos, k) >= quad_byte(inv, k) ? 1u : 0u;  // 4/phase_unwrap.cpp:183, :187-191
             a.code[k] = a.code[k] * 2 + (int)b[k];                   // :193
         }
     }
@@ -73,7 +69,7 @@ __device__ __forceinline__ void rpf_axis(const KParams &P, const uint8_t *quad, 
     for (int k = 0; k < 4; k++) {
         a.w[k] = a.unw[k] = 0.f;
         if (!(bits >> k & 1u)) continue;
-        const float phi = wrapped_phase<false>(P.F, rpf_byte(i0, k), rpf_byte(i1, k), rpf_byte(i2, k), rpf_byte(i3, k), nullptr, K);
+        const float phi = wrapped_phase<false>(P.F, quad_byte(i0, k), quad_byte(i1, k), quad_byte(i2, k), quad_byte(i3, k), nullptr, K);
         const bool in_range = axis == 0 ? (gx0 + k >= 1 && gx0 + k <= P.fullW - 2) : (gy >= 1 && gy <= P.fullH - 2);  // :285 / :304
         if (in_range) {
             a.w[k] = shift_pi(phi);
@@ -84,7 +80,7 @@ __device__ __forceinline__ void rpf_axis(const KParams &P, const uint8_t *quad, 
 
 // what the pixels of a quad at window (col0, row) bring into a neighbourhood of `axis` (period_request / period_staged): the absolute
 // phase of a sample -- valid bit set, inside window columns 1..W-2 (vertical axis) or window rows 1..H-2 (horizontal) -- else +infinity
-__device__ __forceinline__ rpf_f32x4 rpf_staged(const KParams &P, int axis, unsigned bits, int col0, int row, const float unw[4])
+__device__ __forceinline__ f32x4 rpf_staged(const KParams &P, int axis, unsigned bits, int col0, int row, const float unw[4])
 {
     float s[4];
 #pragma unroll
@@ -92,7 +88,7 @@ __device__ __forceinline__ rpf_f32x4 rpf_staged(const KParams &P, int axis, unsi
         const bool in_range = axis == 0 ? (col0 + k >= 1 && col0 + k <= P.W - 2) : (row >= 1 && row <= P.H - 2);
         s[k] = (bits >> k & 1u) && in_range ? unw[k] : period_no_sample();
     }
-    return (rpf_f32x4){s[0], s[1], s[2], s[3]};
+    return (f32x4){s[0], s[1], s[2], s[3]};
 }
 
 // k_period_jumps + k_period_apply of one pixel: v = its neighbourhood (v[4] the pixel itself), w / code / unw = what stage 4 left
@@ -138,11 +134,8 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
     const bool halo = haxis >= 0 && hcol >= 0 && hcol < P.pitch && hrow >= 0 && hrow < P.H && (haxis == 0 ? P.Nv : P.Nh) != 0;
     const size_t hpx0 = halo ? (size_t)hrow * P.pitch + hcol : 0;
     const bool decodes = P.F != 5;  // check_I_mod_criteria, 3/wrapped_phase.cpp:106-115: with 5 steps nothing is valid (k_wrap)
-    // the camera side of the pixels some view of the launch selects
-    unsigned need = 0u;
-    if (decodes && owns)
-        for (int vi = 0; vi < n_views; vi++) need |= mask_quad_bits(load_mask_quad(P, first_view + vi, (unsigned)px0));
-    double u[4], v[4];
+    const unsigned need = quad_need(P, decodes && owns, first_view, n_views, (unsigned)px0);
+    double u[4], v[4];  // the camera side (written here: sl3d_quad.h, shape)
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         u[k] = v[k] = 0.0;
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
     for (int j = 0; j < 4; j++) { PR.c2[j] = C.Ac[8 + j]; PR.p2[j] = C.Ap[8 + j]; }
     const AtanK K = atan_consts<false>();
     const float nanv = __builtin_nanf("");
-    const rpf_f32x4 none = {period_no_sample(), period_no_sample(), period_no_sample(), period_no_sample()};
+    const f32x4 none = {period_no_sample(), period_no_sample(), period_no_sample(), period_no_sample()};
 #pragma unroll 1
     for (int vi = 0; vi < n_views; vi++) {
         const int view = first_view + vi;
@@ -163,21 +156,21 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
             rpf_axis(P, frames + px0, 0, bits, gx0, gy, K, a0);
             rpf_axis(P, frames + px0, 1, bits, gx0, gy, K, a1);
         }
-        *(rpf_f32x4 *)&s_v[tr][SL3D_RPF_RADIUS + 4 * q] = bits ? rpf_staged(P, 0, bits, col, row, a0.unw) : none;
-        *(rpf_f32x4 *)&s_h[SL3D_RPF_RADIUS + tr][4 * q] = bits ? rpf_staged(P, 1, bits, col, row, a1.unw) : none;
+        *(f32x4 *)&s_v[tr][SL3D_RPF_RADIUS + 4 * q] = bits ? rpf_staged(P, 0, bits, col, row, a0.unw) : none;
+        *(f32x4 *)&s_h[SL3D_RPF_RADIUS + tr][4 * q] = bits ? rpf_staged(P, 1, bits, col, row, a1.unw) : none;
         if (haxis >= 0) {
             const unsigned hbits = decodes && halo ? mask_quad_bits(load_mask_quad(P, view, (unsigned)hpx0)) : 0u;
-            rpf_f32x4 s = none;
+            f32x4 s = none;
             if (hbits) {
                 RpfAxis h;
                 rpf_axis(P, frames + hpx0, haxis, hbits, P.col0 + hcol, P.row0 + hrow, K, h);
                 s = rpf_staged(P, haxis, hbits, hcol, hrow, h.unw);
             }
-            if (haxis == 1) *(rpf_f32x4 *)&s_h[hslot][4 * q] = s;
-            else *(rpf_f32x4 *)&s_v[(t - RPF_HALO_H) >> 1][hslot] = s;
+            if (haxis == 1) *(f32x4 *)&s_h[hslot][4 * q] = s;
+            else *(f32x4 *)&s_v[(t - RPF_HALO_H) >> 1][hslot] = s;
         }
         __syncthreads();
-        float out[12], res[4];
+        float out[12], res[4];  // (quad_clear's statements)
 #pragma unroll
         for (int j = 0; j < 12; j++) out[j] = nanv;
 #pragma unroll
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
                 float run[4 + 2 * SL3D_RPF_RADIUS];
 #pragma unroll
                 for (int j = 0; j < 3; j++) {
-                    const rpf_f32x4 x = *(const rpf_f32x4 *)&s_v[tr][4 * q + 4 * j];
+                    const f32x4 x = *(const f32x4 *)&s_v[tr][4 * q + 4 * j];
                     run[4 * j] = x.x, run[4 * j + 1] = x.y, run[4 * j + 2] = x.z, run[4 * j + 3] = x.w;
                 }
 #pragma unroll
@@ -203,7 +196,7 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
                 float colv[2 * SL3D_RPF_RADIUS + 1][4];
 #pragma unroll
                 for (int d = 0; d < 2 * SL3D_RPF_RADIUS + 1; d++) {
-                    const rpf_f32x4 x = *(const rpf_f32x4 *)&s_h[tr + d][4 * q];
+                    const f32x4 x = *(const f32x4 *)&s_h[tr + d][4 * q];
                     colv[d][0] = x.x, colv[d][1] = x.y, colv[d][2] = x.z, colv[d][3] = x.w;
                 }
 #pragma unroll
@@ -218,9 +211,8 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
             for (int k = 0; k < 4; k++) {
                 if (!(bits >> k & 1u)) continue;  // merge_valid_maps: both axes carry the valid byte of the boundary removal
                 long cx, cy;
-                double dx, dy;
-                const bool okx = correspond(a0.unw[k], P.fwv, P.PW, cx, dx), oky = correspond(a1.unw[k], P.fwh, P.PH, cy, dy);
-                if (!(okx && oky)) continue;      // k_corr
+                if (!quad_correspond(P, a0.unw[k], a1.unw[k], cx, cy)) continue;
+                // (quad_coordinate<false>'s and quad_solve<SUB>'s statements)
                 // k_subpixel: the continuous projector coordinate; k_tri: the c_p_map's integers
                 const double xs = SUB ? correspond_arg(a0.unw[k], P.fwv) : (double)cx, ys = SUB ? correspond_arg(a1.unw[k], P.fwh) : (double)cy;
                 double up, vp, X[3];
@@ -237,25 +229,15 @@ __global__ __launch_bounds__(SL3D_RPF_BLOCK) void k_repair_fused(const KParams P
                 valid |= 1u << (8 * k);
             }
         }
-        if (owns) {
-            const size_t px = (size_t)view * P.px_view_stride + px0;
-            rpf_f32x4 *pts = (rpf_f32x4 *)(P.points + 3 * px);
-#pragma unroll
-            for (int j = 0; j < 3; j++) __builtin_nontemporal_store((rpf_f32x4){out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]}, pts + j);
-            if (SUB) __builtin_nontemporal_store((rpf_f32x4){res[0], res[1], res[2], res[3]}, (rpf_f32x4 *)(residual + px));
-            *(unsigned *)(P.valid + px) = valid;
-        }
+        if (owns) quad_store<SUB>(P, (size_t)view * P.px_view_stride + px0, out, res, valid, residual);
         __syncthreads();  // (every lane has read its neighbourhood: the next view may be staged)
     }
 }
 
 int launch_repair_fused(const KParams &P, const DevCal *C, int first_view, int n_views, float *residual, void *stream)
 {
-    (void)hipGetLastError();
     const dim3 grid((unsigned)((P.pitch + RPF_COLS - 1) / RPF_COLS), (unsigned)((P.H + RPF_ROWS - 1) / RPF_ROWS));
-    if (residual) hipLaunchKernelGGL(k_repair_fused<true>, grid, dim3(SL3D_RPF_BLOCK), 0, (hipStream_t)stream, P, C, first_view, n_views, residual);
-    else hipLaunchKernelGGL(k_repair_fused<false>, grid, dim3(SL3D_RPF_BLOCK), 0, (hipStream_t)stream, P, C, first_view, n_views, residual);
-    return (int)hipGetLastError();
+    return quad_launch(residual ? k_repair_fused<true> : k_repair_fused<false>, grid, stream, P, C, first_view, n_views, residual);
 }
 
 }  // namespace sl3d

@@ -8,7 +8,11 @@ Prints one line per kernel that differs (first differing instruction + the instr
 With `--kernarg` the immediate offsets of scalar loads from the kernel-argument segment (s[0:1] / s[4:5] ...) are masked too
 (a change of the KParams layout moves them and nothing else).  `--pair=OLD=NEW` (any number of them) also compares the kernel of A
 whose name (demangled where llvm-cxxfilt is there, mangled otherwise) contains OLD -- OLD holds no `=` -- with the kernel of B whose
-name contains NEW: a kernel that was renamed."""
+name contains NEW: a kernel that was renamed.  With `--scalar-equivalent` every kernel that differs gets a second line: the histogram delta
+restricted to vector, memory and LDS instructions, scalar loads, waits and barriers (v_*, global_*, flat_*, buffer_*, ds_*, s_load_*,
+s_buffer_load_*, s_waitcnt, s_barrier), the registers, scratch, LDS and occupancy lines of both sides, and the verdict: SCALAR-EQUIVALENT if that
+delta is empty and those lines are all found and equal -- what is left is scalar ALU, compare, branch, move and s_nop -- or NOT EQUIVALENT; the summary then
+counts them.  The default output is unchanged."""
 import collections
 import re
 import subprocess
@@ -60,6 +64,26 @@ def kernels(paths, mask_kernarg):
     return norm
 
 
+RESTRICTED = re.compile(r"^(v_|global_|flat_|buffer_|ds_|s_load_|s_buffer_load_|s_waitcnt|s_barrier)")
+RESOURCES = ("NumVgprs", "NumAgprs", "ScratchSize", "LDSByteSize", "Occupancy")
+
+
+def resources(paths):
+    """kernel symbol -> the resource lines of its `; Kernel info:` block"""
+    out = {}
+    for path in paths.split(","):
+        cur = None
+        for line in open(path, errors="replace"):
+            m = re.match(r"^\s*\.size\s+(_Z\w+),", line)
+            if m:
+                cur = m.group(1)
+                continue
+            m = re.match(r"^; (\w+): (\d+)", line)
+            if m and cur and m.group(1) in RESOURCES:
+                out.setdefault(cur, {})[m.group(1)] = int(m.group(2))
+    return out
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     mask = "--kernarg" in sys.argv
@@ -72,7 +96,9 @@ def main():
         if len(ka) != 1 or len(kb) != 1:
             sys.exit(f"--pair={old}={new}: {len(ka)} kernels of A and {len(kb)} of B match")
         pairs.append((ka[0], kb[0], f"{names[ka[0]]} = {names[kb[0]]}"))
-    same = diff = 0
+    scalar = "--scalar-equivalent" in sys.argv
+    RA, RB = (resources(args[0]), resources(args[1])) if scalar else ({}, {})
+    same = diff = equivalent = 0
     for ka, kb, name in pairs:
         a, b = A[ka], B[kb]
         if a == b:
@@ -85,7 +111,14 @@ def main():
         first = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
         print(f"DIFF {name}: {len(a)} -> {len(b)} lines, first difference at {first}: "
               f"{a[first] if first < len(a) else '<end>'!r} vs {b[first] if first < len(b) else '<end>'!r}; histogram delta {delta or 'none (order only)'}")
-    print(f"{same} kernels identical, {diff} differ; {len(set(A) - set(B))} only in A, {len(set(B) - set(A))} only in B")
+        if scalar:
+            restricted = {op: d for op, d in delta.items() if RESTRICTED.match(op)}
+            ra, rb = RA.get(ka, {}), RB.get(kb, {})
+            ok = not restricted and ra == rb and set(ra) == set(RESOURCES)  # (resource lines missing on a side: not shown equal)
+            equivalent += ok
+            print(f"  {'SCALAR-EQUIVALENT' if ok else 'NOT EQUIVALENT'}: restricted histogram delta {restricted or 'none'}; resources {ra} vs {rb}")
+    print(f"{same} kernels identical, {diff} differ; {len(set(A) - set(B))} only in A, {len(set(B) - set(A))} only in B"
+          + (f"; of the {diff}: {equivalent} scalar-equivalent, {diff - equivalent} not" if scalar else ""))
 
 
 if __name__ == "__main__":
