@@ -3,7 +3,8 @@ the device).  Inputs only: this module imports no scanner (oracle_scan runs the 
 
 FRAMES   `random` (uniform random bytes on both axes: every code, Gray ties, correspondences outside the projector), `flat_17`, `flat_0`,
          `flat_255` (every plane one value: pos == inv on every Gray plane, atan2(0, 0)), `noise3` (make_capture(..., noise=3) of a
-         plane that leaves part of the frame unlit).
+         plane that leaves part of the frame unlit), `steps` (flat fringes 40 / 200 / 90 and codes 0..3 at random: one wrapped phase per
+         axis, four absolute phases, so every neighbourhood of the period repair is full of ties between DIFFERENT periods).
 SHAPES   `base`: the 101 x 37 full frame; the ragged full frames 64 x 5, 19 x 64 and 130 x 3 of
          test_gpu_stage_parity.py::test_ragged_sizes_random_masks; `window`: 70 x 9 at (37, 5) of a 320 x 240 frame.
          The projector is 300 x 200 with N = (7, 6) Gray planes and fringe widths (4, 6): both extents are smaller than fw * 2^N (512 and
@@ -14,7 +15,11 @@ MASKS    random_mask(rng, p), full-frame; the 0.9 mask holds the value 2 on 5 % 
          view_masks(): three masks of the base shape whose selections differ per quad and lane (see there).
 
 `selected(mask)` is stage 3's boundary removal in closed form (tests/test_oracle.py::closed_form_valid): the valid byte every sub-pixel
-kernel masks with.  tests/test_edge_frames.py holds it against the oracle on these masks."""
+kernel masks with.  tests/test_edge_frames.py holds it against the oracle on these masks.
+
+REPAIR   REPAIR_CASES and restated_repair / restated_repaired_scan: the period repair (tests/period_repair_reference.py) of a case's
+         oracle planes and stage 5 restated from the repaired phases -- the yardsticks of tests/test_repair_edge_cases.py (CPU) and
+         tests/test_gpu_repair_edges.py."""
 import functools
 import importlib
 import zlib
@@ -35,12 +40,20 @@ SHAPES = {
     "130x3": ((130, 3), (0, 0), (130, 3)),
     "window": ((70, 9), (37, 5), (320, 240)),
 }
-FRAMES = ("random", "flat_17", "flat_0", "flat_255", "noise3")
+FRAMES = ("random", "flat_17", "flat_0", "flat_255", "noise3", "steps")
+STEPS_FRINGES = (40, 200, 90)
 # (frames, shape, p of the random mask): every frame set on the base shape with every pixel selected, the frame's border lines included;
 # `random` on the base shape under the mask that holds the value 2, on the ragged shapes and on the window, each under one random mask
 BASE_CASES = tuple((f, "base", 1.0) for f in ("random", "flat_17", "noise3"))
 RAGGED_CASES = (("random", "base", 0.9), ("random", "64x5", 0.5), ("random", "19x64", 0.9), ("random", "130x3", 1.0), ("random", "window", 0.9))
 CASES = BASE_CASES + RAGGED_CASES
+# the cases of the period repair: those, `steps` under both masks of the base shape, and the window with every pixel selected -- under the 0.9
+# mask stage 3 leaves no pixel of window column 0 selected, and that column (frame column 37: an absolute phase, but no sample) is what the
+# window is there for
+REPAIR_CASES = CASES + (("steps", "base", 1.0), ("steps", "base", 0.9), ("random", "window", 1.0))
+# whether one pass at radius 4 repairs pixels on the (vertical, horizontal) axis: nothing on flat frames, nothing on a horizontal axis of
+# one or three sample rows (tests/test_repair_edge_cases.py asserts this of the restatement)
+REPAIRS = {c: (c[0] != "flat_17", c[0] != "flat_17" and c[1] not in ("64x5", "130x3")) for c in REPAIR_CASES}
 
 
 def _syn():
@@ -86,6 +99,13 @@ def frames(name, shape, rig_axis=0, plane=None, noise=3, view=0):
         return tuple([rng.integers(0, 256, (H, W), dtype=np.uint8) for _ in range(c)] for c in counts)
     if name.startswith("flat_"):
         return tuple([np.full((H, W), int(name[5:]), np.uint8) for _ in range(c)] for c in counts)
+    if name == "steps":
+        rng = np.random.default_rng(_seed(name, shape))
+        out = []
+        for n in N:
+            gray = [np.zeros((H, W), np.uint8) for _ in range(n - 2)] + [(255 * rng.integers(0, 2, (H, W))).astype(np.uint8) for _ in range(2)]
+            out.append([np.full((H, W), v, np.uint8) for v in STEPS_FRINGES] + gray + [255 - g for g in gray])
+        return tuple(out)
     assert name == "noise3"
     cap = _syn().make_capture(W, H, PW, PH, N[0], N[1], FW[0], FW[1], cal=rig(rig_axis, *full), plane=NOISE_PLANE if plane is None else plane, noise=noise, view=view,
                               col0=col0, row0=row0, full=full)
@@ -100,21 +120,32 @@ def case(name, shape, p, rig_axis=0):
     return dict(W=W, H=H, origin=origin, full=full, planes=frames(name, shape, rig_axis), mask=mask, cal=_syn().cal_tuple(rig(rig_axis, *full)))
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_scan(name, shape, p, rig_axis=0):
-    """The oracle's planes of a case, both axes decoded, computed once: dict(w, code, unw, valid_axis (pairs v, h), valid, c_p_map, ipoints,
-    A_cam, A_proj).  A window is run as the oracle's own image at its origin, under the window of the mask: compare on inner(shape)."""
+def _oracle(W, H, origin, mask, cal, planes):
     from oracle.oracle import Oracle
-    c = case(name, shape, p, rig_axis)
-    o = Oracle(c["W"], c["H"], PW, PH, N[0], N[1], FW[0], FW[1], col0=c["origin"][0], row0=c["origin"][1])
-    o.set_mask(window(c["mask"], shape))
-    o.set_calibration(*c["cal"])
-    o.run_scan(*c["planes"])
+    o = Oracle(W, H, PW, PH, N[0], N[1], FW[0], FW[1], col0=origin[0], row0=origin[1])
+    o.set_mask(mask)
+    o.set_calibration(*cal)
+    o.run_scan(*planes)
     A, B = o.projection_matrices()
     out = dict(w=(o.wrapped_phi(0), o.wrapped_phi(1)), code=(o.code(0), o.code(1)), unw=(o.unwrapped_phi(0), o.unwrapped_phi(1)),
                valid_axis=(o.valid_map(0), o.valid_map(1)), valid=o.valid_map(2), c_p_map=o.c_p_map(), ipoints=o.intersection_points(), A_cam=A, A_proj=B)
     o.close()
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_scan(name, shape, p, rig_axis=0):
+    """The oracle's planes of a case, both axes decoded, computed once: dict(w, code, unw, valid_axis (pairs v, h), valid, c_p_map, ipoints,
+    A_cam, A_proj).  A window is run as the oracle's own image at its origin, under the window of the mask: compare on inner(shape)."""
+    c = case(name, shape, p, rig_axis)
+    return _oracle(c["W"], c["H"], c["origin"], window(c["mask"], shape), c["cal"], c["planes"])
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_view_scan(v, rig_axis=0):
+    """oracle_scan of capture v of view_captures() under mask v of view_masks() (the base shape and its calibration)."""
+    c = case("flat_17", "base", 1.0, rig_axis)
+    return _oracle(c["W"], c["H"], c["origin"], view_masks()[v], c["cal"], view_captures(rig_axis)[v])
 
 
 @functools.lru_cache(maxsize=None)
@@ -136,6 +167,71 @@ def restated_two_axis(name, shape, p, anchored):
     xy = AR.correspondences(o["w"], o["code"], o["unw"], o["valid_axis"], FW, 3, N, c["origin"], c["full"]) if anchored else \
         SR.correspondences(*o["unw"], *o["valid_axis"], *FW)
     return dict(SR.triangulate(xy, o["valid"], c["cal"], o["A_cam"], o["A_proj"], c["origin"]), xy=xy)
+
+
+# ---- the period repair -----------------------------------------------------------------------------------------------------------------------
+def stage5(unw, valid_axis):
+    """(merged valid uint8, c_p_map int64 (H, W, 2)) restated from the absolute phases (float32) and valid bytes of both axes, as
+    include/sl3d.h states stage 5: a pixel is valid iff both axis bytes are 1 and, per axis, 0 <= rint(fw * (unw / ((2 * 22) / 7))) <=
+    extent - 1 (rint in float64, half to even); c_p_map holds those integers, and 0 where the pixel is not valid."""
+    ok = (valid_axis[0] == 1) & (valid_axis[1] == 1)
+    r = []
+    for a in (0, 1):
+        assert unw[a].dtype == np.float32
+        r.append(np.rint(np.float64(FW[a]) * (unw[a].astype(np.float64) / ((2.0 * 22.0) / 7.0))))
+        ok = ok & (r[a] >= 0.0) & (r[a] <= np.float64(EXTENT[a] - 1))
+    cp = np.where(ok[..., None], np.stack(r, axis=-1), 0.0).astype(np.int64)
+    return ok.astype(np.uint8), cp
+
+
+def repair(o, radius, passes=1):
+    """tests/period_repair_reference.py over both axes of a dict of stage planes (w, code, unw, valid_axis: pairs), `passes` times: dict(code,
+    unw (pairs), counts [pass][axis] = (repaired, unrepairable))."""
+    import period_repair_reference as PR
+    code, unw, counts = list(o["code"]), list(o["unw"]), []
+    for _ in range(passes):
+        res = [PR.repair_periods(code[a], o["w"][a], unw[a], o["valid_axis"][a], a, radius, N[a]) for a in (0, 1)]
+        code, unw = [r[0] for r in res], [r[1] for r in res]
+        counts.append(tuple(r[2:] for r in res))
+    return dict(code=tuple(code), unw=tuple(unw), counts=counts)
+
+
+@functools.lru_cache(maxsize=None)
+def stage_planes(name, shape, p):
+    """The planes stages 3 and 4 leave ON THE DEVICE, from the oracle alone: dict(w, code, unw, valid_axis (pairs), A_cam, A_proj).  A full
+    frame: oracle_scan.  A window: the device runs stage 3 over the whole frame's mask and stage 4's loop by FRAME coordinates, so the
+    window's first and last lines carry an absolute phase, while the oracle sees a window as its own image.  It is therefore run on the
+    window grown by one pixel on every side, with every pixel selected (the added pixels repeat their neighbours: stages 3 and 4 form a
+    pixel's phases from its own bytes), and the valid byte is selected() of the full-frame mask.  Compare where the valid byte is 1."""
+    o = oracle_scan(name, shape, p)
+    if inner(shape).all():
+        return o
+    c = case(name, shape, p)
+    (col0, row0), (W, H), (fullW, fullH) = c["origin"], (c["W"], c["H"]), c["full"]
+    assert 2 <= col0 and col0 + W <= fullW - 2 and 2 <= row0 and row0 + H <= fullH - 2
+    g = _oracle(W + 2, H + 2, (col0 - 1, row0 - 1), np.ones((H + 2, W + 2), np.uint8), c["cal"], [[np.pad(q, 1, mode="edge") for q in axis] for axis in c["planes"]])
+    sel = window(selected(c["mask"]), shape)
+    cut = lambda pair: tuple(np.ascontiguousarray(a[1:-1, 1:-1]) for a in pair)
+    return dict(w=cut(g["w"]), code=cut(g["code"]), unw=cut(g["unw"]), valid_axis=(sel, sel), A_cam=o["A_cam"], A_proj=o["A_proj"])
+
+
+@functools.lru_cache(maxsize=None)
+def restated_repair(name, shape, p, radius, passes=1):
+    """repair() of stage_planes() of a case, computed once."""
+    return repair(stage_planes(name, shape, p), radius, passes)
+
+
+@functools.lru_cache(maxsize=None)
+def restated_view_repair(v, radius):
+    return repair(oracle_view_scan(v), radius)
+
+
+@functools.lru_cache(maxsize=None)
+def restated_repaired_scan(name, shape, p, radius=4):
+    """Stage 5 behind one pass per axis: dict(valid, c_p_map, unw, code, counts, valid_before)."""
+    o, r = stage_planes(name, shape, p), restated_repair(name, shape, p, radius)
+    valid, cp = stage5(r["unw"], o["valid_axis"])
+    return dict(valid=valid, c_p_map=cp, unw=r["unw"], code=r["code"], counts=r["counts"][0], valid_before=stage5(o["unw"], o["valid_axis"])[0])
 
 
 def window(a, shape):

@@ -9,7 +9,10 @@ The captures in two dimensions (PC.GRID_CASES, PC.make_fuzz_case, PC.make_wide_c
 span several tiles of k_period_jumps<0> (256 x 8) and <1> (64 x 32, 8 rows per wave) both ways, with partial last tiles and padding
 columns of the pitch inside a launched tile, both axes carry jumps, and no two lines of a tile ask for the same correction
 (tests/test_period_repair_arith.py asserts that of the restatement) -- so a window read from the wrong row of a tile or the wrong lane, or
-a jump written to another line, cannot equal the restatement."""
+a jump written to another line, cannot equal the restatement.
+
+All of these captures are smooth planes: nothing in them is random, flat, ragged in size or under a mask that holds a value other than
+0 / 1.  tests/test_gpu_repair_edges.py runs the same check (tests/period_repair_checks.py) on the edge frames of tests/edge_frames.py."""
 import ctypes
 import functools
 
@@ -20,14 +23,11 @@ from conftest import pkg
 
 import period_cases as PC
 import period_repair_reference as PR
+from period_repair_checks import assert_same_planes as _assert_same_planes, bits as _bits, check_pass, planes as _planes, stages34 as _stages34
 
 pytestmark = pytest.mark.gpu
 
 RADII = (1, 4, 8)
-
-
-def _bits(a):
-    return a.view(np.uint32)
 
 
 def _open(case, max_views=1, keep=True, calibrate=False):
@@ -45,36 +45,8 @@ def _load(sc, case, view=0):
     sc.set_frames(1, case["planes_h"], view=view)
 
 
-def _stages34(sc, view=0):
-    for a in (0, 1):
-        sc.compute_wrapped_phase(a, view)
-    for a in (0, 1):
-        sc.unwrap_phase(a, view)
-
-
-def _planes(sc, axis, view=0):
-    return sc.code(axis, view), sc.wrapped_phase(axis, view), sc.unwrapped_phase(axis, view), sc.valid_map(axis, view)
-
-
-def _assert_same_planes(got, want, what):
-    for g, w, n in zip(got, want, ("code", "wrapped", "unwrapped", "valid")):
-        assert np.array_equal(g.view(np.uint32) if g.dtype == np.float32 else g, w.view(np.uint32) if w.dtype == np.float32 else w), (what, n)
-
-
 def _check_pass(sc, case, axis, radius, view=0, what=""):
-    """One repair_periods call against the restatement applied to the planes downloaded before it."""
-    before = _planes(sc, axis, view)
-    other = _planes(sc, 1 - axis, view)
-    want_code, want_unw, rep, unrep = PR.repair_periods(*before, axis, radius, case["N"])
-    counts = sc.repair_periods(axis, radius, view)
-    code, wrapped, unw, valid = _planes(sc, axis, view)
-    bad = np.argwhere(code != want_code)
-    assert bad.size == 0, (what, axis, radius, "code", bad[:5].tolist())
-    assert np.array_equal(_bits(unw), _bits(want_unw)), (what, axis, radius, "unwrapped")
-    assert counts == (rep, unrep), (what, axis, radius, counts, (rep, unrep))
-    assert np.array_equal(_bits(wrapped), _bits(before[1])) and np.array_equal(valid, before[3]), (what, axis, radius, "wrapped / valid touched")
-    _assert_same_planes(_planes(sc, 1 - axis, view), other, (what, "the other axis"))
-    return rep, unrep
+    return check_pass(sc, case["N"], axis, radius, view, what)
 
 
 @functools.lru_cache(maxsize=None)

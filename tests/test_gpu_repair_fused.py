@@ -7,7 +7,9 @@ tests/test_gpu_period_repair.py holds that route against the NumPy restatement. 
 of the points and valid planes (sub-pixel mode: and the residual plane) over EVERY pixel of the window.  The captures are those of
 tests/period_cases.py; tests/test_repair_fused_cases.py asserts that they cover every seam of the new kernel's tile.  Every yardstick is
 computed once and checked for what it is there for BEFORE a device result is compared with it: the staged call reports repaired pixels,
-and the repaired scan differs from the unrepaired one of the same context."""
+and the repaired scan differs from the unrepaired one of the same context.
+What these smooth captures cannot see -- random and flat frames, ragged sizes, a mask holding the value 2, per-view masks at the tile's
+seams, sl3d_set_masks_modulated -- is in tests/test_gpu_repair_edges.py."""
 import functools
 
 import numpy as np
