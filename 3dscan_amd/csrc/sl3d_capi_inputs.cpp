@@ -1,6 +1,7 @@
 // sl3d_capi_inputs.cpp -- what goes INTO a context: selection masks (H0 / S3b / S3d: prepared by k_mask_prepare when they are set, or deferred to
 // the launch that consumes them -- a MASKIN launch of the fused kernel) and frames, in row-major planes or the reference's own [col][row] layouts.
 #include "sl3d_capi_internal.h"
+#include "../../include/sl3d_fuse.h"  // sl3d_fuse_exposures, sl3d_get_exposure_map: the calls at the end of this file
 
 
 // Quads of `view` that hold a valid pixel, as k_mask_prepare counted them: the sum of the view's per-block words, known only once
@@ -511,6 +512,56 @@ try {
     x->quad_last[dst] = x->quad_last[src];
     x->quad_sum_seq[dst] = 0u;  // (a sum cached for dst under the same sequence number -- one sl3d_set_masks call serves many views -- is not the source's)
     return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// The exposure fusion (the rule: include/sl3d_fuse.h; k_fuse_exposures, sl3d_exposure.hip): views [first_view, first_view + n_exposures) are the
+// exposures of one scene, dst_view gets per pixel the bytes of the exposure chosen.  Frames only: no mask, no dense result, no stage plane
+// and no calibration is read or written, so the views' deferred masks stay deferred.  One launch on the context's stream behind the
+// launch lanes (ON_DEVICE), in front of it the memset of the count words.
+static_assert(SL3D_EXPOSURE_COUNTS == SL3D_MAX_EXPOSURES + 1, "one count per exposure and one of the pixels clipped in every exposure");
+extern "C" int sl3d_fuse_exposures(sl3d_ctx *x, int first_view, int n_exposures, int dst_view, int saturation, uint32_t *counts)
+try {
+    if (!x) return SL3D_E_INVALID_ARG;
+    if (n_exposures < 1 || n_exposures > SL3D_MAX_EXPOSURES) return fail(x, SL3D_E_INVALID_ARG, "fuse_exposures: n_exposures must be 1 .. SL3D_MAX_EXPOSURES");
+    int rc = check_view(x, first_view, n_exposures);
+    if (rc || (rc = check_view(x, dst_view))) return rc;
+    if (dst_view >= first_view && dst_view < first_view + n_exposures) return fail(x, SL3D_E_INVALID_ARG, "fuse_exposures: dst_view is one of the exposures");
+    if (saturation < 1 || saturation > 256) return fail(x, SL3D_E_INVALID_ARG, "fuse_exposures: saturation must be 1 .. 256 (256: nothing clips)");
+    const KParams &P = x->P;
+    if (P.F != 3 && P.F != 4) return fail(x, SL3D_E_UNSUPPORTED, "fuse_exposures: the score is defined for n_fringe 3 and 4 (with 5 no scan is valid)");
+    ON_DEVICE(x);
+    if ((rc = ensure_plane(x, &x->d_exposure_map, (size_t)x->cfg.max_views * P.px_view_stride)) ||
+        (rc = ensure_plane(x, &x->d_exposure_counts, (size_t)SL3D_EXPOSURE_COUNTS)))
+        return rc;
+    x->exposure_written.resize((size_t)x->cfg.max_views, 0);
+    ExposurePlan X{};
+    for (int axis = 0; axis < 2; axis++) {  // (the planes in use of a coded axis: what frame_plane_runs names, its fringe planes first)
+        if (x->one_axis >= 0 && x->one_axis != axis) continue;
+        const int N = axis == 0 ? P.Nv : P.Nh;
+        X.base[X.n_axes] = axis == 0 ? 0 : P.F + 2 * P.Nv;
+        X.count[X.n_axes++] = x->direct_gray ? direct_gray_planes(P.F, N) : P.F + 2 * N;
+    }
+    HIPCHK(x, hipMemsetAsync(x->d_exposure_counts, 0, SL3D_EXPOSURE_COUNTS * sizeof(unsigned), x->stream));
+    rc = launched(x, launch_fuse_exposures(P, X, first_view, n_exposures, dst_view, saturation, x->d_exposure_map + (size_t)dst_view * P.px_view_stride,
+                                           x->d_exposure_counts, x->stream));
+    if (rc) return rc;
+    x->exposure_written[(size_t)dst_view] = 1;
+    if (!counts) return SL3D_OK;
+    HIPCHK(x, hipMemcpyAsync(counts, x->d_exposure_counts, (size_t)(n_exposures + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    SYNC_FOR_CALLER(x);
+    return SL3D_OK;
+}
+SL3D_CATCH(x)
+
+// the exposure map the last fusion into `view` left: a byte per window pixel, exposure | 0x80 where that exposure clips
+extern "C" int sl3d_get_exposure_map(sl3d_ctx *x, int view, uint8_t *out, size_t stride)
+try {
+    int rc = check_view(x, view);
+    if (rc) return rc;
+    if (!out || stride < (size_t)x->P.W) return fail(x, SL3D_E_INVALID_ARG, "get_exposure_map: null output or stride < width");
+    if (!x->d_exposure_map || !x->exposure_written[(size_t)view]) return fail(x, SL3D_E_STATE, "get_exposure_map: no sl3d_fuse_exposures has written this view");
+    return download_plane(x, x->d_exposure_map + (size_t)view * x->P.px_view_stride, 1, out, stride);
 }
 SL3D_CATCH(x)
 

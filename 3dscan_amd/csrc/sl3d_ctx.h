@@ -171,6 +171,11 @@ struct sl3d_ctx {
     bool residual_ready = false;
     unsigned *d_subpixel_partials = nullptr, *d_subpixel_counts = nullptr;
     double *d_subpixel_xy = nullptr;
+    // sl3d_fuse_exposures (allocated on the first fusion): the exposure maps [max_views][px_view_stride] bytes, the SL3D_EXPOSURE_COUNTS
+    // words a launch adds its counts to, and which views' maps a fusion has written (sl3d_get_exposure_map refuses the others)
+    uint8_t *d_exposure_map = nullptr;
+    unsigned *d_exposure_counts = nullptr;
+    std::vector<char> exposure_written;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip -- these four share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip -- the four before it share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -257,6 +257,16 @@ int launch_unwrap_direct(const KParams &P, int view, int axis, void *stream);
 int launch_direct_gray(const KParams &P, const DevCal *d_cal, int axes, int first_view, int n_views, float *residual, bool anchor, void *stream);
 // the fringe-modulation test of a one-axis context: gamma of the coded axis alone, no plane of the other axis read
 int launch_modulation_select_one(const KParams &P, int first_view, int n_views, uint8_t *staging, bool has_mask, double thr, int axis, void *stream);
+// the exposure fusion (sl3d_exposure.hip, sl3d_exposure.h; the rule: include/sl3d_fuse.h, sl3d_fuse_exposures).  The planes in use: of coded axis
+// i (n_axes of them) the count[i] planes from plane base[i] of planes_per_view on, its F fringe planes first.  Exposure e is view first_view
+// + e; map: the map plane of dst_view ([row][pitch] bytes); counts: n_exposures + 1 words the launch ADDS to (the caller has cleared them)
+#define SL3D_EXPOSURE_COUNTS 9  // SL3D_MAX_EXPOSURES + 1
+struct ExposurePlan {
+    int n_axes;
+    int base[2], count[2];
+};
+int launch_fuse_exposures(const KParams &P, const ExposurePlan &X, int first_view, int n_exposures, int dst_view, int saturation, uint8_t *map,
+                          unsigned *counts, void *stream);
 // the period-repaired scan of a timed context (sl3d_repair_fused.hip, SL3D_FLAG_REPAIR_PERIODS): what launch_wrap / launch_unwrap of both
 // axes, launch_period_repair(radius SL3D_REPAIR_FUSED_RADIUS) of every axis that has Gray planes, launch_corr and launch_tri leave in
 // the views' points and valid planes, in one launch; residual != NULL: the sub-pixel ending instead (launch_subpixel(+inf)) and the

@@ -192,6 +192,12 @@ _PROTOTYPES = (
 )
 # every symbol include/sl3d.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = tuple(row[0] for row in _PROTOTYPES)
+# the same for include/sl3d_fuse.h, the header of the exposure fusion (tests/test_exposure_flag.py holds one against the other)
+_FUSE_PROTOTYPES = (
+    ("sl3d_fuse_exposures", [_vp, _i, _i, _i, _i, _pu]),
+    ("sl3d_get_exposure_map", [_vp, _i, _vp, _sz]),
+)
+FUSE_SYMBOLS = tuple(row[0] for row in _FUSE_PROTOTYPES)
 
 _lib = None
 
@@ -210,7 +216,7 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    for name, argtypes, *restype in _PROTOTYPES:
+    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES:
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -523,6 +529,19 @@ class Scanner(_Handle):
 
     def copy_view(self, src_view, dst_view):
         self._chk(self.L.sl3d_copy_view(self._h, src_view, dst_view), "sl3d_copy_view")
+
+    def fuse_exposures(self, first_view, n_exposures, dst_view, saturation=255, counts=True):
+        """sl3d_fuse_exposures: views first_view .. first_view + n_exposures - 1 hold one pattern set at n_exposures (1 .. 8) exposures;
+        dst_view gets, per pixel, the bytes of the exposure with the fewest planes >= saturation, among those the best modulated, among
+        those the first (the rule: include/sl3d_fuse.h).  Returns np.uint32[n_exposures + 1]: the pixels taken from each exposure, then the
+        pixels clipped in every exposure; counts=False: the call stays asynchronous and returns None."""
+        out = (C.c_uint32 * (max(n_exposures, 0) + 1))() if counts else None
+        self._chk(self.L.sl3d_fuse_exposures(self._h, first_view, n_exposures, dst_view, saturation, out), "sl3d_fuse_exposures")
+        return np.array(out, dtype=np.uint32) if counts else None
+
+    def exposure_map(self, view=0):
+        """The map the last fuse_exposures into `view` left: uint8 [H][W], the chosen exposure | 0x80 where that exposure clips."""
+        return self._plane("sl3d_get_exposure_map", np.uint8, view)
 
     # ---- the reference's four stage entry points ----------------------------------------------
     def compute_wrapped_phase(self, pattern_type, view=0):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.20.0"
+#define SL3D_VERSION_STRING "0.21.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -369,6 +369,9 @@ int sl3d_set_frames_range(sl3d_ctx *ctx, int view, int axis, int first_plane, co
 
 /* Device-to-device duplicate of one resident view (frame stack + mask) into another slot of the batch. */
 int sl3d_copy_view(sl3d_ctx *ctx, int src_view, int dst_view);
+
+/* (0.21.0) Exposure fusion on the device -- several exposures of one pattern set, one per view, fused into one ordinary view -- has a header
+ * of its own, include/sl3d_fuse.h: the rule, SL3D_MAX_EXPOSURES and the two calls that work on a context of this header. */
 
 /* Synthetic capture generated on the device into view slot `view` (inputs for tests and benchmarks; the pattern
  * formulas are the reference generator's, 1/pattern_generator.cpp:80-105,302,313,497, Pi = 22/7): plane[3] = z0,a,b of
