@@ -176,6 +176,11 @@ struct sl3d_ctx {
     uint8_t *d_exposure_map = nullptr;
     unsigned *d_exposure_counts = nullptr;
     std::vector<char> exposure_written;
+    // sl3d_filter_outliers (allocated on the first call): the support planes [max_views][px_view_stride] bytes, [max_views][2] words a
+    // call adds its views' counts to, and which views' planes a call has written (sl3d_get_support refuses the others)
+    uint8_t *d_support = nullptr;
+    unsigned *d_outlier_counts = nullptr;
+    std::vector<char> support_written;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip -- the four before it share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip -- the four before the last two share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -267,6 +267,13 @@ struct ExposurePlan {
 };
 int launch_fuse_exposures(const KParams &P, const ExposurePlan &X, int first_view, int n_exposures, int dst_view, int saturation, uint8_t *map,
                           unsigned *counts, void *stream);
+// the radius outlier filter (sl3d_outlier.hip, sl3d_outlier.h; the rule: include/sl3d_filter.h, sl3d_filter_outliers).  support: the support
+// planes [max_views][px_view_stride] bytes, view v's at v * px_view_stride.  launch_outlier_support writes the planes of the launch's views
+// (radius 1 .. SL3D_OUTLIER_MAX_RADIUS) and changes nothing else; launch_outlier_apply, behind it, rejects the samples whose support is
+// below min_neighbours (0: none, the launch only counts) in P.valid, P.points and, where the context has it, P.ipoints; counts: [n_views][2]
+// words the launch ADDS the views' samples and rejected samples to (the caller has cleared them)
+int launch_outlier_support(const KParams &P, int first_view, int n_views, int radius, float max_dist, uint8_t *support, void *stream);
+int launch_outlier_apply(const KParams &P, int first_view, int n_views, int min_neighbours, const uint8_t *support, unsigned *counts, void *stream);
 // the period-repaired scan of a timed context (sl3d_repair_fused.hip, SL3D_FLAG_REPAIR_PERIODS): what launch_wrap / launch_unwrap of both
 // axes, launch_period_repair(radius SL3D_REPAIR_FUSED_RADIUS) of every axis that has Gray planes, launch_corr and launch_tri leave in
 // the views' points and valid planes, in one launch; residual != NULL: the sub-pixel ending instead (launch_subpixel(+inf)) and the

@@ -198,6 +198,12 @@ _FUSE_PROTOTYPES = (
     ("sl3d_get_exposure_map", [_vp, _i, _vp, _sz]),
 )
 FUSE_SYMBOLS = tuple(row[0] for row in _FUSE_PROTOTYPES)
+# ... and for include/sl3d_filter.h, the header of the outlier filter (tests/test_outlier_flag.py)
+_FILTER_PROTOTYPES = (
+    ("sl3d_filter_outliers", [_vp, _i, _i, _i, _f, _i, _pu]),
+    ("sl3d_get_support", [_vp, _i, _vp, _sz]),
+)
+FILTER_SYMBOLS = tuple(row[0] for row in _FILTER_PROTOTYPES)
 
 _lib = None
 
@@ -216,7 +222,7 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES:
+    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES:
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -542,6 +548,21 @@ class Scanner(_Handle):
     def exposure_map(self, view=0):
         """The map the last fuse_exposures into `view` left: uint8 [H][W], the chosen exposure | 0x80 where that exposure clips."""
         return self._plane("sl3d_get_exposure_map", np.uint8, view)
+
+    def filter_outliers(self, radius, max_dist, min_neighbours, first_view=0, n_views=1, counts=True):
+        """sl3d_filter_outliers: every valid pixel of views first_view .. first_view + n_views - 1 that has fewer than min_neighbours valid
+        pixels within max_dist (mm, 3-D) among the (2 * radius + 1)^2 - 1 pixels around it (radius 1 .. 4) loses its valid byte, its point
+        becomes NaN (the rule: include/sl3d_filter.h).  In place: points(), cloud(), the meshes ... then see the filtered scan; run() over the
+        view restores it.  min_neighbours=0 only writes the support planes.  Returns np.uint32[n_views][2]: per view the valid pixels on
+        entry and the rejected ones; counts=False: the call stays asynchronous and returns None."""
+        out = (C.c_uint32 * (2 * max(n_views, 1)))() if counts else None
+        self._chk(self.L.sl3d_filter_outliers(self._h, first_view, n_views, radius, max_dist, min_neighbours, out), "sl3d_filter_outliers")
+        return np.array(out, dtype=np.uint32).reshape(n_views, 2) if counts else None
+
+    def support(self, view=0):
+        """The plane the last filter_outliers over `view` left: uint8 [H][W], the number of valid neighbours within max_dist, 0xFF where the
+        pixel was not valid."""
+        return self._plane("sl3d_get_support", np.uint8, view)
 
     # ---- the reference's four stage entry points ----------------------------------------------
     def compute_wrapped_phase(self, pattern_type, view=0):
