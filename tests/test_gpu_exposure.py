@@ -20,10 +20,10 @@ import pytest
 from conftest import pkg
 
 import exposure_reference as XR
+from exposure_cases import _crafted
 
 pytestmark = pytest.mark.gpu
 
-ALPHABET = np.array([0, 10, 200, 254, 255], np.uint8)
 MARKER = 0x5C
 SHAPES = [(64, 7), (67, 9), (322, 13), (1920, 3)]
 GRAYS = [(7, 7), (6, 5), (0, 4), (16, 16)]
@@ -38,20 +38,6 @@ def _bits(a):
 
 def _ppv(F, N):
     return 2 * F + 2 * N[0] + 2 * N[1]
-
-
-@functools.lru_cache(maxsize=None)
-def _crafted(W, H, ppv, seed):
-    """uint8 [8][ppv][H][W]: half the pixels of an exposure take one of six pooled plane vectors (equal clip counts AND equal scores across
-    exposures are frequent), the others independent bytes; exposure 2 is exposure 0 and exposure 6 is exposure 3."""
-    rng = np.random.default_rng(seed)
-    stack = ALPHABET[rng.integers(0, len(ALPHABET), (8, ppv, H, W))]
-    pool = ALPHABET[rng.integers(0, len(ALPHABET), (6, ppv))]
-    pooled = pool[rng.integers(0, 6, (8, H, W))].transpose(0, 3, 1, 2)                 # [8][ppv][H][W]
-    stack = np.where(rng.random((8, 1, H, W)) < 0.5, pooled, stack)
-    stack[2], stack[6] = stack[0], stack[3]
-    stack.setflags(write=False)
-    return stack
 
 
 def _scanner(W, H, N, F=3, max_views=1, **kw):
