@@ -424,6 +424,7 @@ try {
         return launch_register(clouds + 3 * (size_t)k * stride, out, (long)n, R4, tx, ty, tz, x->stream);
     });
     if (rc) return rc;
+    x->reg_total = off;  // (sl3d_voxel_grid over the registered cloud)
     SYNC_FOR_CALLER(x);
     *total = off;
     const int64_t m = off < capacity ? off : capacity;
@@ -460,6 +461,7 @@ try {
         return n > 0 ? launch_seg_close(x->P, first_view + k, 1, SegClose{out, 0, false, 0, R4, tx, ty, tz}, x->stream) : 0;
     });
     if (rc) return rc;
+    x->reg_total = off;
     *total = off;
     const int64_t m = off < capacity ? off : capacity;
     if (xyz && m > 0) HIPCHK(x, hipMemcpyAsync(xyz, x->d_reg, (size_t)m * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));

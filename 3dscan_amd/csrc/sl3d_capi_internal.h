@@ -7,6 +7,7 @@
 //   sl3d_capi_period.cpp   the period repair between stage 4 and stage 5 (sl3d_repair_periods)
 //   sl3d_capi_subpixel.cpp stage 7 from the continuous correspondences, its residual plane (sl3d_triangulate_subpixel and its getters)
 //   sl3d_capi_filter.cpp   the radius outlier filter of the dense result (include/sl3d_filter.h: sl3d_filter_outliers, sl3d_get_support)
+//   sl3d_capi_voxel.cpp    the voxel grid over a cloud (include/sl3d_voxel.h: sl3d_voxel_grid, sl3d_get_voxel_grid)
 #pragma once
 #include <hip/hip_runtime.h>
 

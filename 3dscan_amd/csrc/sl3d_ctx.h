@@ -181,6 +181,21 @@ struct sl3d_ctx {
     uint8_t *d_support = nullptr;
     unsigned *d_outlier_counts = nullptr;
     std::vector<char> support_written;
+    // sl3d_voxel_grid (all allocated on first use and grown with the cloud, vox_cap: the elements each holds, in the order
+    // sl3d_capi_voxel.cpp names them): the upload of a host cloud, the hash table (one allocation: key, first, count, sums), a slot word
+    // per point, the block scratch (vox_s.tot is not used: the total is one of the call's words), the three outputs and the call's
+    // words.  vox_n: the points of the last grid call, -1 before any (sl3d_get_voxel_grid refuses then).  reg_total: the points the last
+    // sl3d_register_views / sl3d_register_clouds left in d_reg, -1 before any
+    float *d_vox_in = nullptr;
+    uint8_t *d_vox_table = nullptr;
+    unsigned *d_vox_slot = nullptr;
+    CompactScratch vox_s{};
+    float *d_vox_xyz = nullptr;
+    int32_t *d_vox_first = nullptr;
+    unsigned *d_vox_count = nullptr;
+    unsigned long long *d_vox_words = nullptr;
+    size_t vox_cap[8] = {0};
+    int64_t vox_n = -1, reg_total = -1;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

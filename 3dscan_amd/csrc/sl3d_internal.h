@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip -- the four before the last two share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip -- the four before the last two share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -303,6 +303,27 @@ inline ViewPlanes view_planes(const KParams &P, int first_view)
 int launch_compact_views(const KParams &P, int first_view, int n_views, const CompactScratch &s, float *clouds, const uint8_t *texture,
                          uint8_t *rgb_out, void *stream);
 int launch_compact_scan(const unsigned *counts, unsigned long long *offsets, int n, int n_arrays, unsigned long long *totals, void *stream);
+// the voxel grid over an unorganised cloud (sl3d_voxel.hip, sl3d_voxel.h; the rule: include/sl3d_voxel.h, sl3d_voxel_grid).  The table is a
+// structure of arrays of `capacity` slots (voxel_table_capacity); sums: 3 x capacity, the three coordinates one after the other, NULL in
+// first mode.  slot_of: a word per point, padded to whole 1024-point blocks.  words: VOXEL_WORDS 64-bit words of the call.  All of it is
+// initialised on the stream by launch_voxel_grid itself (keys and first to all ones, the rest to zero)
+struct VoxelTable {
+    unsigned long long *key;
+    unsigned *first, *count;
+    long long *sums;
+    unsigned long long capacity;
+};
+enum { VOXEL_WORD_DROPPED, VOXEL_WORD_OCCUPIED, VOXEL_WORD_KEPT, VOXEL_WORD_ERROR, VOXEL_WORDS };
+struct VoxelOut {
+    float *xyz;
+    int *first;
+    unsigned *count;
+};
+// cloud: n (> 0, < 2^31) points on the device.  Memsets, k_voxel_insert, k_voxel_count, k_compact_scan, k_voxel_scatter: out holds the
+// cells kept, in order of first appearance; words[VOXEL_WORD_KEPT] their number (the scan's total), words[VOXEL_WORD_ERROR] is non-zero
+// if a probe ran through the whole table (it cannot at this load factor)
+int launch_voxel_grid(const float *cloud, long long n, float leaf, long long min_points, bool centroid, const VoxelTable &T, unsigned *slot_of,
+                      const CompactScratch &s, unsigned long long *words, const VoxelOut &out, void *stream);
 // the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A row has
 // mesh_row_chunks(P) chunks (1024 pixels of one row), a view mesh_chunks(P) = H times as many; s: the mesh form of CompactScratch,
 // faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)

@@ -76,6 +76,11 @@ class MeshLod(C.Structure):
                 ("view_stride_points", C.c_size_t), ("view_stride_faces", C.c_size_t), ("grid_width", C.c_int32), ("grid_height", C.c_int32)]
 
 
+class Voxels(C.Structure):
+    """sl3d_voxels: device addresses of the xyz, first and count arrays sl3d_voxel_grid left in HBM"""
+    _fields_ = [("xyz", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p)]
+
+
 class MeshHoles(C.Structure):
     """sl3d_mesh_holes: device addresses of the vertices, faces, original vertex ids (-1: filled) and (with SL3D_FILL_NORMALS, else
     None) normals sl3d_mesh_fill_holes left in HBM"""
@@ -204,6 +209,13 @@ _FILTER_PROTOTYPES = (
     ("sl3d_get_support", [_vp, _i, _vp, _sz]),
 )
 FILTER_SYMBOLS = tuple(row[0] for row in _FILTER_PROTOTYPES)
+# ... and for include/sl3d_voxel.h, the header of the voxel grid (tests/test_voxel_flag.py)
+_VOXEL_PROTOTYPES = (
+    ("sl3d_voxel_grid", [_vp, _vp, _i64, _f, _i64, _u, C.POINTER(Voxels), _p64]),
+    ("sl3d_get_voxel_grid", [_vp, _vp, _vp, _vp, _i64, _p64]),
+)
+VOXEL_SYMBOLS = tuple(row[0] for row in _VOXEL_PROTOTYPES)
+VOXEL_FIRST, VOXEL_CENTROID = 0, 1   # SL3D_VOXEL_FIRST, SL3D_VOXEL_CENTROID
 
 _lib = None
 
@@ -222,7 +234,7 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES:
+    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES:
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -256,7 +268,7 @@ def _ptrs(arrs):
     return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
 
 
-_XYZ, _RGB, _TRI, _IDS = (np.float32, 3), (np.uint8, 3), (np.int32, 3), (np.int32,)   # an output array: (dtype, *shape of one row)
+_XYZ, _RGB, _TRI, _IDS, _CNT = (np.float32, 3), (np.uint8, 3), (np.int32, 3), (np.int32,), (np.uint32,)   # an output array: (dtype, *shape of one row)
 
 
 class _Handle:
@@ -934,6 +946,25 @@ class Scanner(_Handle):
     def register_views(self, first_view, n_views, tx, ty, tz, rot_step):
         """register_point_clouds(): rotate view k by k*rot_step degrees about Y through (tx,ty,tz), concatenate."""
         return self._fill("sl3d_register_views", (first_view, n_views, tx, ty, tz, rot_step), _XYZ)[0]
+
+    def voxel_grid_device(self, leaf, min_points=1, centroid=True, cloud=None):
+        """sl3d_voxel_grid: one point per occupied cell of a grid of edge `leaf` over the registered cloud the last register_views /
+        register_clouds left on the device, or over `cloud` ((n, 3) float32 on the host), left in HBM; returns (Voxels, [points in, points
+        dropped, occupied cells, cells kept])."""
+        a = None if cloud is None else np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+        v, counts = Voxels(), (C.c_int64 * 4)()
+        self._chk(self.L.sl3d_voxel_grid(self._h, None if a is None else a.ctypes.data, 0 if a is None else len(a), leaf, int(min_points),
+                                         VOXEL_CENTROID if centroid else VOXEL_FIRST, C.byref(v), counts), "sl3d_voxel_grid")
+        return v, [int(c) for c in counts]
+
+    def voxel_grid(self, leaf, min_points=1, centroid=True, cloud=None, stats=False):
+        """The voxel grid of voxel_grid_device on the host: (xyz float32 (m, 3), first int32 (m,), count uint32 (m,)) of the cells that
+        hold at least min_points points, in order of first appearance -- xyz the cell's centroid (centroid=False: its first point), first
+        the index of its first point in the cloud (colours, normals, the source view are gathered through it), count its points (the rule:
+        include/sl3d_voxel.h).  stats=True appends [points in, points dropped, occupied cells, cells kept]."""
+        _, counts = self.voxel_grid_device(leaf, min_points, centroid, cloud)
+        out = tuple(self._fill("sl3d_get_voxel_grid", (), _XYZ, _IDS, _CNT))
+        return out + (counts,) if stats else out
 
     def pinned(self, shape, dtype):
         """numpy array in pinned host memory (sl3d_host_alloc); freed when the Scanner is closed."""
