@@ -64,7 +64,9 @@ try {
         return fail(x, SL3D_E_UNSUPPORTED, "triangulate: the integer solve needs both axes; a SL3D_FLAG_ONLY_VERTICAL / SL3D_FLAG_ONLY_HORIZONTAL context "
                                            "triangulates with sl3d_triangulate_subpixel");
     ON_DEVICE(x);
-    return launched(x, launch_tri(x->P, x->C, view, x->stream));
+    rc = launched(x, launch_tri(x->P, x->C, view, x->stream));
+    if (!rc) x->dense_ran = true;
+    return rc;
 }
 SL3D_CATCH(x)
 
@@ -151,8 +153,12 @@ static int run_k_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int 
 int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bool may_overlap)
 {
     const FusedRoute route = fused_route(x);
-    if (route == ROUTE_K_FUSED) return run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
     int rc;
+    if (route == ROUTE_K_FUSED) {
+        rc = run_k_fused(x, first_view, n_views, keep, cmode, may_overlap);
+        if (!rc && cmode == 0) x->dense_ran = true;
+        return rc;
+    }
     if (route != ROUTE_K_FUSED_THEN_STAGES) {  // (run_k_fused prepares the masks and counts its launch itself)
         if ((rc = flush_masks(x, first_view, n_views))) return rc;
         x->launches_on_stream++;  // (one per call, as the parity launch counts)
@@ -190,6 +196,7 @@ int run_fused(sl3d_ctx *x, int first_view, int n_views, bool keep, int cmode, bo
     }
     if (!rc && own_kernel(route)) x->own_kernel_ran = true;
     if (!rc && x->subpixel && x->one_axis < 0) x->residual_ready = true;
+    if (!rc && cmode == 0) x->dense_ran = true;
     return rc;
 }
 

@@ -30,6 +30,7 @@ try {
         int rc = launched(x, launch_subpixel_one(x->P, x->C, x->one_axis, first_view, n_views, counts ? x->d_subpixel_partials : nullptr, x->d_subpixel_counts,
                                                  x->anchor, x->stream));
         if (rc) return rc;
+        x->dense_ran = true;
         if (counts) {
             HIPCHK(x, hipMemcpyAsync(counts, x->d_subpixel_counts, 2 * (size_t)n_views * sizeof(unsigned), hipMemcpyDeviceToHost, x->stream));
             SYNC_FOR_CALLER(x);
@@ -51,7 +52,7 @@ try {
     unsigned *cnt = x->d_subpixel_counts;
     int rc = launched(x, launch_subpixel(x->P, x->C, first_view, n_views, max_residual, x->d_residual, counts ? x->d_subpixel_partials : nullptr, cnt, x->anchor, x->stream));
     if (rc) return rc;
-    x->residual_ready = true;
+    x->residual_ready = x->dense_ran = true;
     if (counts) {
         HIPCHK(x, hipMemcpyAsync(counts, cnt, 2 * (size_t)n_views * sizeof(unsigned), hipMemcpyDeviceToHost, x->stream));
         SYNC_FOR_CALLER(x);

@@ -196,6 +196,12 @@ struct sl3d_ctx {
     unsigned long long *d_vox_words = nullptr;
     size_t vox_cap[8] = {0};
     int64_t vox_n = -1, reg_total = -1;
+    // sl3d_align_sums / sl3d_refine_turntable (allocated on first use, freed by sl3d_destroy): [max_views - 1][ALIGN_WORDS] words, a pair's
+    // record, on the device, and the pinned block of the same size a pass's words are downloaded into.  dense_ran: a call that writes
+    // the dense planes (sl3d_run, sl3d_process_views, sl3d_triangulate, sl3d_triangulate_subpixel) has gone out -- the passes refuse before
+    unsigned long long *d_align_rec = nullptr;
+    long long *h_align_words = nullptr;
+    bool dense_ran = false;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

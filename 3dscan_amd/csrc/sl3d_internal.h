@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip -- the four before the last two share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip, sl3d_align.hip -- the four before the last three share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -16,6 +16,9 @@
 #define SL3D_ATAN_T1 511        // t1 = I0 - I2        in [-255, 255]
 #define SL3D_ATAN_T2 1021       // t2 = 2*I1 - I0 - I2 in [-510, 510]
 #define SL3D_SEG_POINTS 256     // pixels (point slots) per segment of the segmented clouds = one wave of the fused kernel
+
+struct AlignCam;   // sl3d_align.h
+struct AlignPass;
 
 namespace sl3d {
 
@@ -324,6 +327,11 @@ struct VoxelOut {
 // if a probe ran through the whole table (it cannot at this load factor)
 int launch_voxel_grid(const float *cloud, long long n, float leaf, long long min_points, bool centroid, const VoxelTable &T, unsigned *slot_of,
                       const CompactScratch &s, unsigned long long *words, const VoxelOut &out, void *stream);
+// one correspondence pass of the turntable refinement (sl3d_align.hip, sl3d_align.h; the rule: include/sl3d_align.h, sl3d_align_sums): pair j
+// is (source view first_view + j + 1, target view first_view + j), window 0 .. ALIGN_MAX_WINDOW; record: [n_pairs][ALIGN_WORDS] 64-bit words,
+// cleared on the stream by the launcher itself in front of k_align_pass
+int launch_align_pass(const KParams &P, int first_view, int n_pairs, int window, const ::AlignCam &cam, const ::AlignPass &a, unsigned long long *record,
+                      void *stream);
 // the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A row has
 // mesh_row_chunks(P) chunks (1024 pixels of one row), a view mesh_chunks(P) = H times as many; s: the mesh form of CompactScratch,
 // faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)

@@ -81,6 +81,17 @@ class Voxels(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p)]
 
 
+class Turntable(C.Structure):
+    """sl3d_turntable: what sl3d_refine_turntable leaves"""
+    _fields_ = [("tx", C.c_float), ("ty", C.c_float), ("tz", C.c_float), ("rot_step", C.c_float), ("est", C.c_double * 4), ("n", C.c_int64),
+                ("sources", C.c_int64), ("rms_xz", C.c_double), ("rms_y", C.c_double), ("degenerate", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AlignIteration(C.Structure):
+    """sl3d_align_iteration: one entry of sl3d_refine_turntable's log"""
+    _fields_ = [("est", C.c_double * 4), ("n", C.c_int64), ("sources", C.c_int64), ("rms_xz", C.c_double), ("rms_y", C.c_double)]
+
+
 class MeshHoles(C.Structure):
     """sl3d_mesh_holes: device addresses of the vertices, faces, original vertex ids (-1: filled) and (with SL3D_FILL_NORMALS, else
     None) normals sl3d_mesh_fill_holes left in HBM"""
@@ -217,6 +228,16 @@ _VOXEL_PROTOTYPES = (
 VOXEL_SYMBOLS = tuple(row[0] for row in _VOXEL_PROTOTYPES)
 VOXEL_FIRST, VOXEL_CENTROID = 0, 1   # SL3D_VOXEL_FIRST, SL3D_VOXEL_CENTROID
 
+# ... and for include/sl3d_align.h, the header of the turntable refinement (tests/test_align_flag.py)
+_ALIGN_PROTOTYPES = (
+    ("sl3d_align_sums", [_vp, _i, _i, _vp, _d, _d, _f, _f, _i, _vp]),
+    ("sl3d_align_solve", [_vp, _i, _f, _d, _d, _vp, _vp, _vp]),
+    ("sl3d_refine_turntable", [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, C.POINTER(Turntable), C.POINTER(AlignIteration), _pi]),
+    ("sl3d_get_align_camera", [_vp, _vp]),
+)
+ALIGN_SYMBOLS = tuple(row[0] for row in _ALIGN_PROTOTYPES)
+ALIGN_WORDS = 12                     # SL3D_ALIGN_WORDS
+
 _lib = None
 
 
@@ -234,7 +255,7 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES:
+    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES + _ALIGN_PROTOTYPES:
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -255,6 +276,18 @@ def pattern_counts(proj_extent, fringe_width):
     if rc != 0:
         raise Sl3dError("sl3d_pattern_counts: " + L.sl3d_strerror(rc).decode())
     return nc.value, npl.value
+
+
+def align_solve(sums, range, ox, oz, est):
+    """sl3d_align_solve: the closed-form solve over the (n_pairs, 12) int64 words of a pass (the rule: include/sl3d_align.h); host only, no
+    context.  est: (c, s, tx, tz).  Returns (the new estimate float64[4], dict(n, rms_xz, rms_y, degenerate))."""
+    L = load_library()
+    w = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, ALIGN_WORDS)
+    e, out, stats = np.ascontiguousarray(est, dtype=np.float64).reshape(4), np.empty(4), np.empty(4)
+    rc = L.sl3d_align_solve(w.ctypes.data, len(w), range, ox, oz, e.ctypes.data, out.ctypes.data, stats.ctypes.data)
+    if rc != 0:
+        raise Sl3dError("sl3d_align_solve: " + L.sl3d_strerror(rc).decode())
+    return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
 
 
 def _cut(flat, counts):
@@ -946,6 +979,36 @@ class Scanner(_Handle):
     def register_views(self, first_view, n_views, tx, ty, tz, rot_step):
         """register_point_clouds(): rotate view k by k*rot_step degrees about Y through (tx,ty,tz), concatenate."""
         return self._fill("sl3d_register_views", (first_view, n_views, tx, ty, tz, rot_step), _XYZ)[0]
+
+    def align_camera(self):
+        """sl3d_get_align_camera: float64[26] = Rc (9), tc (3), Kc (9), dc (5) exactly as a correspondence pass uses them."""
+        cam = np.empty(26)
+        self._chk(self.L.sl3d_get_align_camera(self._h, cam.ctypes.data), "sl3d_get_align_camera")
+        return cam
+
+    def align_sums(self, first_view, n_views, est, ox, oz, range, max_dist, window=2):
+        """sl3d_align_sums: one correspondence pass between the consecutive views first_view .. first_view + n_views - 1 (pair j: source
+        view first_view + j + 1, target first_view + j) at the estimate est = (c, s, tx, tz) -- cosine and sine of the step, the axis
+        point -- quantised about (ox, oz) (the rule: include/sl3d_align.h).  Returns the (n_views - 1, 12) int64 words."""
+        e = np.ascontiguousarray(est, dtype=np.float64).reshape(4)
+        out = np.zeros((max(n_views - 1, 1), ALIGN_WORDS), dtype=np.int64)
+        self._chk(self.L.sl3d_align_sums(self._h, first_view, n_views, e.ctypes.data, ox, oz, range, max_dist, window, out.ctypes.data), "sl3d_align_sums")
+        return out[:n_views - 1]
+
+    def refine_turntable(self, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window=2, iterations=20):
+        """sl3d_refine_turntable: the axis point and the step of register_views / register_clouds refined from the views' own overlap,
+        from the rough (tx, ty, tz, rot_step): up to `iterations` rounds of pass and solve.  Returns a dict: tx, ty, tz, rot_step (float32
+        values, ready for register_views), est (c, s, tx, tz in float64), n, sources, rms_xz, rms_y of the last pass, degenerate, n_done
+        and log -- per iteration made a dict(est, n, sources, rms_xz, rms_y) with the estimate its pass used."""
+        out, done = Turntable(), C.c_int(0)
+        log = (AlignIteration * max(iterations, 1))()
+        self._chk(self.L.sl3d_refine_turntable(self._h, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window, iterations, C.byref(out), log,
+                                               C.byref(done)), "sl3d_refine_turntable")
+        return dict(tx=np.float32(out.tx), ty=np.float32(out.ty), tz=np.float32(out.tz), rot_step=np.float32(out.rot_step),
+                    est=np.array(out.est[:], dtype=np.float64), n=int(out.n), sources=int(out.sources), rms_xz=float(out.rms_xz), rms_y=float(out.rms_y),
+                    degenerate=bool(out.degenerate), n_done=done.value,
+                    log=[dict(est=np.array(e.est[:], dtype=np.float64), n=int(e.n), sources=int(e.sources), rms_xz=float(e.rms_xz), rms_y=float(e.rms_y))
+                         for e in log[:done.value]])
 
     def voxel_grid_device(self, leaf, min_points=1, centroid=True, cloud=None):
         """sl3d_voxel_grid: one point per occupied cell of a grid of edge `leaf` over the registered cloud the last register_views /
