@@ -310,6 +310,7 @@ try {
     if (x->h_quad_part) (void)hipHostFree((void *)x->h_quad_part);
     if (x->h_mi_part) (void)hipHostFree((void *)x->h_mi_part);
     if (x->h_align_words) (void)hipHostFree(x->h_align_words);
+    if (x->h_align_plane_words) (void)hipHostFree(x->h_align_plane_words);
     for (hipEvent_t e : x->ev_up) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_done) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_down) (void)hipEventDestroy(e);

@@ -9,6 +9,8 @@
 //   sl3d_capi_filter.cpp   the radius outlier filter of the dense result (include/sl3d_filter.h: sl3d_filter_outliers, sl3d_get_support)
 //   sl3d_capi_voxel.cpp    the voxel grid over a cloud (include/sl3d_voxel.h: sl3d_voxel_grid, sl3d_get_voxel_grid)
 //   sl3d_capi_align.cpp    the turntable refinement (include/sl3d_align.h: sl3d_align_sums, sl3d_align_solve, sl3d_refine_turntable, sl3d_get_align_camera)
+//   sl3d_capi_align_plane.cpp  its point-to-plane form (include/sl3d_align_plane.h: sl3d_align_normals, sl3d_get_align_normals, sl3d_align_plane_sums,
+//                          sl3d_align_plane_solve, sl3d_refine_turntable_plane)
 #pragma once
 #include <hip/hip_runtime.h>
 

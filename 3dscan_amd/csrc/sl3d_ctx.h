@@ -202,6 +202,16 @@ struct sl3d_ctx {
     unsigned long long *d_align_rec = nullptr;
     long long *h_align_words = nullptr;
     bool dense_ran = false;
+    // sl3d_align_normals / sl3d_align_plane_sums / sl3d_refine_turntable_plane (include/sl3d_align_plane.h; first use, sl3d_destroy): the
+    // normal planes of the views [align_nrm_lo, align_nrm_hi) -- every view a call has asked for so far -- back to back, a view's laid out
+    // like its points ([px_view_stride][3] floats, rows pitch pixels apart); align_nrm_ready[view]: its normals have been computed since the
+    // block was last allocated.  The pairs' records of the point-to-plane pass ([max_views - 1][ALIGN_PLANE_WORDS]) and their pinned twin
+    float *d_align_nrm = nullptr;
+    size_t align_nrm_cap = 0;
+    int align_nrm_lo = 0, align_nrm_hi = 0;
+    std::vector<char> align_nrm_ready;
+    unsigned long long *d_align_plane_rec = nullptr;
+    long long *h_align_plane_words = nullptr;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

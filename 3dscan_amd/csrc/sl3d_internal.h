@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip, sl3d_align.hip -- the four before the last three share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip, sl3d_align.hip, sl3d_align_plane.hip -- the four before the last four share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -332,6 +332,13 @@ int launch_voxel_grid(const float *cloud, long long n, float leaf, long long min
 // cleared on the stream by the launcher itself in front of k_align_pass
 int launch_align_pass(const KParams &P, int first_view, int n_pairs, int window, const ::AlignCam &cam, const ::AlignPass &a, unsigned long long *record,
                       void *stream);
+// the point-to-plane form (sl3d_align_plane.hip, sl3d_align_plane.h; the rule: include/sl3d_align_plane.h).  k_align_normals over views
+// [first_view, first_view + n_views): normals is the plane of first_view, the views' planes 3 * px_view_stride floats apart and laid out
+// like points.  k_align_plane_pass: pairs as launch_align_pass, a.Q the scale of the lengths (align_plane_Q), normals the plane of the first target view, record: [n_pairs]
+// [ALIGN_PLANE_WORDS] words cleared on the stream by the launcher itself
+int launch_align_normals(const KParams &P, int first_view, int n_views, float normal_edge, float *normals, void *stream);
+int launch_align_plane_pass(const KParams &P, int first_view, int n_pairs, int window, const ::AlignCam &cam, const ::AlignPass &a,
+                            const float *normals, unsigned long long *record, void *stream);
 // the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A row has
 // mesh_row_chunks(P) chunks (1024 pixels of one row), a view mesh_chunks(P) = H times as many; s: the mesh form of CompactScratch,
 // faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)

@@ -238,6 +238,17 @@ _ALIGN_PROTOTYPES = (
 ALIGN_SYMBOLS = tuple(row[0] for row in _ALIGN_PROTOTYPES)
 ALIGN_WORDS = 12                     # SL3D_ALIGN_WORDS
 
+# ... and for include/sl3d_align_plane.h, the header of its point-to-plane form (tests/test_align_plane_flag.py)
+_ALIGN_PLANE_PROTOTYPES = (
+    ("sl3d_align_normals", [_vp, _i, _i, _f]),
+    ("sl3d_get_align_normals", [_vp, _i, _vp, _sz]),
+    ("sl3d_align_plane_sums", [_vp, _i, _i, _vp, _d, _d, _f, _f, _f, _i, _vp]),
+    ("sl3d_align_plane_solve", [_vp, _i, _f, _d, _d, _vp, _vp, _vp]),
+    ("sl3d_refine_turntable_plane", [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _i, C.POINTER(Turntable), C.POINTER(AlignIteration), _pi]),
+)
+ALIGN_PLANE_SYMBOLS = tuple(row[0] for row in _ALIGN_PLANE_PROTOTYPES)
+ALIGN_PLANE_WORDS = 18               # SL3D_ALIGN_PLANE_WORDS
+
 _lib = None
 
 
@@ -255,7 +266,7 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES + _ALIGN_PROTOTYPES:
+    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES + _ALIGN_PROTOTYPES + _ALIGN_PLANE_PROTOTYPES:
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -287,6 +298,19 @@ def align_solve(sums, range, ox, oz, est):
     rc = L.sl3d_align_solve(w.ctypes.data, len(w), range, ox, oz, e.ctypes.data, out.ctypes.data, stats.ctypes.data)
     if rc != 0:
         raise Sl3dError("sl3d_align_solve: " + L.sl3d_strerror(rc).decode())
+    return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
+
+
+def align_plane_solve(sums, range, ox, oz, est):
+    """sl3d_align_plane_solve: the Gauss-Newton solve over the (n_pairs, 18) int64 words of a point-to-plane pass (the rule:
+    include/sl3d_align_plane.h); host only, no context.  est: (c, s, tx, tz).  Returns (the new estimate float64[4], dict(n, rms_xz,
+    rms_y, degenerate)): rms_xz carries rms_plane, rms_y is NaN."""
+    L = load_library()
+    w = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, ALIGN_PLANE_WORDS)
+    e, out, stats = np.ascontiguousarray(est, dtype=np.float64).reshape(4), np.empty(4), np.empty(4)
+    rc = L.sl3d_align_plane_solve(w.ctypes.data, len(w), range, ox, oz, e.ctypes.data, out.ctypes.data, stats.ctypes.data)
+    if rc != 0:
+        raise Sl3dError("sl3d_align_plane_solve: " + L.sl3d_strerror(rc).decode())
     return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
 
 
@@ -1004,6 +1028,40 @@ class Scanner(_Handle):
         log = (AlignIteration * max(iterations, 1))()
         self._chk(self.L.sl3d_refine_turntable(self._h, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window, iterations, C.byref(out), log,
                                                C.byref(done)), "sl3d_refine_turntable")
+        return dict(tx=np.float32(out.tx), ty=np.float32(out.ty), tz=np.float32(out.tz), rot_step=np.float32(out.rot_step),
+                    est=np.array(out.est[:], dtype=np.float64), n=int(out.n), sources=int(out.sources), rms_xz=float(out.rms_xz), rms_y=float(out.rms_y),
+                    degenerate=bool(out.degenerate), n_done=done.value,
+                    log=[dict(est=np.array(e.est[:], dtype=np.float64), n=int(e.n), sources=int(e.sources), rms_xz=float(e.rms_xz), rms_y=float(e.rms_y))
+                         for e in log[:done.value]])
+
+    def align_normals(self, first_view, n_views, normal_edge):
+        """sl3d_align_normals: the dense normals of the views first_view .. first_view + n_views - 1 from each pixel's four neighbours
+        within normal_edge (the rule: include/sl3d_align_plane.h); asynchronous."""
+        self._chk(self.L.sl3d_align_normals(self._h, first_view, n_views, normal_edge), "sl3d_align_normals")
+
+    def align_normal_plane(self, view):
+        """sl3d_get_align_normals: (H, W, 3) float32, NaN where a pixel has no normal."""
+        out = np.empty((self.H, self.W, 3), dtype=np.float32)
+        self._chk(self.L.sl3d_get_align_normals(self._h, view, out.ctypes.data, out.strides[0]), "sl3d_get_align_normals")
+        return out
+
+    def align_plane_sums(self, first_view, n_views, est, ox, oz, range, max_dist, normal_edge, window=2):
+        """sl3d_align_plane_sums: the normals of the target views and one point-to-plane pass between the consecutive views (pairs and
+        estimate as align_sums).  Returns the (n_views - 1, 18) int64 words: accepted pairs, the upper triangle of the moments of the
+        five fixed-point features, sources, sources lost to a missing normal."""
+        e = np.ascontiguousarray(est, dtype=np.float64).reshape(4)
+        out = np.zeros((max(n_views - 1, 1), ALIGN_PLANE_WORDS), dtype=np.int64)
+        self._chk(self.L.sl3d_align_plane_sums(self._h, first_view, n_views, e.ctypes.data, ox, oz, range, max_dist, normal_edge, window,
+                                               out.ctypes.data), "sl3d_align_plane_sums")
+        return out[:n_views - 1]
+
+    def refine_turntable_plane(self, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, normal_edge, window=2, iterations=20):
+        """sl3d_refine_turntable_plane: refine_turntable with the point-to-plane error metric -- the residual along the target's surface
+        normal, normals from neighbours within normal_edge.  The dict of refine_turntable: rms_xz carries rms_plane, rms_y is NaN."""
+        out, done = Turntable(), C.c_int(0)
+        log = (AlignIteration * max(iterations, 1))()
+        self._chk(self.L.sl3d_refine_turntable_plane(self._h, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, normal_edge, window,
+                                                     iterations, C.byref(out), log, C.byref(done)), "sl3d_refine_turntable_plane")
         return dict(tx=np.float32(out.tx), ty=np.float32(out.ty), tz=np.float32(out.tz), rot_step=np.float32(out.rot_step),
                     est=np.array(out.est[:], dtype=np.float64), n=int(out.n), sources=int(out.sources), rms_xz=float(out.rms_xz), rms_y=float(out.rms_y),
                     degenerate=bool(out.degenerate), n_done=done.value,
