@@ -212,6 +212,23 @@ struct sl3d_ctx {
     std::vector<char> align_nrm_ready;
     unsigned long long *d_align_plane_rec = nullptr;
     long long *h_align_plane_words = nullptr;
+    // sl3d_tsdf_reset / sl3d_tsdf_integrate / sl3d_tsdf_extract (include/sl3d_tsdf.h; first use, grown on demand, sl3d_destroy): the two
+    // planes of the volume, the rotations and the depth planes of a call's views, the block scratch of an extraction (tsdf_s.tot is not used), its three
+    // outputs and the calls' words; tsdf_cap: the elements each growing array holds, in the order sl3d_capi_tsdf.cpp names them.  The
+    // volume as sl3d_tsdf_reset took it (tsdf_dims[0] == 0: no reset yet), the views integrated since, the crossings the last extraction
+    // left (-1: none since the last reset)
+    int32_t *d_tsdf_sum = nullptr;
+    uint32_t *d_tsdf_weight = nullptr;
+    double *d_tsdf_turns = nullptr;  // [max_views][2]: c_m, s_m
+    double *d_tsdf_depth = nullptr;  // the depth planes of a call's views: [n_views][px_view_stride]
+    CompactScratch tsdf_s{};
+    float *d_tsdf_xyz = nullptr, *d_tsdf_nrm = nullptr;
+    int32_t *d_tsdf_edge = nullptr;
+    unsigned long long *d_tsdf_words = nullptr;
+    size_t tsdf_cap[8] = {0};
+    float tsdf_origin[3] = {0.0f, 0.0f, 0.0f}, tsdf_voxel = 0.0f, tsdf_trunc = 0.0f;
+    int32_t tsdf_dims[3] = {0, 0, 0};
+    int64_t tsdf_views = 0, tsdf_m = -1;
     bool clouds_ready = false;                // ensure_cloud_buffers ran to its end: every pointer sl3d_run_clouds needs is set
     unsigned long long *h_counts = nullptr;   // pinned + mapped: the per-view counts k_seg_scan stores, sl3d_get_cloud_counts reads
     // a view's total out of those words (the device stores them: read once the stream has drained)

@@ -1,5 +1,5 @@
 // sl3d_internal.h -- structures shared by the C-ABI host code (sl3d_capi_*.cpp) and the HIP kernels (sl3d_fused_*.hip, sl3d_kernels.hip,
-// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip, sl3d_align.hip, sl3d_align_plane.hip -- the four before the last four share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
+// sl3d_clouds.hip, sl3d_modulation.hip, sl3d_mesh.hip, sl3d_mesh_normals.hip, sl3d_mesh_components.hip, sl3d_mesh_smooth.hip, sl3d_mesh_lod.hip, sl3d_mesh_holes.hip, sl3d_period.hip, sl3d_subpixel.hip, sl3d_subpixel_fused.hip, sl3d_repair_fused.hip, sl3d_one_axis.hip, sl3d_direct_gray.hip, sl3d_exposure.hip, sl3d_outlier.hip, sl3d_voxel.hip, sl3d_align.hip, sl3d_align_plane.hip, sl3d_tsdf.hip -- the four before the last five share sl3d_quad.h, what a quad-per-lane kernel is made of).  Not part of
 // the public ABI.  What the consumers of a dense result share on the HOST side is here (CompactScratch, compact_blocks, view_planes,
 // mesh_launch, mesh_face_stride, CcTotals); the block idioms of their kernels are in sl3d_block.h, a mesh lane's loads in sl3d_mesh_lane.h.
 #pragma once
@@ -19,6 +19,9 @@
 
 struct AlignCam;   // sl3d_align.h
 struct AlignPass;
+struct TsdfVolume;  // sl3d_tsdf.h
+struct TsdfTurn;
+struct TsdfPlanes;
 
 namespace sl3d {
 
@@ -339,6 +342,17 @@ int launch_align_pass(const KParams &P, int first_view, int n_pairs, int window,
 int launch_align_normals(const KParams &P, int first_view, int n_views, float normal_edge, float *normals, void *stream);
 int launch_align_plane_pass(const KParams &P, int first_view, int n_pairs, int window, const ::AlignCam &cam, const ::AlignPass &a,
                             const float *normals, unsigned long long *record, void *stream);
+// the TSDF volume (sl3d_tsdf.hip, sl3d_tsdf.h; the rule: include/sl3d_tsdf.h).  launch_tsdf_integrate: views [first_view, first_view +
+// n_views) into the planes sum / weight of vol; turns: [n_views] rotations on the device; depth: n_views * px_view_stride doubles, the
+// views' depth planes (k_tsdf_depth fills them first); words: TSDF_WORDS 64-bit words, the two of an
+// integration cleared on the stream by the launcher itself.  launch_tsdf_count: k_tsdf_count and k_compact_scan over s.cnt / s.off (a
+// slot per 1024 voxels), the two words of an extraction cleared likewise; launch_tsdf_scatter: the crossings into arrays of at least
+// words[TSDF_WORD_CROSSINGS] rows
+int launch_tsdf_integrate(const KParams &P, int first_view, int n_views, const ::AlignCam &cam, const ::TsdfVolume &vol, double tx, double tz,
+                          const ::TsdfTurn *turns, double *depth, int32_t *sum, uint32_t *weight, unsigned long long *words, void *stream);
+int launch_tsdf_count(const ::TsdfPlanes &planes, const ::TsdfVolume &vol, const CompactScratch &s, unsigned long long *words, void *stream);
+int launch_tsdf_scatter(const ::TsdfPlanes &planes, const ::TsdfVolume &vol, const CompactScratch &s, float *xyz, float *normals, int32_t *edge,
+                        void *stream);
 // the mesh stage (sl3d_mesh.hip, sl3d_mesh.h): the faces of views [first_view, first_view + n_views) over their dense result.  A row has
 // mesh_row_chunks(P) chunks (1024 pixels of one row), a view mesh_chunks(P) = H times as many; s: the mesh form of CompactScratch,
 // faces: [max_views][face_stride][3] vertex ids into the view's compacted cloud (launch_compact_views)

@@ -81,6 +81,16 @@ class Voxels(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("first", C.c_void_p), ("count", C.c_void_p)]
 
 
+class TsdfVolume(C.Structure):
+    """sl3d_tsdf_volume: the origin, the voxel edge, the truncation distance and the dims (nx, ny, nz) of a TSDF volume"""
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float), ("dims", C.c_int32 * 3)]
+
+
+class TsdfSurface(C.Structure):
+    """sl3d_tsdf_surface: device addresses of the xyz, normals and edge arrays sl3d_tsdf_extract left in HBM"""
+    _fields_ = [("xyz", C.c_void_p), ("normals", C.c_void_p), ("edge", C.c_void_p)]
+
+
 class Turntable(C.Structure):
     """sl3d_turntable: what sl3d_refine_turntable leaves"""
     _fields_ = [("tx", C.c_float), ("ty", C.c_float), ("tz", C.c_float), ("rot_step", C.c_float), ("est", C.c_double * 4), ("n", C.c_int64),
@@ -249,6 +259,16 @@ _ALIGN_PLANE_PROTOTYPES = (
 ALIGN_PLANE_SYMBOLS = tuple(row[0] for row in _ALIGN_PLANE_PROTOTYPES)
 ALIGN_PLANE_WORDS = 18               # SL3D_ALIGN_PLANE_WORDS
 
+# ... and for include/sl3d_tsdf.h, the header of the TSDF volume (tests/test_tsdf_flag.py)
+_TSDF_PROTOTYPES = (
+    ("sl3d_tsdf_reset", [_vp, C.POINTER(TsdfVolume)]),
+    ("sl3d_tsdf_integrate", [_vp, _i, _i, _i, _vp, _p64]),
+    ("sl3d_tsdf_extract", [_vp, _i64, C.POINTER(TsdfSurface), _p64]),
+    ("sl3d_get_tsdf", [_vp, _vp, _vp, _i64, _p64]),
+    ("sl3d_get_tsdf_surface", [_vp, _vp, _vp, _vp, _i64, _p64]),
+)
+TSDF_SYMBOLS = tuple(row[0] for row in _TSDF_PROTOTYPES)
+
 _lib = None
 
 
@@ -266,7 +286,7 @@ def load_library(path=None):
         raise Sl3dError(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                         "or `make -C 3dscan_amd/csrc` (there is no CPU fallback)")
     L = C.CDLL(p)
-    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES + _ALIGN_PROTOTYPES + _ALIGN_PLANE_PROTOTYPES:
+    for name, argtypes, *restype in _PROTOTYPES + _FUSE_PROTOTYPES + _FILTER_PROTOTYPES + _VOXEL_PROTOTYPES + _ALIGN_PROTOTYPES + _ALIGN_PLANE_PROTOTYPES + _TSDF_PROTOTYPES:
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -312,6 +332,20 @@ def align_plane_solve(sums, range, ox, oz, est):
     if rc != 0:
         raise Sl3dError("sl3d_align_plane_solve: " + L.sl3d_strerror(rc).decode())
     return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
+
+
+def tsdf_bounds(cloud, voxel, margin=2):
+    """(origin float32[3], dims (nx, ny, nz)) of the TSDF volume of edge `voxel` around a registered cloud ((n, 3), points that are not
+    finite ignored) with `margin` voxels of room on every side: what Scanner.tsdf_reset takes."""
+    p = np.asarray(cloud, dtype=np.float64).reshape(-1, 3)
+    p = p[np.isfinite(p).all(axis=1)]
+    if not len(p):
+        raise Sl3dError("tsdf_bounds: the cloud has no finite point")
+    L = float(np.float32(voxel))
+    origin = (np.floor(p.min(axis=0) / L) - margin).astype(np.float64) * L
+    origin = origin.astype(np.float32)
+    dims = np.ceil((p.max(axis=0) - origin.astype(np.float64)) / L).astype(np.int64) + margin
+    return origin, tuple(int(max(d, 1)) for d in dims)
 
 
 def _cut(flat, counts):
@@ -1086,6 +1120,42 @@ class Scanner(_Handle):
         _, counts = self.voxel_grid_device(leaf, min_points, centroid, cloud)
         out = tuple(self._fill("sl3d_get_voxel_grid", (), _XYZ, _IDS, _CNT))
         return out + (counts,) if stats else out
+
+    def tsdf_reset(self, origin, voxel, trunc, dims):
+        """sl3d_tsdf_reset: defines the TSDF volume -- origin (3 floats), the voxel edge, the truncation distance, dims (nx, ny, nz) -- and
+        clears it (the rule: include/sl3d_tsdf.h); asynchronous."""
+        v = TsdfVolume((C.c_float * 3)(*[float(o) for o in origin]), voxel, trunc, (C.c_int32 * 3)(*[int(d) for d in dims]))
+        self._chk(self.L.sl3d_tsdf_reset(self._h, C.byref(v)), "sl3d_tsdf_reset")
+        self._tsdf_dims = tuple(int(d) for d in dims)
+
+    def tsdf_integrate(self, first_view, n_views, est, first_step=0):
+        """sl3d_tsdf_integrate: the views first_view .. first_view + n_views - 1 of the dense result, the turntable indices first_step ..,
+        voted into the volume at the estimate est = (c, s, tx, tz) (refine_turntable's "est").  Returns [samples taken, voxels with
+        weight > 0]."""
+        e = np.ascontiguousarray(est, dtype=np.float64).reshape(4)
+        counts = (C.c_int64 * 2)()
+        self._chk(self.L.sl3d_tsdf_integrate(self._h, first_view, n_views, first_step, e.ctypes.data, counts), "sl3d_tsdf_integrate")
+        return [int(c) for c in counts]
+
+    def tsdf_extract_device(self, min_weight=1):
+        """sl3d_tsdf_extract: the oriented points of the zero level over the voxels of weight >= min_weight, left in HBM; returns
+        (TsdfSurface, [voxels, known voxels, crossings])."""
+        out, counts = TsdfSurface(), (C.c_int64 * 3)()
+        self._chk(self.L.sl3d_tsdf_extract(self._h, int(min_weight), C.byref(out), counts), "sl3d_tsdf_extract")
+        return out, [int(c) for c in counts]
+
+    def tsdf_extract(self, min_weight=1, stats=False):
+        """The surface of tsdf_extract_device on the host: (xyz float32 (m, 3), normals float32 (m, 3), edge int32 (m,)), edge = 3 * v0 +
+        axis of the crossing's edge -- weights are gathered through it.  stats=True appends [voxels, known voxels, crossings]."""
+        _, counts = self.tsdf_extract_device(min_weight)
+        out = tuple(self._fill("sl3d_get_tsdf_surface", (), _XYZ, _XYZ, _IDS))
+        return out + (counts,) if stats else out
+
+    def tsdf_volume(self):
+        """sl3d_get_tsdf: (sum int32, weight uint32), each shaped (nz, ny, nx)."""
+        s, w = self._fill("sl3d_get_tsdf", (), (np.int32,), (np.uint32,))
+        nx, ny, nz = self._tsdf_dims
+        return s.reshape(nz, ny, nx), w.reshape(nz, ny, nx)
 
     def pinned(self, shape, dtype):
         """numpy array in pinned host memory (sl3d_host_alloc); freed when the Scanner is closed."""

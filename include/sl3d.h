@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SL3D_VERSION_STRING "0.25.0"
+#define SL3D_VERSION_STRING "0.26.0"
 
 typedef struct sl3d_ctx sl3d_ctx;
 
@@ -386,6 +386,10 @@ int sl3d_copy_view(sl3d_ctx *ctx, int src_view, int dst_view);
 /* (0.25.0) The same refinement with the point-to-plane error metric -- the residual measured along the target's surface normal, which
  * removes the bias of the point-to-point form -- has a header of its own, include/sl3d_align_plane.h: dense normals of a view, the rule of
  * the pass, the solve and the five calls. */
+
+/* (0.26.0) The views of a turntable scan fused into one oriented surface -- every view votes with a truncated signed distance into a
+ * regular voxel volume on the device, the surface is the zero level of the averaged votes -- has a header of its own,
+ * include/sl3d_tsdf.h: the rule of an integration, the rule of the extraction and the five calls. */
 
 /* Synthetic capture generated on the device into view slot `view` (inputs for tests and benchmarks; the pattern
  * formulas are the reference generator's, 1/pattern_generator.cpp:80-105,302,313,497, Pi = 22/7): plane[3] = z0,a,b of

@@ -1,0 +1,266 @@
+"""The inputs of the TSDF tests (tests/test_tsdf_arith.py on the CPU, tests/test_gpu_tsdf_cases.py and tests/test_gpu_tsdf_extract.py on the
+device): crafted turntable views on a 48 x 36 window at (37, 5) of a 320 x 240 frame with volumes of the shapes the kernels can go wrong
+at, and planes crafted pixel by pixel for an exact camera, in which one voxel meets one special case of the rule (include/sl3d_tsdf.h).
+
+The exact camera: Rc = I, tc = 0, no distortion, Kc = (64, 0, 45; 0, 64, 11; 0, 0, 1) -- the principal point is window pixel (8, 6).  With
+the identity estimate a voxel centre X at depth 64 projects to u = X.x + 45, v = X.y + 11 without a rounding, and the camera depth of a
+pixel's point q is q.z itself: a test sets u, v, every depth and with them sdf to the bit."""
+import numpy as np
+
+import align_reference as AR
+
+F8 = np.float64
+FULL, ORIGIN = (320, 240), (37, 5)
+FRAME = (48, 36)                                                            # (W, H) of the window
+SHAPES = [(5, 3, 2), (64, 1, 1), (65, 3, 2), (33, 9, 7), (70, 33, 5)]        # (nx, ny, nz)
+IDENTITY = np.array([1.0, 0.0, 0.0, 0.0])
+
+EXACT = dict(W=40, H=24, Kc=(64.0, 0.0, 45.0, 0.0, 64.0, 11.0, 0.0, 0.0, 1.0), dc=(0.0,) * 5, rc=(0.0,) * 3, tc=(0.0,) * 3, depth=64.0,
+             trunc=np.float32(32767.0 / 16384.0))                           # T = 32767 * 2^-14: sdf = (2k + 1) * 2^-15 lands d * 32767 on k + 0.5
+PX, PY = 8, 6                                                               # the principal point in window coordinates
+
+
+def rig_calibration():
+    import importlib
+    syn = importlib.import_module("3dscan_amd.synth")
+    return syn.cal_tuple(syn.synth_rig(FULL[0], FULL[1], 2048, 2048))
+
+
+def exact_calibration():
+    """the rig's calibration with the exact camera in place of the rig's"""
+    cal = list(rig_calibration())
+    cal[0:4] = [np.array(EXACT[k], F8) for k in ("Kc", "dc", "rc", "tc")]
+    return tuple(cal)
+
+
+def camera(cal):
+    return AR.camera_of(*cal[:4])
+
+
+# ---- crafted turntable views and a volume of a given shape around them ----------------------------------------------------------------------
+def shape_case(cam, dims, V, seed):
+    """V views (align_reference.crafted_views: noise, outliers that trip the depth guard, one pixel in nine invalid) and a volume of
+    `dims` about the point under the window's centre at depth 100 mm; voxel so that the volume spans about 15 mm, trunc three voxels.
+    Returns points, valid, est, pads, vol."""
+    W, H = FRAME
+    points, valid, est, pads = AR.crafted_views(cam, W, H, ORIGIN[0], ORIGIN[1], V, seed)
+    centre = AR.backproject(cam, 1, 1, ORIGIN[0] + W // 2, ORIGIN[1] + H // 2, 100.0)[0, 0]
+    L = np.float32(15.0 / max(dims[0], 1.4 * dims[1], 3.0 * dims[2]))
+    origin = (centre - 0.5 * float(L) * np.array(dims, F8)).astype(np.float32)
+    return points, valid, est, pads, dict(origin=origin, voxel=L, trunc=np.float32(3.0) * L, dims=tuple(dims))
+
+
+# ---- one voxel, one special case ---------------------------------------------------------------------------------------------------------------
+def one_voxel(c, r, a=0.0, b=0.0, z=None):
+    """the volume of one voxel (voxel 1 mm) whose centre projects to window pixel (c + a, r + b) of the exact camera at depth z"""
+    z = EXACT["depth"] if z is None else z
+    s = z / EXACT["depth"]                                                  # (x / z must stay what it is at depth 64)
+    X = np.array([(c - PX + a) * s, (r - PY + b) * s, z], F8)
+    origin = (X - 0.5).astype(np.float32)
+    assert np.array_equal(origin.astype(F8), X - 0.5)
+    return dict(origin=origin, voxel=np.float32(1.0), trunc=EXACT["trunc"], dims=(1, 1, 1))
+
+
+def special_cases():
+    """One view for the exact camera and the cases: (name, vol, weight expected, q expected or None).  Every pixel is valid at depth 70
+    (a clamped sample) but for what a case changes in the quad of its own; pad: the point of the padding columns, a perfect depth under
+    a valid byte, which only a kernel that reads past the window's last column takes."""
+    W, H, D = EXACT["W"], EXACT["H"], EXACT["depth"]
+    T32 = EXACT["trunc"]
+    T = float(T32)
+    f = np.float32
+    xyz = np.zeros((H, W, 3), np.float32)
+    xyz[..., 0], xyz[..., 1], xyz[..., 2] = 3.0, -2.0, 70.0                 # (x and y of a pixel's point do not enter its depth)
+    valid = np.ones((H, W), np.uint8)
+    cases = []
+    slot = [0]
+
+    def quad(depths=(64.5,) * 4):
+        """the next free quad: its upper left pixel; depths = z00, z10, z01, z11"""
+        k = slot[0]
+        slot[0] += 1
+        c, r = 2 + 4 * (k % 9), 1 + 3 * (k // 9)
+        assert c + 1 < W - 2 and r + 1 < H - 2
+        for (dx, dy), z in zip(((0, 0), (1, 0), (0, 1), (1, 1)), depths):
+            xyz[r + dy, c + dx, 2] = z
+        return c, r
+
+    def case(name, vol, weight, q=None):
+        cases.append((name, vol, weight, q))
+    c, r = quad()
+    case("plain", one_voxel(c, r, 0.25, 0.75), 1)
+    case("behind the camera", one_voxel(c, r, 0.25, 0.75, z=-64.0), 0)
+    case("in the camera's plane", one_voxel(c, r, z=0.0), 0)
+    # the last usable column and row (fu + 1 < W, fv + 1 < H), one past them, the first ones and one before
+    case("last column", one_voxel(W - 2, 10, 0.5, 0.5), 1, 32767)
+    case("past the last column", one_voxel(W - 1, 10, 0.5, 0.5), 0)
+    case("last row", one_voxel(20, H - 2, 0.5, 0.5), 1, 32767)
+    case("past the last row", one_voxel(20, H - 1, 0.5, 0.5), 0)
+    case("first column and row", one_voxel(0, 0), 1, 32767)
+    case("before the first column", one_voxel(-1, 10, 0.5, 0.5), 0)
+    case("before the first row", one_voxel(20, -1, 0.5, 0.5), 0)
+    case("far outside", one_voxel(5000, -7000, 0.5, 0.5), 0)
+    for k, (dx, dy) in enumerate(((0, 0), (1, 0), (0, 1), (1, 1))):
+        c, r = quad()
+        valid[r + dy, c + dx] = 0
+        case(f"pixel {dx}{dy} invalid", one_voxel(c, r, 0.5, 0.5), 0)
+    for k, (comp, odd) in enumerate(((0, np.nan), (1, np.inf), (2, np.nan), (2, -np.inf))):
+        c, r = quad()
+        dx, dy = ((0, 0), (1, 0), (0, 1), (1, 1))[k]
+        xyz[r + dy, c + dx, comp] = odd
+        case(f"pixel {dx}{dy} not finite in {'xyz'[comp]}", one_voxel(c, r, 0.5, 0.5), 0)
+    # a depth spread of exactly T and the float above it
+    above = np.nextafter(f(66.0) + T32, f(np.inf))
+    assert float(f(66.0) + T32) - 66.0 == T and float(above) - 66.0 > T
+    c, r = quad((66.0, f(66.0) + T32, 66.0, 66.0))
+    case("depth spread exactly T", one_voxel(c, r, 0.5, 0.5), 1)
+    c, r = quad((66.0, 66.0, above, 66.0))
+    case("depth spread above T", one_voxel(c, r, 0.5, 0.5), 0)
+    # sdf exactly -T and the float below it; a = b = 0 makes zq = z00 without a rounding
+    at = f(D) - T32
+    assert float(at) - D == -T
+    c, r = quad((at,) * 4)
+    case("sdf exactly -T", one_voxel(c, r), 1, -32767)
+    c, r = quad((np.nextafter(at, f(0.0)), at, at, at))
+    case("sdf below -T", one_voxel(c, r), 0)
+    c, r = quad((100.0,) * 4)
+    case("d clamped at 1", one_voxel(c, r, 0.5, 0.25), 1, 32767)
+    c, r = quad((f(D) + T32,) * 4)
+    case("d exactly 1", one_voxel(c, r), 1, 32767)
+    c, r = quad((D,) * 4)
+    case("sdf exactly 0", one_voxel(c, r, 0.5, 0.5), 1, 0)
+    # d * 32767 on k + 0.5: ties go to the even neighbour
+    for k in (1000, 1001, -1000, -1001):
+        z = f(D + (2 * k + 1) / 32768.0)
+        assert float(z) - D == (2 * k + 1) / 32768.0
+        c, r = quad((z,) * 4)
+        case(f"tie at {k} + 0.5", one_voxel(c, r), 1, 2 * round((k + 0.5) / 2.0))
+    pad = np.zeros((H, 3), np.float32)
+    pad[:, 2] = 64.5
+    return xyz, valid, pad, cases
+
+
+# ---- planes whose integration leaves a chosen volume (the exact camera, the identity estimate) ------------------------------------------------
+def slab_case(values):
+    """A volume (nx, ny, 1) one voxel thick at depth 64, voxel 2 mm, whose voxel (i, j) sits exactly on window pixel (2 + 2 i, 3 + 2 j), so
+    that the quads of the voxels are disjoint: integrating the returned view once leaves sum = rint(clamp(values[j][i]) * 32767) and weight
+    1 there; a value of None leaves the quad invalid (the voxel takes no sample).  values: rows j of columns i, d itself (in units of T), a
+    multiple of 2^-10."""
+    W, H, D, T = EXACT["W"], EXACT["H"], EXACT["depth"], float(EXACT["trunc"])
+    ny, nx = len(values), len(values[0])
+    xyz = np.zeros((H, W, 3), np.float32)
+    xyz[..., 2] = 70.0
+    valid = np.zeros((H, W), np.uint8)
+    c0, r0 = 2, 3
+    assert c0 + 2 * nx <= W and r0 + 2 * ny <= H
+    for j in range(ny):
+        for i in range(nx):
+            if values[j][i] is None:
+                continue
+            z = np.float32(D + values[j][i] * T)
+            assert float(z) == D + values[j][i] * T                          # (d * T: at most 10 + 15 bits)
+            r, c = r0 + 2 * j, c0 + 2 * i
+            xyz[r:r + 2, c:c + 2, 2] = z                                     # (a = b = 0: zq = z00; the other three pass the depth guard)
+            valid[r:r + 2, c:c + 2] = 1
+    X = np.array([c0 - PX, r0 - PY, D], F8)
+    vol = dict(origin=(X - 1.0).astype(np.float32), voxel=np.float32(2.0), trunc=EXACT["trunc"], dims=(nx, ny, 1))
+    return xyz, valid, vol
+
+
+def column_case(nz, depth_of_surface):
+    """A volume (1, 1, nz) along the optical axis, voxel 1 mm, first centre at depth 60: every voxel projects to the principal point, and
+    sdf falls by one millimetre a voxel -- one crossing along axis 2 where it passes zero."""
+    W, H = EXACT["W"], EXACT["H"]
+    xyz = np.zeros((H, W, 3), np.float32)
+    xyz[..., 2] = np.float32(depth_of_surface)
+    valid = np.ones((H, W), np.uint8)
+    vol = dict(origin=np.array([-0.5, -0.5, 59.5], np.float32), voxel=np.float32(1.0), trunc=EXACT["trunc"], dims=(1, 1, nz))
+    return xyz, valid, vol
+
+
+# ---- the ray-cast turntable scene fused with the true estimate (tests/test_tsdf_quality_reference.py, tests/test_gpu_tsdf_scene.py) -------------
+SCENE = dict(voxel=np.float32(1.0), trunc=np.float32(3.0), min_weight=1, margin=2, sigma=0.3, seed=20260)
+
+
+def scene_shapes(cam):
+    """the two ellipsoids of align_reference.raycast_scene, (centre, semi-axes), in the frame of view 0"""
+    body = AR.to_world(cam, np.array([0.0, 0.0, 125.0]))
+    return [(body, np.array([24.0, 30.0, 17.0])), (body + np.array([31.0, 8.0, -6.0]), np.array([9.0, 9.0, 9.0]))]
+
+
+def surface_distance(cam, P):
+    """the distance of the points P (n, 3) to the nearer of the two true surfaces, to first order: |F| / |grad F| of F = sum ((x - c) / s)^2 - 1"""
+    P = np.asarray(P, F8)
+    d = []
+    for c, s in scene_shapes(cam):
+        e = (P - c) / s
+        d.append(np.abs((e * e).sum(axis=1) - 1.0) / np.linalg.norm(2.0 * e / s, axis=1))
+    return np.minimum(*d)
+
+
+def registered(points, valid, truth):
+    """the valid points of the views turned into the frame of view 0 by the estimate, concatenated: (n, 3) float64"""
+    out = []
+    for k in range(len(points)):
+        p = points[k][valid[k] == 1].astype(F8)
+        for _ in range(k):
+            p = AR.turn(p, truth)
+        out.append(p)
+    return np.concatenate(out)
+
+
+def scene(sigma=0.0, cam=None):
+    """cam, points, valid, truth of the ray-cast scene; sigma > 0: Gaussian depth noise along each pixel's ray, a fixed seed.  cam: the
+    camera to cast through (the device's own 26 doubles), by default the scene calibration's as NumPy derives it"""
+    if cam is None:
+        cal = AR.scene_calibration()
+        cam = AR.camera_of(cal[0], cal[1], cal[2], cal[3])
+    points, valid, truth = AR.raycast_scene(cam)
+    if sigma > 0.0:
+        rng = np.random.default_rng(SCENE["seed"])
+        o = AR.to_world(cam, np.zeros(3))
+        ray = points.astype(F8) - o
+        ray /= np.linalg.norm(ray, axis=-1, keepdims=True)
+        noisy = points.astype(F8) + rng.normal(0.0, sigma, valid.shape)[..., None] * ray
+        points = np.where((valid == 1)[..., None], noisy, np.nan).astype(np.float32)
+    return cam, points, valid, truth
+
+
+def scene_volume(cloud):
+    import tsdf_reference as TR
+    origin, dims = TR.bounds(cloud, SCENE["voxel"], SCENE["margin"])
+    return dict(origin=origin, voxel=SCENE["voxel"], trunc=SCENE["trunc"], dims=dims)
+
+
+def coverage(cloud, crossings, radius):
+    """the share of the cloud's points that have a crossing within `radius`"""
+    hit = np.zeros(len(cloud), bool)
+    c = np.asarray(crossings, F8)
+    for lo in range(0, len(cloud), 512):
+        d2 = ((cloud[lo:lo + 512, None, :] - c[None, :, :]) ** 2).sum(axis=2)
+        hit[lo:lo + 512] = d2.min(axis=1) <= radius * radius
+    return float(hit.mean())
+
+
+_FUSED = {}
+
+
+def fused_scene(sigma=0.0, cam=None):
+    """The scene fused by the restatement, computed once a process and camera: dict(cam, points, valid, truth, cloud, vol, sum, weight,
+    counts, xyz, normals, edge, stats)"""
+    key = sigma if cam is None else (sigma, np.asarray(cam, F8).tobytes())
+    if cam is not None and sigma in _FUSED and np.array_equal(_FUSED[sigma]["cam"], cam):
+        key = sigma
+    if key not in _FUSED:
+        import tsdf_reference as TR
+        cam, points, valid, truth = scene(sigma, cam)
+        cloud = registered(points, valid, truth)
+        vol = scene_volume(cloud)
+        s, w = TR.new_volume(vol)
+        counts = TR.integrate(s, w, vol, points, valid, cam, 0, 0, truth)
+        xyz, nrm, edge, stats = TR.extract(s, w, vol, SCENE["min_weight"])
+        for a in (points, valid, s, w, xyz, nrm, edge):
+            a.setflags(write=False)
+        _FUSED[key] = dict(cam=cam, points=points, valid=valid, truth=truth, cloud=cloud, vol=vol, sum=s, weight=w, counts=counts, xyz=xyz,
+                             normals=nrm, edge=edge, stats=stats)
+    return _FUSED[key]
