@@ -11,7 +11,7 @@
 //   xc[i]    = ((Rc[3i] * p^.x + Rc[3i+1] * p^.y) + Rc[3i+2] * p^.z) + tc[i]; no candidate unless xc.z > 0 and finite
 //   xn, yn   = xc.x / xc.z, xc.y / xc.z;  r2 = xn * xn + yn * yn;  rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
 //   xd       = xn * rad + (2 * p1 * xn * yn + p2 * (r2 + 2 * xn * xn));  yd = yn * rad + (p1 * (r2 + 2 * yn * yn) + 2 * p2 * xn * yn)
-//   u, v, w  = (K[3i] * xd + K[3i+1] * yd) + K[3i+2];  u / w, v / w
+//   u, v, w  = (K[3i] * xd + K[3i+1] * yd) + K[3i+2];  u / w, v / w                                                         (align_project)
 //   cc, rr   = rint(u) - col0, rint(v) - row0 (ties to even): a centre iff both are finite and below 2^30 in magnitude      (align_centre)
 //   d2       = (ex * ex + ey * ey) + ez * ez, e = (double)q - p^                                                            (align_d2)
 //   quantised coordinate of w about o: e = ((double)w - o) * Q, in range iff |e| < 2^18, its integer (int64)rint(e)         (align_quant)
@@ -45,7 +45,8 @@ SL3D_MESH_FN double align_thr2(float max_dist) { return (double)max_dist * (doub
 // is p a source / a candidate's point: three finite coordinates
 SL3D_MESH_FN int align_finite(const float *p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
-// step 1: the source point turned once by the step about the axis
+// step 1: the source point turned once by the step about the axis.  (tsdf_step, sl3d_tsdf.h, is this text over a double point: routed
+// through one form the pass kernels' instructions come out in another order, so a change here goes there too)
 SL3D_MESH_FN void align_step(const float *p, const struct AlignPass *a, double *ph)
 {
     const double x = (double)p[0] - a->tx, z = (double)p[2] - a->tz;
@@ -54,8 +55,8 @@ SL3D_MESH_FN void align_step(const float *p, const struct AlignPass *a, double *
     ph[2] = (a->s * x + a->c * z) + a->tz;
 }
 
-// steps 2 and 3: the centre pixel (window coordinates, as doubles that hold integers) of ph's search window; 0: no candidate
-SL3D_MESH_FN int align_centre(const double *ph, const struct AlignCam *m, int col0, int row0, double *cc, double *rr)
+// step 2: ph into the camera: *pu, *pv the pixel it projects to, unrounded, *zc = xc.z.  0: nothing (xc.z <= 0 or not finite)
+SL3D_MESH_FN int align_project(const double *ph, const struct AlignCam *m, double *pu, double *pv, double *zc)
 {
     double xc[3];
     for (int i = 0; i < 3; i++) xc[i] = ((m->Rc[3 * i] * ph[0] + m->Rc[3 * i + 1] * ph[1]) + m->Rc[3 * i + 2] * ph[2]) + m->tc[i];
@@ -69,6 +70,15 @@ SL3D_MESH_FN int align_centre(const double *ph, const struct AlignCam *m, int co
     const double *K = m->Kc;
     const double w = (K[6] * xd + K[7] * yd) + K[8];
     const double u = ((K[0] * xd + K[1] * yd) + K[2]) / w, v = ((K[3] * xd + K[4] * yd) + K[5]) / w;
+    *pu = u, *pv = v, *zc = xc[2];
+    return 1;
+}
+
+// steps 2 and 3: the centre pixel (window coordinates, as doubles that hold integers) of ph's search window; 0: no candidate
+SL3D_MESH_FN int align_centre(const double *ph, const struct AlignCam *m, int col0, int row0, double *cc, double *rr)
+{
+    double u, v, zc;
+    if (!align_project(ph, m, &u, &v, &zc)) return 0;
     *cc = rint(u) - (double)col0;
     *rr = rint(v) - (double)row0;
     return fabs(*cc) < ALIGN_PIXEL_LIMIT && fabs(*rr) < ALIGN_PIXEL_LIMIT;  // false for NaN and the infinities

@@ -15,23 +15,13 @@
 // shuffles, the four waves through LDS, then one 64-bit integer atomicAdd per non-zero word and block into the record the host cleared
 // on the stream.  Integer atomics only: the result does not depend on the order of arrival.  Every loop has a compile-time bound.
 // Compiled with -ffp-contract=off.
+// The tile walk, the search, the tail behind the waves' words and the dispatch over the window are sl3d_align_lane.h's, shared by the two forms.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sl3d_align.h"
-#include "sl3d_block.h"
-#include "sl3d_internal.h"
+#include "sl3d_align_lane.h"
 
 namespace sl3d {
-
-#define ALIGN_TILE_W 64
-#define ALIGN_TILE_ROWS 32
-
-__device__ __forceinline__ long long wave_sum64(long long n)
-{
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    return n;
-}
 
 // valid / points: the planes of the launch's first view (the target of pair 0), views px_view_stride pixels apart; record: [pairs][ALIGN_WORDS]
 template <int WINDOW>
@@ -43,19 +33,19 @@ __global__ __launch_bounds__(256) void k_align_pass(const uint8_t *__restrict__ 
     const size_t t0 = (size_t)blockIdx.y * px_view_stride, s0 = t0 + px_view_stride;
     const uint8_t *tvalid = valid + t0, *svalid = valid + s0;
     const float *tpoints = points + 3 * t0, *spoints = points + 3 * s0;
-    const int tiles_x = (W + ALIGN_TILE_W - 1) / ALIGN_TILE_W;
-    const int tile_r = (int)(blockIdx.x / (unsigned)tiles_x), tile_c = (int)(blockIdx.x - (unsigned)tile_r * (unsigned)tiles_x);
-    const int c = tile_c * ALIGN_TILE_W + (int)(threadIdx.x & 63);
+    const AlignLane lane = align_lane(W);
+    const int c = lane.c;
     // words 0 - 4, 9, 11 (n, ax, az, bx, bz, dy, sources) and words 5 - 8, 10 (the products)
     int lin[7] = {0, 0, 0, 0, 0, 0, 0};
     long long prod[5] = {0, 0, 0, 0, 0};
 #pragma unroll 1
     for (int k = 0; k < ALIGN_TILE_ROWS / 4; k++) {
-        const int r = tile_r * ALIGN_TILE_ROWS + 4 * k + (int)(threadIdx.x >> 6);
+        const int r = align_row(lane.tile_r, k);
         if (r >= H || c >= W) continue;
         const size_t px = (size_t)r * pitch + c;
         if (svalid[px] != 1) continue;
-        const float p[3] = {spoints[3 * px], spoints[3 * px + 1], spoints[3 * px + 2]};
+        float p[3];
+        load3(spoints, px, p);
         if (!align_finite(p)) continue;
         lin[6]++;
         double ph[3], dcc, drr;
@@ -64,21 +54,7 @@ __global__ __launch_bounds__(256) void k_align_pass(const uint8_t *__restrict__ 
         const int cc = (int)dcc, rr = (int)drr;  // below 2^30 in magnitude
         double best = (double)__builtin_inff();
         float q[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-        for (int dy = -WINDOW; dy <= WINDOW; dy++) {
-            const int tr = rr + dy;
-            if (tr < 0 || tr >= H) continue;
-#pragma unroll
-            for (int dx = -WINDOW; dx <= WINDOW; dx++) {
-                const int tc = cc + dx;
-                if (tc < 0 || tc >= W) continue;
-                const size_t tpx = (size_t)tr * pitch + tc;
-                if (tvalid[tpx] != 1) continue;
-                const float cand[3] = {tpoints[3 * tpx], tpoints[3 * tpx + 1], tpoints[3 * tpx + 2]};
-                const double d2 = align_d2(cand, ph);
-                if (d2 < best) best = d2, q[0] = cand[0], q[1] = cand[1], q[2] = cand[2];
-            }
-        }
+        ALIGN_SEARCH(WINDOW, cc, rr, W, H, pitch, tvalid, tpoints, ph, best, q, (void)0)
         int64_t t[5];
         if (!align_accept(p, q, best, &a, t)) continue;
         const long long ax = t[0], az = t[1], bx = t[2], bz = t[3], dy = t[4];
@@ -99,20 +75,7 @@ __global__ __launch_bounds__(256) void k_align_pass(const uint8_t *__restrict__ 
         w[5] = prod[0], w[6] = prod[1], w[7] = prod[2], w[8] = prod[3];
         w[9] = lin[5], w[10] = prod[4], w[11] = lin[6];
     }
-    __syncthreads();
-    if (threadIdx.x < ALIGN_WORDS) {
-        const long long v = (s_words[0][threadIdx.x] + s_words[1][threadIdx.x]) + (s_words[2][threadIdx.x] + s_words[3][threadIdx.x]);
-        if (v) atomicAdd(record + (size_t)blockIdx.y * ALIGN_WORDS + threadIdx.x, (unsigned long long)v);
-    }
-}
-
-template <int WINDOW>
-static void launch_pass(const KParams &P, int first_view, int n_pairs, const AlignCam &cam, const AlignPass &a, unsigned long long *record, hipStream_t st)
-{
-    const unsigned tiles = (unsigned)((P.W + ALIGN_TILE_W - 1) / ALIGN_TILE_W) * (unsigned)((P.H + ALIGN_TILE_ROWS - 1) / ALIGN_TILE_ROWS);
-    const ViewPlanes in = view_planes(P, first_view);
-    hipLaunchKernelGGL(k_align_pass<WINDOW>, dim3(tiles, n_pairs), dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch, P.px_view_stride, P.col0,
-                       P.row0, cam, a, record);
+    align_words_add<ALIGN_WORDS>(s_words, record + (size_t)blockIdx.y * ALIGN_WORDS);
 }
 
 // the memset of the n_pairs records and the pass over views [first_view, first_view + n_pairs]
@@ -120,18 +83,11 @@ int launch_align_pass(const KParams &P, int first_view, int n_pairs, int window,
                       void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(record, 0, (size_t)n_pairs * ALIGN_WORDS * sizeof(unsigned long long), st);
-    if (e != hipSuccess) return (int)e;
-    (void)hipGetLastError();
-    switch (window) {
-    case 0: launch_pass<0>(P, first_view, n_pairs, cam, a, record, st); break;
-    case 1: launch_pass<1>(P, first_view, n_pairs, cam, a, record, st); break;
-    case 2: launch_pass<2>(P, first_view, n_pairs, cam, a, record, st); break;
-    case 3: launch_pass<3>(P, first_view, n_pairs, cam, a, record, st); break;
-    case 4: launch_pass<4>(P, first_view, n_pairs, cam, a, record, st); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-    return (int)hipGetLastError();
+    const ViewPlanes in = view_planes(P, first_view);
+    return align_dispatch(record, n_pairs, ALIGN_WORDS, window, st, [&](auto w) {
+        hipLaunchKernelGGL(k_align_pass<decltype(w)::value>, dim3(align_tiles(P), n_pairs), dim3(256), 0, st, in.valid, in.points, P.W, P.H, P.pitch,
+                           P.px_view_stride, P.col0, P.row0, cam, a, record);
+    });
 }
 
 }  // namespace sl3d

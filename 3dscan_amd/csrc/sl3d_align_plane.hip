@@ -12,29 +12,16 @@
 // The words: three counts in an int per lane, the products in an int64; wave sums by shuffles, the four waves through LDS, then one 64-bit
 // integer atomicAdd per non-zero word and block into the record the launcher cleared on the stream.  Integer atomics only, no float
 // atomics.  Every loop has a compile-time bound.  Compiled with -ffp-contract=off.
+// The tile walk, the search, the tail behind the waves' words and the dispatch over the window are sl3d_align_lane.h's, shared by the two forms.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sl3d_align_lane.h"
 #include "sl3d_align_plane.h"
-#include "sl3d_block.h"
-#include "sl3d_internal.h"
 
 namespace sl3d {
 
-#define ALIGN_TILE_W 64
-#define ALIGN_TILE_ROWS 32
 #define ALIGN_PLANE_PRODUCTS 15
-
-__device__ __forceinline__ long long plane_wave_sum64(long long n)
-{
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    return n;
-}
-
-__device__ __forceinline__ void load3(const float *__restrict__ points, size_t px, float *p)
-{
-    p[0] = points[3 * px], p[1] = points[3 * px + 1], p[2] = points[3 * px + 2];
-}
 
 // valid / points / normals: the planes of the launch's first view, views px_view_stride pixels apart
 __global__ __launch_bounds__(256) void k_align_normals(const uint8_t *__restrict__ valid, const float *__restrict__ points, int W, int H, int pitch,
@@ -42,12 +29,11 @@ __global__ __launch_bounds__(256) void k_align_normals(const uint8_t *__restrict
 {
     const size_t v0 = (size_t)blockIdx.y * px_view_stride;
     valid += v0, points += 3 * v0, normals += 3 * v0;
-    const int tiles_x = (W + ALIGN_TILE_W - 1) / ALIGN_TILE_W;
-    const int tile_r = (int)(blockIdx.x / (unsigned)tiles_x), tile_c = (int)(blockIdx.x - (unsigned)tile_r * (unsigned)tiles_x);
-    const int c = tile_c * ALIGN_TILE_W + (int)(threadIdx.x & 63);
+    const AlignLane lane = align_lane(W);
+    const int c = lane.c;
 #pragma unroll 1
     for (int k = 0; k < ALIGN_TILE_ROWS / 4; k++) {
-        const int r = tile_r * ALIGN_TILE_ROWS + 4 * k + (int)(threadIdx.x >> 6);
+        const int r = align_row(lane.tile_r, k);
         if (r >= H || c >= W) continue;
         const size_t px = (size_t)r * pitch + c;
         float n[3] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
@@ -71,16 +57,15 @@ __global__ __launch_bounds__(256) void k_align_plane_pass(const uint8_t *__restr
     const size_t t0 = (size_t)blockIdx.y * px_view_stride, s0 = t0 + px_view_stride;
     const uint8_t *tvalid = valid + t0, *svalid = valid + s0;
     const float *tpoints = points + 3 * t0, *spoints = points + 3 * s0, *tnormals = normals + 3 * t0;
-    const int tiles_x = (W + ALIGN_TILE_W - 1) / ALIGN_TILE_W;
-    const int tile_r = (int)(blockIdx.x / (unsigned)tiles_x), tile_c = (int)(blockIdx.x - (unsigned)tile_r * (unsigned)tiles_x);
-    const int c = tile_c * ALIGN_TILE_W + (int)(threadIdx.x & 63);
+    const AlignLane lane = align_lane(W);
+    const int c = lane.c;
     int cnt[3] = {0, 0, 0};  // words 0, 16, 17: accepted, sources, lost to a missing normal
     long long prod[ALIGN_PLANE_PRODUCTS];
 #pragma unroll
     for (int k = 0; k < ALIGN_PLANE_PRODUCTS; k++) prod[k] = 0;
 #pragma unroll 1
     for (int k = 0; k < ALIGN_TILE_ROWS / 4; k++) {
-        const int r = tile_r * ALIGN_TILE_ROWS + 4 * k + (int)(threadIdx.x >> 6);
+        const int r = align_row(lane.tile_r, k);
         if (r >= H || c >= W) continue;
         const size_t px = (size_t)r * pitch + c;
         if (svalid[px] != 1) continue;
@@ -95,22 +80,7 @@ __global__ __launch_bounds__(256) void k_align_plane_pass(const uint8_t *__restr
         double best = (double)__builtin_inff();
         float q[3] = {0.0f, 0.0f, 0.0f};
         size_t bpx = 0;
-#pragma unroll 1
-        for (int dy = -WINDOW; dy <= WINDOW; dy++) {
-            const int tr = rr + dy;
-            if (tr < 0 || tr >= H) continue;
-#pragma unroll
-            for (int dx = -WINDOW; dx <= WINDOW; dx++) {
-                const int tc = cc + dx;
-                if (tc < 0 || tc >= W) continue;
-                const size_t tpx = (size_t)tr * pitch + tc;
-                if (tvalid[tpx] != 1) continue;
-                float cand[3];
-                load3(tpoints, tpx, cand);
-                const double d2 = align_d2(cand, ph);
-                if (d2 < best) best = d2, q[0] = cand[0], q[1] = cand[1], q[2] = cand[2], bpx = tpx;
-            }
-        }
+        ALIGN_SEARCH(WINDOW, cc, rr, W, H, pitch, tvalid, tpoints, ph, best, q, bpx = tpx)
         int64_t f[ALIGN_PLANE_FEATURES];
         const int verdict = align_plane_accept(p, q, tnormals + 3 * bpx, best, &a, f);  // (the normal is read behind a finite best: bpx is a pixel of the window)
         cnt[2] += verdict == 2;
@@ -125,23 +95,14 @@ __global__ __launch_bounds__(256) void k_align_plane_pass(const uint8_t *__restr
 #pragma unroll
     for (int k = 0; k < 3; k++) cnt[k] = (int)wave_sum((unsigned)cnt[k]);
 #pragma unroll
-    for (int k = 0; k < ALIGN_PLANE_PRODUCTS; k++) prod[k] = plane_wave_sum64(prod[k]);
+    for (int k = 0; k < ALIGN_PLANE_PRODUCTS; k++) prod[k] = wave_sum64(prod[k]);
     if ((threadIdx.x & 63) == 0) {
         long long *w = s_words[threadIdx.x >> 6];
         w[0] = cnt[0], w[16] = cnt[1], w[17] = cnt[2];
 #pragma unroll
         for (int k = 0; k < ALIGN_PLANE_PRODUCTS; k++) w[1 + k] = prod[k];
     }
-    __syncthreads();
-    if (threadIdx.x < ALIGN_PLANE_WORDS) {
-        const long long v = (s_words[0][threadIdx.x] + s_words[1][threadIdx.x]) + (s_words[2][threadIdx.x] + s_words[3][threadIdx.x]);
-        if (v) atomicAdd(record + (size_t)blockIdx.y * ALIGN_PLANE_WORDS + threadIdx.x, (unsigned long long)v);
-    }
-}
-
-static unsigned align_tiles(const KParams &P)
-{
-    return (unsigned)((P.W + ALIGN_TILE_W - 1) / ALIGN_TILE_W) * (unsigned)((P.H + ALIGN_TILE_ROWS - 1) / ALIGN_TILE_ROWS);
+    align_words_add<ALIGN_PLANE_WORDS>(s_words, record + (size_t)blockIdx.y * ALIGN_PLANE_WORDS);
 }
 
 int launch_align_normals(const KParams &P, int first_view, int n_views, float normal_edge, float *normals, void *stream)
@@ -153,32 +114,16 @@ int launch_align_normals(const KParams &P, int first_view, int n_views, float no
     return (int)hipGetLastError();
 }
 
-template <int WINDOW>
-static void launch_plane_pass(const KParams &P, int first_view, int n_pairs, const AlignCam &cam, const AlignPass &a, const float *normals,
-                              unsigned long long *record, hipStream_t st)
-{
-    const ViewPlanes in = view_planes(P, first_view);
-    hipLaunchKernelGGL(k_align_plane_pass<WINDOW>, dim3(align_tiles(P), n_pairs), dim3(256), 0, st, in.valid, in.points, normals, P.W, P.H, P.pitch,
-                       P.px_view_stride, P.col0, P.row0, cam, a, record);
-}
-
 // the memset of the n_pairs records and the pass over views [first_view, first_view + n_pairs]
 int launch_align_plane_pass(const KParams &P, int first_view, int n_pairs, int window, const AlignCam &cam, const AlignPass &a, const float *normals,
                             unsigned long long *record, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(record, 0, (size_t)n_pairs * ALIGN_PLANE_WORDS * sizeof(unsigned long long), st);
-    if (e != hipSuccess) return (int)e;
-    (void)hipGetLastError();
-    switch (window) {
-    case 0: launch_plane_pass<0>(P, first_view, n_pairs, cam, a, normals, record, st); break;
-    case 1: launch_plane_pass<1>(P, first_view, n_pairs, cam, a, normals, record, st); break;
-    case 2: launch_plane_pass<2>(P, first_view, n_pairs, cam, a, normals, record, st); break;
-    case 3: launch_plane_pass<3>(P, first_view, n_pairs, cam, a, normals, record, st); break;
-    case 4: launch_plane_pass<4>(P, first_view, n_pairs, cam, a, normals, record, st); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-    return (int)hipGetLastError();
+    const ViewPlanes in = view_planes(P, first_view);
+    return align_dispatch(record, n_pairs, ALIGN_PLANE_WORDS, window, st, [&](auto w) {
+        hipLaunchKernelGGL(k_align_plane_pass<decltype(w)::value>, dim3(align_tiles(P), n_pairs), dim3(256), 0, st, in.valid, in.points, normals, P.W, P.H,
+                           P.pitch, P.px_view_stride, P.col0, P.row0, cam, a, record);
+    });
 }
 
 }  // namespace sl3d

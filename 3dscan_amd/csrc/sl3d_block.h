@@ -35,6 +35,11 @@ __device__ __forceinline__ unsigned wave_sum(unsigned n)
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
     return n;
 }
+__device__ __forceinline__ long long wave_sum64(long long n)
+{
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    return n;
+}
 
 // inclusive prefix of c over the lane's wave; the wave's total goes to s_wave[wave] (__shared__ unsigned [4]), valid behind the barrier
 // this ends in

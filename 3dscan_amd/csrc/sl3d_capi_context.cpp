@@ -309,8 +309,8 @@ try {
     if (x->h_counts) (void)hipHostFree(x->h_counts);
     if (x->h_quad_part) (void)hipHostFree((void *)x->h_quad_part);
     if (x->h_mi_part) (void)hipHostFree((void *)x->h_mi_part);
-    if (x->h_align_words) (void)hipHostFree(x->h_align_words);
-    if (x->h_align_plane_words) (void)hipHostFree(x->h_align_plane_words);
+    for (const auto &r : x->align_rec)
+        if (r.host) (void)hipHostFree(r.host);
     for (hipEvent_t e : x->ev_up) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_done) (void)hipEventDestroy(e);
     for (hipEvent_t e : x->ev_down) (void)hipEventDestroy(e);

@@ -11,6 +11,8 @@
 //   sl3d_capi_align.cpp    the turntable refinement (include/sl3d_align.h: sl3d_align_sums, sl3d_align_solve, sl3d_refine_turntable, sl3d_get_align_camera)
 //   sl3d_capi_align_plane.cpp  its point-to-plane form (include/sl3d_align_plane.h: sl3d_align_normals, sl3d_get_align_normals, sl3d_align_plane_sums,
 //                          sl3d_align_plane_solve, sl3d_refine_turntable_plane)
+//   sl3d_capi_tsdf.cpp     the TSDF volume (include/sl3d_tsdf.h: sl3d_tsdf_reset, sl3d_tsdf_integrate, sl3d_tsdf_extract and the two getters)
+//   sl3d_capi_align.h      what those three share beyond this header: the camera hand-over, the checks, one pass and one loop over an AlignForm
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -2,7 +2,7 @@
 // sl3d_tsdf_reset defines and clears the volume, sl3d_tsdf_integrate adds views of the dense result to it, sl3d_tsdf_extract leaves the
 // oriented points of its zero level on the device; sl3d_get_tsdf and sl3d_get_tsdf_surface hand the planes and the surface out.  The calls
 // read the points / valid planes and write nothing but the context's own volume, surface and words.
-#include "sl3d_capi_internal.h"
+#include "sl3d_capi_align.h"  // align_camera
 #include "../../include/sl3d_tsdf.h"
 #include "sl3d_tsdf.h"
 
@@ -59,8 +59,7 @@ try {
     if (rc) return rc;
     if (first_step < 0 || (int64_t)first_step + n_views > TSDF_MAX_STEPS)
         return fail(x, SL3D_E_INVALID_ARG, "tsdf_integrate: first_step must be >= 0 and first_step + n_views <= 65535");
-    if (!est || !std::isfinite(est[0]) || !std::isfinite(est[1]) || !std::isfinite(est[2]) || !std::isfinite(est[3]))
-        return fail(x, SL3D_E_INVALID_ARG, "tsdf_integrate: a null or non-finite estimate");
+    if (!est || !finite4(est)) return fail(x, SL3D_E_INVALID_ARG, "tsdf_integrate: a null or non-finite estimate");
     if (!x->have_cal) return fail(x, SL3D_E_STATE, "tsdf_integrate: sl3d_set_calibration has not been called");
     if (!x->dense_ran) return fail(x, SL3D_E_STATE, "tsdf_integrate: no dense result yet (sl3d_run)");
     if (!x->tsdf_dims[0]) return fail(x, SL3D_E_STATE, "tsdf_integrate: no sl3d_tsdf_reset has defined a volume");
@@ -80,10 +79,7 @@ try {
     // (pageable memory: it has been read when the copy returns)
     HIPCHK(x, hipMemcpyAsync(x->d_tsdf_turns, turns.data(), turns.size() * sizeof(TsdfTurn), hipMemcpyHostToDevice, x->stream));
     AlignCam cam;
-    memcpy(cam.Rc, x->S.Rc, sizeof cam.Rc);
-    memcpy(cam.tc, x->S.tc, sizeof cam.tc);
-    memcpy(cam.Kc, x->Kc_raw, sizeof cam.Kc);
-    memcpy(cam.dc, x->dc_raw, sizeof cam.dc);
+    align_camera(x, &cam);
     rc = launched(x, launch_tsdf_integrate(x->P, first_view, n_views, cam, tsdf_volume(x), est[2], est[3], (const TsdfTurn *)x->d_tsdf_turns, x->d_tsdf_depth, x->d_tsdf_sum,
                                            x->d_tsdf_weight, x->d_tsdf_words, x->stream));
     if (rc) return rc;

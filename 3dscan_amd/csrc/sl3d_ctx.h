@@ -196,22 +196,24 @@ struct sl3d_ctx {
     unsigned long long *d_vox_words = nullptr;
     size_t vox_cap[8] = {0};
     int64_t vox_n = -1, reg_total = -1;
-    // sl3d_align_sums / sl3d_refine_turntable (allocated on first use, freed by sl3d_destroy): [max_views - 1][ALIGN_WORDS] words, a pair's
-    // record, on the device, and the pinned block of the same size a pass's words are downloaded into.  dense_ran: a call that writes
-    // the dense planes (sl3d_run, sl3d_process_views, sl3d_triangulate, sl3d_triangulate_subpixel) has gone out -- the passes refuse before
-    unsigned long long *d_align_rec = nullptr;
-    long long *h_align_words = nullptr;
+    // The pairs' records of the two refinements (allocated on first use by align_pass, sl3d_capi_align.cpp; freed by sl3d_destroy): [0]
+    // sl3d_align_sums / sl3d_refine_turntable, [max_views - 1][ALIGN_WORDS] words; [1] the point-to-plane form, [max_views - 1]
+    // [ALIGN_PLANE_WORDS].  dev: the records on the device; host: the pinned block of the same size a pass's words are downloaded into.  Two
+    // buffers: a call of one form leaves what the other has in flight alone.  dense_ran: a call that writes the dense planes (sl3d_run,
+    // sl3d_process_views, sl3d_triangulate, sl3d_triangulate_subpixel) has gone out -- the passes refuse before
+    struct AlignRecord {
+        unsigned long long *dev = nullptr;
+        long long *host = nullptr;
+    } align_rec[2];
     bool dense_ran = false;
     // sl3d_align_normals / sl3d_align_plane_sums / sl3d_refine_turntable_plane (include/sl3d_align_plane.h; first use, sl3d_destroy): the
     // normal planes of the views [align_nrm_lo, align_nrm_hi) -- every view a call has asked for so far -- back to back, a view's laid out
     // like its points ([px_view_stride][3] floats, rows pitch pixels apart); align_nrm_ready[view]: its normals have been computed since the
-    // block was last allocated.  The pairs' records of the point-to-plane pass ([max_views - 1][ALIGN_PLANE_WORDS]) and their pinned twin
+    // block was last allocated
     float *d_align_nrm = nullptr;
     size_t align_nrm_cap = 0;
     int align_nrm_lo = 0, align_nrm_hi = 0;
     std::vector<char> align_nrm_ready;
-    unsigned long long *d_align_plane_rec = nullptr;
-    long long *h_align_plane_words = nullptr;
     // sl3d_tsdf_reset / sl3d_tsdf_integrate / sl3d_tsdf_extract (include/sl3d_tsdf.h; first use, grown on demand, sl3d_destroy): the two
     // planes of the volume, the rotations and the depth planes of a call's views, the block scratch of an extraction (tsdf_s.tot is not used), its three
     // outputs and the calls' words; tsdf_cap: the elements each growing array holds, in the order sl3d_capi_tsdf.cpp names them.  The

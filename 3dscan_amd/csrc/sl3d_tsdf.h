@@ -8,7 +8,7 @@
 //
 //   X_a      = ((double)i_a + 0.5) * L + (double)origin[a]                                                                  (tsdf_centre)
 //   P        = (c_m * x - (-s_m) * z) + tx, X.y, ((-s_m) * x + c_m * z) + tz with x = X.x - tx, z = X.z - tz                 (tsdf_step)
-//   xc, u, v = the camera algebra of align_centre (sl3d_align.h), the same text, u and v left unrounded                    (tsdf_project)
+//   xc, u, v = P into the camera as a pass takes p^ there, u and v left unrounded                                          (align_project, sl3d_align.h)
 //   fu, fv   = floor(u) - col0, floor(v) - row0: a cell iff 0 <= fu, fu + 1 < W, 0 <= fv, fv + 1 < H; a, b = u - floor(u), v - floor(v)
 //   z_dxdy   = ((Rc[6] * q.x + Rc[7] * q.y) + Rc[8] * q.z) + tc[2] of a pixel with valid == 1 and a finite q               (tsdf_depth)
 //   zq       = ((z00 * (1 - a) + z10 * a) * (1 - b)) + ((z01 * (1 - a) + z11 * a) * b) unless max z - min z > T
@@ -53,7 +53,7 @@ SL3D_MESH_FN struct TsdfTurn tsdf_next_turn(struct TsdfTurn t, double c, double 
     return n;
 }
 
-// step 1: align_step (sl3d_align.h) over a double point -- a: (c_m, -s_m, tx, tz)
+// step 1: align_step (sl3d_align.h) over a double point -- a: (c_m, -s_m, tx, tz).  Its own text for the reason given there
 SL3D_MESH_FN void tsdf_step(const double *p, const struct AlignPass *a, double *ph)
 {
     const double x = p[0] - a->tx, z = p[2] - a->tz;
@@ -62,26 +62,8 @@ SL3D_MESH_FN void tsdf_step(const double *p, const struct AlignPass *a, double *
     ph[2] = (a->s * x + a->c * z) + a->tz;
 }
 
-// step 2: the camera algebra of align_centre, u and v unrounded; *zc = xc.z.  0: no sample
-SL3D_MESH_FN int tsdf_project(const double *ph, const struct AlignCam *m, double *pu, double *pv, double *zc)
-{
-    double xc[3];
-    for (int i = 0; i < 3; i++) xc[i] = ((m->Rc[3 * i] * ph[0] + m->Rc[3 * i + 1] * ph[1]) + m->Rc[3 * i + 2] * ph[2]) + m->tc[i];
-    if (!(xc[2] > 0.0) || !isfinite(xc[2])) return 0;
-    const double xn = xc[0] / xc[2], yn = xc[1] / xc[2];
-    const double k1 = m->dc[0], k2 = m->dc[1], p1 = m->dc[2], p2 = m->dc[3], k3 = m->dc[4];
-    const double r2 = xn * xn + yn * yn;
-    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-    const double xd = xn * rad + (2.0 * p1 * xn * yn + p2 * (r2 + 2.0 * xn * xn));
-    const double yd = yn * rad + (p1 * (r2 + 2.0 * yn * yn) + 2.0 * p2 * xn * yn);
-    const double *K = m->Kc;
-    const double w = (K[6] * xd + K[7] * yd) + K[8];
-    const double u = ((K[0] * xd + K[1] * yd) + K[2]) / w, v = ((K[3] * xd + K[4] * yd) + K[5]) / w;
-    *pu = u, *pv = v, *zc = xc[2];
-    return 1;
-}
-
-// step 3: the window pixel (c, r) of the upper left of the four, the weights a and b.  0: no sample (NaN fails every comparison)
+// step 2 is align_project (sl3d_align.h).  step 3: the window pixel (c, r) of the upper left of the four, the weights a and b.  0: no sample
+// (NaN fails every comparison)
 SL3D_MESH_FN int tsdf_cell(double u, double v, int W, int H, int col0, int row0, int *c, int *r, double *a, double *b)
 {
     const double flu = floor(u), flv = floor(v);
@@ -122,7 +104,7 @@ SL3D_MESH_FN int tsdf_sample(const double *X, const struct AlignPass *a, const s
     double P[3], u, v, zc, wa, wb, z[4];
     int c, r;
     tsdf_step(X, a, P);
-    if (!tsdf_project(P, m, &u, &v, &zc)) return 0;
+    if (!align_project(P, m, &u, &v, &zc)) return 0;
     if (!tsdf_cell(u, v, f->W, f->H, f->col0, f->row0, &c, &r, &wa, &wb)) return 0;
     for (int k = 0; k < 4; k++) {  // (dx, dy) = (0, 0), (1, 0), (0, 1), (1, 1)
         const size_t px = (size_t)(r + (k >> 1)) * (size_t)f->pitch + (size_t)(c + (k & 1));
@@ -150,7 +132,7 @@ SL3D_MESH_FN int tsdf_sample_plane(const double *X, const struct AlignPass *a, c
     double P[3], u, v, zc, wa, wb, z[4];
     int c, r;
     tsdf_step(X, a, P);
-    if (!tsdf_project(P, m, &u, &v, &zc)) return 0;
+    if (!align_project(P, m, &u, &v, &zc)) return 0;
     if (!tsdf_cell(u, v, f->W, f->H, f->col0, f->row0, &c, &r, &wa, &wb)) return 0;
     for (int k = 0; k < 4; k++) {
         z[k] = zp[(size_t)(r + (k >> 1)) * (size_t)f->pitch + (size_t)(c + (k & 1))];

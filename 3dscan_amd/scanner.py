@@ -309,29 +309,28 @@ def pattern_counts(proj_extent, fringe_width):
     return nc.value, npl.value
 
 
+def _host_solve(symbol, words, sums, range, ox, oz, est):
+    """a host-only solve (`symbol`) over the (n_pairs, words) int64 words of a pass"""
+    L = load_library()
+    w = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, words)
+    e, out, stats = np.ascontiguousarray(est, dtype=np.float64).reshape(4), np.empty(4), np.empty(4)
+    rc = getattr(L, symbol)(w.ctypes.data, len(w), range, ox, oz, e.ctypes.data, out.ctypes.data, stats.ctypes.data)
+    if rc != 0:
+        raise Sl3dError(symbol + ": " + L.sl3d_strerror(rc).decode())
+    return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
+
+
 def align_solve(sums, range, ox, oz, est):
     """sl3d_align_solve: the closed-form solve over the (n_pairs, 12) int64 words of a pass (the rule: include/sl3d_align.h); host only, no
     context.  est: (c, s, tx, tz).  Returns (the new estimate float64[4], dict(n, rms_xz, rms_y, degenerate))."""
-    L = load_library()
-    w = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, ALIGN_WORDS)
-    e, out, stats = np.ascontiguousarray(est, dtype=np.float64).reshape(4), np.empty(4), np.empty(4)
-    rc = L.sl3d_align_solve(w.ctypes.data, len(w), range, ox, oz, e.ctypes.data, out.ctypes.data, stats.ctypes.data)
-    if rc != 0:
-        raise Sl3dError("sl3d_align_solve: " + L.sl3d_strerror(rc).decode())
-    return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
+    return _host_solve("sl3d_align_solve", ALIGN_WORDS, sums, range, ox, oz, est)
 
 
 def align_plane_solve(sums, range, ox, oz, est):
     """sl3d_align_plane_solve: the Gauss-Newton solve over the (n_pairs, 18) int64 words of a point-to-plane pass (the rule:
     include/sl3d_align_plane.h); host only, no context.  est: (c, s, tx, tz).  Returns (the new estimate float64[4], dict(n, rms_xz,
     rms_y, degenerate)): rms_xz carries rms_plane, rms_y is NaN."""
-    L = load_library()
-    w = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, ALIGN_PLANE_WORDS)
-    e, out, stats = np.ascontiguousarray(est, dtype=np.float64).reshape(4), np.empty(4), np.empty(4)
-    rc = L.sl3d_align_plane_solve(w.ctypes.data, len(w), range, ox, oz, e.ctypes.data, out.ctypes.data, stats.ctypes.data)
-    if rc != 0:
-        raise Sl3dError("sl3d_align_plane_solve: " + L.sl3d_strerror(rc).decode())
-    return out, dict(n=int(stats[0]), rms_xz=float(stats[1]), rms_y=float(stats[2]), degenerate=bool(stats[3]))
+    return _host_solve("sl3d_align_plane_solve", ALIGN_PLANE_WORDS, sums, range, ox, oz, est)
 
 
 def tsdf_bounds(cloud, voxel, margin=2):
@@ -1053,20 +1052,23 @@ class Scanner(_Handle):
         self._chk(self.L.sl3d_align_sums(self._h, first_view, n_views, e.ctypes.data, ox, oz, range, max_dist, window, out.ctypes.data), "sl3d_align_sums")
         return out[:n_views - 1]
 
-    def refine_turntable(self, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window=2, iterations=20):
-        """sl3d_refine_turntable: the axis point and the step of register_views / register_clouds refined from the views' own overlap,
-        from the rough (tx, ty, tz, rot_step): up to `iterations` rounds of pass and solve.  Returns a dict: tx, ty, tz, rot_step (float32
-        values, ready for register_views), est (c, s, tx, tz in float64), n, sources, rms_xz, rms_y of the last pass, degenerate, n_done
-        and log -- per iteration made a dict(est, n, sources, rms_xz, rms_y) with the estimate its pass used."""
+    def _refine(self, symbol, iterations, *args):
+        """a refinement (`symbol`, args its arguments between the context and the outputs): the dict refine_turntable documents"""
         out, done = Turntable(), C.c_int(0)
         log = (AlignIteration * max(iterations, 1))()
-        self._chk(self.L.sl3d_refine_turntable(self._h, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window, iterations, C.byref(out), log,
-                                               C.byref(done)), "sl3d_refine_turntable")
+        self._chk(getattr(self.L, symbol)(self._h, *args, C.byref(out), log, C.byref(done)), symbol)
         return dict(tx=np.float32(out.tx), ty=np.float32(out.ty), tz=np.float32(out.tz), rot_step=np.float32(out.rot_step),
                     est=np.array(out.est[:], dtype=np.float64), n=int(out.n), sources=int(out.sources), rms_xz=float(out.rms_xz), rms_y=float(out.rms_y),
                     degenerate=bool(out.degenerate), n_done=done.value,
                     log=[dict(est=np.array(e.est[:], dtype=np.float64), n=int(e.n), sources=int(e.sources), rms_xz=float(e.rms_xz), rms_y=float(e.rms_y))
                          for e in log[:done.value]])
+
+    def refine_turntable(self, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window=2, iterations=20):
+        """sl3d_refine_turntable: the axis point and the step of register_views / register_clouds refined from the views' own overlap,
+        from the rough (tx, ty, tz, rot_step): up to `iterations` rounds of pass and solve.  Returns a dict: tx, ty, tz, rot_step (float32
+        values, ready for register_views), est (c, s, tx, tz in float64), n, sources, rms_xz, rms_y of the last pass, degenerate, n_done
+        and log -- per iteration made a dict(est, n, sources, rms_xz, rms_y) with the estimate its pass used."""
+        return self._refine("sl3d_refine_turntable", iterations, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, window, iterations)
 
     def align_normals(self, first_view, n_views, normal_edge):
         """sl3d_align_normals: the dense normals of the views first_view .. first_view + n_views - 1 from each pixel's four neighbours
@@ -1092,15 +1094,8 @@ class Scanner(_Handle):
     def refine_turntable_plane(self, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, normal_edge, window=2, iterations=20):
         """sl3d_refine_turntable_plane: refine_turntable with the point-to-plane error metric -- the residual along the target's surface
         normal, normals from neighbours within normal_edge.  The dict of refine_turntable: rms_xz carries rms_plane, rms_y is NaN."""
-        out, done = Turntable(), C.c_int(0)
-        log = (AlignIteration * max(iterations, 1))()
-        self._chk(self.L.sl3d_refine_turntable_plane(self._h, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, normal_edge, window,
-                                                     iterations, C.byref(out), log, C.byref(done)), "sl3d_refine_turntable_plane")
-        return dict(tx=np.float32(out.tx), ty=np.float32(out.ty), tz=np.float32(out.tz), rot_step=np.float32(out.rot_step),
-                    est=np.array(out.est[:], dtype=np.float64), n=int(out.n), sources=int(out.sources), rms_xz=float(out.rms_xz), rms_y=float(out.rms_y),
-                    degenerate=bool(out.degenerate), n_done=done.value,
-                    log=[dict(est=np.array(e.est[:], dtype=np.float64), n=int(e.n), sources=int(e.sources), rms_xz=float(e.rms_xz), rms_y=float(e.rms_y))
-                         for e in log[:done.value]])
+        return self._refine("sl3d_refine_turntable_plane", iterations, first_view, n_views, tx, ty, tz, rot_step, range, max_dist, normal_edge, window,
+                            iterations)
 
     def voxel_grid_device(self, leaf, min_points=1, centroid=True, cloud=None):
         """sl3d_voxel_grid: one point per occupied cell of a grid of edge `leaf` over the registered cloud the last register_views /

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 FULL, ORIGIN = (320, 240), (37, 5)
 SHAPES = [(1, 1), (3, 2), (9, 9), (67, 19), (130, 37), (257, 9)]       # (W, H)
-WINDOWS = (0, 1, 2, 4)
+WINDOWS = (0, 1, 2, 3, 4)
 RANGE, MAX_DIST = 64.0, 0.5
 INVALID_ARG, STATE = -1, -4
 
