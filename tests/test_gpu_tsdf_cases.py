@@ -7,12 +7,14 @@ window with col0, row0 != 0 inside a larger full frame, at most 48 x 36.  k_tsdf
 
 1. Volumes (5, 3, 2) below a wave, (64, 1, 1), (65, 3, 2) across lane 64 in i, (33, 9, 7) with a last partial block and (70, 33, 5), over five
    crafted turntable views (tests/tsdf_cases.shape_case: noise, outliers that trip the depth guard, invalid pixels): 1, 2 and 5 views,
-   first_step 0 and 3, views from slot 1 on, two calls that must equal one call over the same views, and a reset that clears.  The
-   padding columns hold perfect points under valid bytes.
+   first_step 0 and 3, views from slot 1 on, two calls that must equal one call over the same views, and a reset that clears.  At 48
+   columns the pitch is 48: these views have no padding columns (tests/test_gpu_tsdf_layouts.py runs several views on windows that
+   have them, with perfect points under valid bytes there).
 2. One voxel each (tests/tsdf_cases.special_cases, an exact camera): a centre behind the camera, a projection on the last usable column
    and row and one past it, one of the four pixels invalid, a NaN or an infinity under a valid byte, a depth spread exactly T and just
    above, sdf exactly -T and just below, d clamped at 1, d * 32767 on a tie.
-3. The call's protocol: the asynchronous form, the state the calls need, every refusal, each checked to have changed nothing."""
+3. The call's protocol: the asynchronous form, the state the calls need, every refusal, each checked to have changed nothing.
+Padded and wide windows, windows without a cell, the int32 bound of sum and the last turntable indices: tests/test_gpu_tsdf_layouts.py."""
 import ctypes as C
 
 import numpy as np

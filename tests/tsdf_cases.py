@@ -1,6 +1,8 @@
 """The inputs of the TSDF tests (tests/test_tsdf_arith.py on the CPU, tests/test_gpu_tsdf_cases.py and tests/test_gpu_tsdf_extract.py on the
 device): crafted turntable views on a 48 x 36 window at (37, 5) of a 320 x 240 frame with volumes of the shapes the kernels can go wrong
 at, and planes crafted pixel by pixel for an exact camera, in which one voxel meets one special case of the rule (include/sl3d_tsdf.h).
+For tests/test_tsdf_layout_cases.py and tests/test_gpu_tsdf_layouts.py: the same views on windows whose rows are padded, that are wider
+than a block of the depth pre-pass or too small for a cell, two voxels that reach the int32 bound of sum, and the last turntable indices.
 
 The exact camera: Rc = I, tc = 0, no distortion, Kc = (64, 0, 45; 0, 64, 11; 0, 0, 1) -- the principal point is window pixel (8, 6).  With
 the identity estimate a voxel centre X at depth 64 projects to u = X.x + 45, v = X.y + 11 without a rounding, and the camera depth of a
@@ -20,10 +22,10 @@ EXACT = dict(W=40, H=24, Kc=(64.0, 0.0, 45.0, 0.0, 64.0, 11.0, 0.0, 0.0, 1.0), d
 PX, PY = 8, 6                                                               # the principal point in window coordinates
 
 
-def rig_calibration():
+def rig_calibration(full=FULL):
     import importlib
     syn = importlib.import_module("3dscan_amd.synth")
-    return syn.cal_tuple(syn.synth_rig(FULL[0], FULL[1], 2048, 2048))
+    return syn.cal_tuple(syn.synth_rig(full[0], full[1], 2048, 2048))
 
 
 def exact_calibration():
@@ -48,6 +50,106 @@ def shape_case(cam, dims, V, seed):
     L = np.float32(15.0 / max(dims[0], 1.4 * dims[1], 3.0 * dims[2]))
     origin = (centre - 0.5 * float(L) * np.array(dims, F8)).astype(np.float32)
     return points, valid, est, pads, dict(origin=origin, voxel=L, trunc=np.float32(3.0) * L, dims=tuple(dims))
+
+
+# ---- windows whose rows are padded, wider than one block of the depth pre-pass, or too small for a cell ----------------------------------------
+# name -> the full frame, the window (W, H) at ORIGIN, the views, the volume's dims and, for the small windows, voxel and trunc in mm.
+# The pitch of a window is (W + 15) & ~15; k_tsdf_depth takes 256 columns a block.
+WIDE = (640, 240)
+LAYOUTS = {
+    "67x19": dict(full=FULL, frame=(67, 19), V=3, dims=(34, 10, 40)),                       # pitch 80: padding and several views
+    "300x20": dict(full=WIDE, frame=(300, 20), V=3, dims=(150, 4, 40)),                     # pitch 304: two column blocks
+    "530x6": dict(full=WIDE, frame=(530, 6), V=3, dims=(265, 2, 40)),                       # pitch 544: three column blocks
+    "2x2": dict(full=FULL, frame=(2, 2), V=5, dims=(6, 6, 40), voxel=0.1, trunc=1.0),       # one cell
+    "1x7": dict(full=FULL, frame=(1, 7), V=5, dims=(4, 20, 20), voxel=0.1, trunc=1.0),      # no cell
+    "9x1": dict(full=FULL, frame=(9, 1), V=5, dims=(20, 4, 20), voxel=0.1, trunc=1.0),      # no cell
+}
+PADDED = ("67x19", "300x20", "530x6")
+SEED = 11
+EST_OFFSET = np.array([0.0, 0.0, 0.05, -0.03])
+
+
+def pitch_of(W):
+    return (W + 15) & ~15
+
+
+def layout_case(cam, name):
+    """The views of align_reference.crafted_views on the window LAYOUTS[name] and a volume about the box around view 0's points -- the
+    camera looks along a tilted axis, so the wavy surface (100 +- 5 mm of depth) spans more of the volume's z than of the camera's.
+    Without a voxel of its own the volume covers the box's whole width and depth (the voxel from the larger of the two spans, 3 % of
+    room, trunc three voxels) and, its dims in y being small, a band of rows about the middle one.  With one (the small windows: a
+    tenth of a millimetre, well below a pixel's footprint, and a trunc above the depth spread of neighbouring pixels) it is centred on
+    the box -- for the 2 x 2 window the surface under window pixel (0.5, 0.5), the middle of the single cell.
+    The estimate is the one that made the views, its axis moved by EST_OFFSET as the other TSDF tests move it.
+    Returns points, valid, est, pads, vol."""
+    lay = LAYOUTS[name]
+    (W, H), V, dims = lay["frame"], lay["V"], lay["dims"]
+    points, valid, est, pads = AR.crafted_views(cam, W, H, ORIGIN[0], ORIGIN[1], V, SEED)
+    p0 = points[0].astype(F8).reshape(-1, 3)
+    lo, hi = p0.min(axis=0), p0.max(axis=0)
+    if "voxel" in lay:
+        L, T = np.float32(lay["voxel"]), np.float32(lay["trunc"])
+    else:
+        L = np.float32(1.03 * max((hi[0] - lo[0]) / dims[0], (hi[2] - lo[2]) / dims[2]))
+        T = np.float32(3.0) * L
+    origin = (0.5 * (lo + hi) - 0.5 * float(L) * np.array(dims, F8)).astype(np.float32)
+    return points, valid, est + EST_OFFSET, pads, dict(origin=origin, voxel=L, trunc=T, dims=tuple(dims))
+
+
+def padded_image(points, valid, pads):
+    """the views as they lie in memory: (V, H, pitch, 3) and (V, H, pitch), the padding columns of a row holding pads[view][row] under
+    valid bytes of 1 -- what tests/tsdf_gpu.put writes"""
+    V, H, W = valid.shape
+    pitch = pitch_of(W)
+    xyz = np.empty((V, H, pitch, 3), np.float32)
+    val = np.ones((V, H, pitch), np.uint8)
+    xyz[:, :, :W], val[:, :, :W] = points, valid
+    for v in range(V):
+        xyz[v, :, W:] = pads[v][:, None, :]
+    return xyz, val
+
+
+def misread_rows(points, valid, pads):
+    """the window as a kernel sees it that takes W for the row stride of the padded planes: row r begins W pixels, not pitch, behind
+    row r - 1"""
+    V, H, W = valid.shape
+    xyz, val = padded_image(points, valid, pads)
+    return (np.ascontiguousarray(xyz.reshape(V, -1, 3)[:, :H * W].reshape(V, H, W, 3)), np.ascontiguousarray(val.reshape(V, -1)[:, :H * W].reshape(V, H, W)))
+
+
+def sample_columns(vol, points, valid, cam, est, first_step=0):
+    """per view the window columns c of the cells under the voxels that take a sample of it (the restatement's steps 1 to 7)"""
+    import tsdf_reference as TR
+    X, _ = TR.centres(vol)
+    tab = TR.turns(est, first_step + len(points))
+    out = []
+    for j in range(len(points)):
+        ok, _ = TR.view_votes(X, tab[first_step + j], est[2], est[3], points[j], valid[j], cam, ORIGIN[0], ORIGIN[1], F8(np.float32(vol["trunc"])))
+        u = TR.project(TR.step(X[ok], tab[first_step + j], est[2], est[3]), cam)[0]
+        out.append((np.floor(u) - ORIGIN[0]).astype(np.int64))
+    return out
+
+
+# ---- the int32 bound of sum, and turntable indices near the last one -----------------------------------------------------------------------------
+SATURATION_VIEWS = 65535                                                    # TSDF_MAX_STEPS
+SATURATED = 65535 * 32767                                                   # 2,147,385,345 < 2^31
+
+
+def saturation_case():
+    """slab_case of two voxels whose votes are +32767 and -32767: xyz, valid, vol (the exact camera, the identity estimate)"""
+    return slab_case([[1.0, -1.0]])
+
+
+LATE = dict(dims=(33, 9, 7), V=5, first_step=65530, period=65532)
+
+
+def late_case(cam):
+    """The five views and the (33, 9, 7) volume of shape_case at seed 11 under an estimate whose step is a 65,532nd of a turn about the
+    views' own axis: the indices 65530 .. 65534 are the last five admissible ones, and the turn is back near the identity there -- through
+    65,530 steps of the recurrence.  Returns points, valid, est, pads, vol."""
+    points, valid, est, pads, vol = shape_case(cam, LATE["dims"], LATE["V"], SEED)
+    th = 2.0 * np.pi / LATE["period"]
+    return points, valid, np.array([np.cos(th), np.sin(th), est[2], est[3]]), pads, vol
 
 
 # ---- one voxel, one special case ---------------------------------------------------------------------------------------------------------------

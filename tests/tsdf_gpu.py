@@ -1,4 +1,5 @@
-"""What the GPU tests of the TSDF volume share (tests/test_gpu_tsdf_cases.py, tests/test_gpu_tsdf_extract.py, tests/test_gpu_tsdf_scene.py):
+"""What the GPU tests of the TSDF volume share (tests/test_gpu_tsdf_cases.py, tests/test_gpu_tsdf_extract.py, tests/test_gpu_tsdf_layouts.py,
+tests/test_gpu_tsdf_scene.py):
 a context whose dense planes a test writes itself (tests/dense_planes.py), and the comparison of a fused volume and its surface with
 the restatement (tests/tsdf_reference.py), word for word."""
 import numpy as np
